@@ -11,10 +11,13 @@ through the C++ host layer and the C-ABI.  Scene data is resident in HBM before 
 ranks (one process per GPU); every step ends with an RCCL all-gather of the RGBA16F bands so that every rank holds the
 full image (the gather of frame i runs while frame i+1 renders).
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step), the run's configuration and
+frame statistics.  --full adds what takes work of its own beyond the headline:
   roofline      for the dominant kernel: what binds it (vector-ALU issue, from the committed SQ counter pass named in profile_tag) next to
                 its HBM roofline: algorithmic bytes per launch (low / high texel bound) / hipEvent-measured launch time vs 8 TB/s
   cpu_baseline  the scalar-C oracle port timed on this box's host cores on a bounded strip of the same frame
+  collective    (N > 1) the exchange step timed alone, and every rank's kernel times
+--dump-outputs DIR writes the image of the last timed step as .npy files (dump_outputs below), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -178,6 +181,25 @@ def hip_backend_path():
     return hip_backend.LIB_PATH
 
 
+DUMP_MAX_PIXELS = 1 << 21      # 32 MB of RGBA f32 + 16 MB of f64 pixel indices: a dump stays under 64 MB
+
+
+def dump_outputs(directory, image_f16):
+    """--dump-outputs: the [H, W, 4] RGBA16F image a caller receives from the last timed step, as float32 (exact).  A frame of up to
+    DUMP_MAX_PIXELS pixels is written whole (image_rgba.npy); a larger one as a fixed, seeded sample of that many pixels (image_rgba_sample.npy,
+    [n, 4]) with their row-major indices (image_rgba_sample_index.npy, float64) — the same pixels in every run of the same frame size."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    img = np.asarray(image_f16, dtype=np.float16).astype(np.float32)
+    n = img.shape[0] * img.shape[1]
+    if n <= DUMP_MAX_PIXELS:
+        np.save(os.path.join(directory, "image_rgba.npy"), img)
+        return
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_PIXELS, replace=False))
+    np.save(os.path.join(directory, "image_rgba_sample.npy"), img.reshape(n, 4)[idx])
+    np.save(os.path.join(directory, "image_rgba_sample_index.npy"), idx.astype(np.float64))
+
+
 def backend_is_rehearsal():
     return os.environ.get("AWSM_BENCH_BACKEND", "nccl") != "nccl"
 
@@ -261,6 +283,9 @@ def main():
     ap.add_argument("--trace", action="store_true", help="add `frame_trace` to the JSON line: per frame of warm-up + timed loop the host time at which step() returned and the "
                     "device-clock times of geometry begin / geometry done / shading done (awsm_hip_frame_trace), ms from the first")
     ap.add_argument("--allow-variant-lib", action="store_true", help="accept an AWSM_HIP_LIB override (A/B builds); the path is printed in the JSON line")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline, CPU baseline (unless --no-cpu-baseline), "
+                    "N > 1: the exchange step alone and per-rank kernel times")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed loop, write the image of the last timed step to DIR as float32 .npy files")
     args = ap.parse_args()
     if os.environ.get("AWSM_HIP_LIB") and not args.allow_variant_lib:
         raise SystemExit("AWSM_HIP_LIB is set: bench.py measures awsm-renderer_amd/libawsm_hip.so; pass --allow-variant-lib for an A/B build")
@@ -496,6 +521,8 @@ def main():
     # round 5 (they used to follow it): the script does this work anyway, and done first it also brings the part out of the idle clock state the seconds of
     # CPU-side scene set-up leave it in — the driver's 20-step run used to be measured on a part still ramping up.  `steps` and
     # `warmup` are exactly what was passed; "frames_before_timed_loop" in the JSON line says what ran before them.
+    # A plain run keeps these frames: the figure of a short run depends on the warm part they leave, and frame_stats and
+    # opaque_route are read from them.  Only --full turns their kernel times into the roofline.
     # (Python's garbage collector is switched off from here to the end of the timed loop, after one collection now: a collection between the profile frames
     # and the warm-up would leave the GPU idle for ~35 ms, and the part's clocks fall back within a few milliseconds of idling.)
     import gc
@@ -546,8 +573,17 @@ def main():
             gc.enable()
         return dt
 
+    def last_image():
+        """--dump-outputs: the image of the last timed step, read before anything renders again (on rank 0: what it gathered)."""
+        if not args.dump_outputs or rank != 0:
+            return None
+        if world == 1:
+            return dev.read_opaque().view(np.float16)      # the library's image of the last submitted frame (waits for it)
+        return image[(frame_no[0] - 1) % n_buf].cpu().numpy()
+
     handoff_mode = dev.stream_handoff()
     dt = timed_loop()
+    output = last_image()
     frame_trace = None
     if args.trace:
         dev_ms, _ = dev.read_frame_trace(args.warmup + args.steps)
@@ -575,6 +611,7 @@ def main():
     if handoff_fault:
         print(f"rank {rank}: a stream hand-off gate timed out during the timed loop; repeating the measurement on hipEvents", file=sys.stderr)
         dt = timed_loop()
+        output = last_image()
     dt_local = dt
     ranks_seen = 1
     gather_alone_ms = None
@@ -586,6 +623,7 @@ def main():
         t = torch.ones(1, dtype=torch.int32, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)           # over RCCL (or the rehearsal backend): how many ranks really took part
         ranks_seen = int(t.item())
+    if world > 1 and args.full:
         # the frame's exchange step by itself (nothing rendering beside it): K collectives back to back on the image buffers
         drain()
         torch.cuda.synchronize()
@@ -631,40 +669,42 @@ def main():
     if st.get("frames_with_dropped_bin_entries", 0) or st.get("bin_overflow_retries", 0):
         raise SystemExit(f"rank {rank}: the timed loop lost geometry or had to replay frames: {st['frames_with_dropped_bin_entries']} dropped, {st['bin_overflow_retries']} replayed")
     rows_mine = H if world == 1 else (y1s - y0s if strips else len(band_rows(H, world, rank)))
-    stats_i = {k: int(round(v)) for k, v in st.items() if not k.startswith("ms_")}
-    stats_i["geometry_cache_frac"] = (st.get("geometry_cache_blocks", 0.0) / st["geometry_blocks"]) if st.get("geometry_blocks") else 0.0
-    alg = algorithmic_bytes(scene, stats_i, rows_mine)
-    dom = max(kernel_ms, key=kernel_ms.get)
-    alg_low = alg.pop("k_shade_low")
-    sec = kernel_ms[dom] * 1e-3
-    achieved = alg[dom] / sec / 1e9 if sec > 0 else 0.0
-    achieved_low = (alg_low if dom == "k_shade" else alg[dom]) / sec / 1e9 if sec > 0 else 0.0
-    # HBM bytes and SQ counters of the dominant kernel come from the committed rocprofv3 passes of this same workload (counters cannot be
-    # read from inside the process): profiles/latest_pmc.json, collected by tools/profile_round.sh — profile_tag says which run.
-    prof = pmc_profile(n_tris, W, H) if (world == 1 and args.config == 4 and not args.msaa and not args.mipmap) else None
-    pk = pmc_kernel(prof, dom)
-    valu = valu_issue(pk, kernel_ms[dom], pmc_mix(prof, dom))
-    # Calibrated (profiles/r04_traffic_calibration.txt, r04_traffic_request_sizes.txt; tools/traffic_calibration.sh, tools/traffic_sizes.sh): on gfx950 EVERY
-    # memory-side read request of these kernels is 128 bytes — an 8-byte scattered texel pair, a 13-lane 16-byte record gather and a streamed key
-    # read alike (TCC_EA0_RDREQ_128B = TCC_EA0_RDREQ; _32B = 0, _64B ~ 0) — while FETCH_SIZE tallies each at 64 bytes.  So traffic = 2 x FETCH_SIZE +
-    # WRITE_SIZE for every access pattern here, not only for wide streams; it is measured at the L2's fabric side and includes Infinity-Cache hits.
-    traffic_raw = pk.get("hbm_read_bytes_raw", 0.0) + pk.get("hbm_write_bytes", 0.0) if pk else None
-    traffic_cal = 2.0 * pk.get("hbm_read_bytes_raw", 0.0) + pk.get("hbm_write_bytes", 0.0) if pk else None
-    roofline = {"bound": "valu_issue" if (valu and valu["frac"] > achieved / HBM_PEAK_GBS) else "hbm",
-                "kernel": ("k_shade_lean" if lean else "k_shade") if dom == "k_shade" else dom,
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "frac_hbm_low": achieved_low / HBM_PEAK_GBS, "frac_hbm_high": achieved / HBM_PEAK_GBS,
-                "frac_valu": valu["frac"] if valu else None,
-                "traffic": traffic_cal, "traffic_raw_counters": traffic_raw,
-                "traffic_note": "2 x FETCH_SIZE + WRITE_SIZE: every read request is 128 B on gfx950 (TCC_EA0_RDREQ_128B), FETCH_SIZE counts 64; L2 fabric side, Infinity-Cache hits included",
-                "frac_fabric": (traffic_cal / (kernel_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic_cal and kernel_ms[dom] > 0) else None,
-                "profile_tag": prof.get("tag") if prof else None,
-                "algorithmic_bytes_per_launch": alg[dom], "algorithmic_bytes_per_launch_low": alg_low if dom == "k_shade" else alg[dom],
-                "launch_ms": kernel_ms[dom], "launch_ms_from": f"hipEvents, mean of the last {len(profile_used)} of the {len(per_frame)} synchronised profile frames (the first ones run while the clocks ramp up)", "valu_issue": valu,
-                "all_kernels_ms": kernel_ms, "all_kernels_algorithmic_bytes": alg}
+    roofline = None
+    if args.full:
+        stats_i = {k: int(round(v)) for k, v in st.items() if not k.startswith("ms_")}
+        stats_i["geometry_cache_frac"] = (st.get("geometry_cache_blocks", 0.0) / st["geometry_blocks"]) if st.get("geometry_blocks") else 0.0
+        alg = algorithmic_bytes(scene, stats_i, rows_mine)
+        dom = max(kernel_ms, key=kernel_ms.get)
+        alg_low = alg.pop("k_shade_low")
+        sec = kernel_ms[dom] * 1e-3
+        achieved = alg[dom] / sec / 1e9 if sec > 0 else 0.0
+        achieved_low = (alg_low if dom == "k_shade" else alg[dom]) / sec / 1e9 if sec > 0 else 0.0
+        # HBM bytes and SQ counters of the dominant kernel come from the committed rocprofv3 passes of this same workload (counters cannot be
+        # read from inside the process): profiles/latest_pmc.json, collected by tools/profile_round.sh — profile_tag says which run.
+        prof = pmc_profile(n_tris, W, H) if (world == 1 and args.config == 4 and not args.msaa and not args.mipmap) else None
+        pk = pmc_kernel(prof, dom)
+        valu = valu_issue(pk, kernel_ms[dom], pmc_mix(prof, dom))
+        # Calibrated (profiles/r04_traffic_calibration.txt, r04_traffic_request_sizes.txt; tools/traffic_calibration.sh, tools/traffic_sizes.sh): on gfx950 EVERY
+        # memory-side read request of these kernels is 128 bytes — an 8-byte scattered texel pair, a 13-lane 16-byte record gather and a streamed key
+        # read alike (TCC_EA0_RDREQ_128B = TCC_EA0_RDREQ; _32B = 0, _64B ~ 0) — while FETCH_SIZE tallies each at 64 bytes.  So traffic = 2 x FETCH_SIZE +
+        # WRITE_SIZE for every access pattern here, not only for wide streams; it is measured at the L2's fabric side and includes Infinity-Cache hits.
+        traffic_raw = pk.get("hbm_read_bytes_raw", 0.0) + pk.get("hbm_write_bytes", 0.0) if pk else None
+        traffic_cal = 2.0 * pk.get("hbm_read_bytes_raw", 0.0) + pk.get("hbm_write_bytes", 0.0) if pk else None
+        roofline = {"bound": "valu_issue" if (valu and valu["frac"] > achieved / HBM_PEAK_GBS) else "hbm",
+                    "kernel": ("k_shade_lean" if lean else "k_shade") if dom == "k_shade" else dom,
+                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "frac_hbm_low": achieved_low / HBM_PEAK_GBS, "frac_hbm_high": achieved / HBM_PEAK_GBS,
+                    "frac_valu": valu["frac"] if valu else None,
+                    "traffic": traffic_cal, "traffic_raw_counters": traffic_raw,
+                    "traffic_note": "2 x FETCH_SIZE + WRITE_SIZE: every read request is 128 B on gfx950 (TCC_EA0_RDREQ_128B), FETCH_SIZE counts 64; L2 fabric side, Infinity-Cache hits included",
+                    "frac_fabric": (traffic_cal / (kernel_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic_cal and kernel_ms[dom] > 0) else None,
+                    "profile_tag": prof.get("tag") if prof else None,
+                    "algorithmic_bytes_per_launch": alg[dom], "algorithmic_bytes_per_launch_low": alg_low if dom == "k_shade" else alg[dom],
+                    "launch_ms": kernel_ms[dom], "launch_ms_from": f"hipEvents, mean of the last {len(profile_used)} of the {len(per_frame)} synchronised profile frames (the first ones run while the clocks ramp up)", "valu_issue": valu,
+                    "all_kernels_ms": kernel_ms, "all_kernels_algorithmic_bytes": alg}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle_lib
         lut_rg = oracle_lib.brdf_lut(64, 64)
         mid = H // 2
@@ -673,9 +713,8 @@ def main():
 
     per_rank = None
     if world > 1:
-        me = {"rank": rank, "device": local_rank, "rows": rows_mine, "loop_s": dt_local, "gather_alone_ms": gather_alone_ms,
-              "kernel_ms": kernel_ms, "covered_pixels": st.get("covered_pixels"), "bin_entries": st.get("bin_entries"),
-              "handoff_faults_in_loop": handoff_in_loop[0]}
+        me = {"rank": rank, "device": local_rank, "rows": rows_mine, "loop_s": dt_local, "covered_pixels": st.get("covered_pixels"), "bin_entries": st.get("bin_entries"),
+              "handoff_faults_in_loop": handoff_in_loop[0], **({"gather_alone_ms": gather_alone_ms, "kernel_ms": kernel_ms} if args.full else {})}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, me)
         dist.barrier()
@@ -708,19 +747,20 @@ def main():
                        "library": os.path.relpath(hip_backend_path(), ROOT)},
             "frame_stats": {k: st[k] for k in ("triangles_in", "triangles_binned", "bin_entries", "covered_pixels", "shade_general_wavefronts",
                                                 "frames_with_dropped_bin_entries", "bin_overflow_retries", "geometry_cache_blocks", "geometry_blocks")},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
+            **({"roofline": roofline, "cpu_baseline": cpu} if args.full else {}),
             # what crosses the boundary as host buffers: `value` is measured with the scene resident; a frame's own uploads are inside it
             "host_to_device": {"first_frame_bytes": first_frame_upload, "first_frame_ms": round(first_frame_ms, 2),
                                "texture_bytes_at_setup": int(sum(int(t.nbytes) for t in scene.textures)),
                                "steady_state_bytes_per_frame": steady_upload[0]},
             **({"collective": {"backend": "rccl" if backend == "nccl" else backend + " (rehearsal: every rank on GPU 0, staged through the host)",
                                "op": "gather to rank 0" if to_root else "all_gather_into_tensor", "bytes_per_rank": rows_out * W * 8,
-                               "alone_ms": max(p["gather_alone_ms"] for p in per_rank), **collective_model(world, rows_out * W * 8, to_root), "launcher": "bench.py (child processes)" if os.environ.get("AWSM_BENCH_SELF_LAUNCHED") else "external (WORLD_SIZE was set)"},
+                               **({"alone_ms": max(p["gather_alone_ms"] for p in per_rank)} if args.full else {}), **collective_model(world, rows_out * W * 8, to_root), "launcher": "bench.py (child processes)" if os.environ.get("AWSM_BENCH_SELF_LAUNCHED") else "external (WORLD_SIZE was set)"},
                 "per_rank": per_rank} if per_rank else {}),
             **({"check": check} if check else {}),
             **({"frame_trace": frame_trace} if frame_trace else {}),
         }
+        if output is not None:
+            dump_outputs(args.dump_outputs, output)
         print(json.dumps(out))
     dev.close()
     r.close()

@@ -169,7 +169,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(msaa, extra, launcher):
         s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
     cmd += [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--width", "640", "--height", "363", "--detail", "0.125",
-            "--tex-scale", "0.0625", "--no-cpu-baseline", "--check", "--profile-frames", "1", "--msaa", str(msaa)] + extra
+            "--tex-scale", "0.0625", "--no-cpu-baseline", "--check", "--profile-frames", "1", "--msaa", str(msaa), "--full"] + extra
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -11,7 +11,7 @@ for mode in "" "--msaa 4 --mipmap" "--static-camera"; do
   for rep in 1 2; do
     for cache in 1 0; do
       echo -n "cache $cache $mode: "
-      AWSM_GEOMETRY_CACHE=$cache timeout -k 10 200 python3 bench.py --gpus 1 --no-cpu-baseline --steps 200 --warmup 20 $mode 2>/dev/null | fps || exit 1
+      AWSM_GEOMETRY_CACHE=$cache timeout -k 10 200 python3 bench.py --gpus 1 --full --no-cpu-baseline --steps 200 --warmup 20 $mode 2>/dev/null | fps || exit 1
     done
   done
 done

@@ -7,7 +7,7 @@ for spec in "$@"; do
   name=${spec%%=*}; envs=${spec#*=}
   (
     IFS=','; for kv in $envs; do export "$kv"; done; unset IFS
-    python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --profile-frames 3 $AB_BENCH_ARGS > $OUT/$name.$rep.json 2> $OUT/$name.$rep.err
+    python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --profile-frames 3 $AB_BENCH_ARGS > $OUT/$name.$rep.json 2> $OUT/$name.$rep.err
   )
   python3 - <<PY
 import json

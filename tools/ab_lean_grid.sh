@@ -3,7 +3,7 @@ mkdir -p gpurun_out/r2i; : > gpurun_out/r2i/ab.log
 run() {  # lib per_cu extra...
   lib=$1; n=$2; shift 2
   echo "== $lib per_cu $n $*" >> gpurun_out/r2i/ab.log
-  AWSM_HIP_LIB=$lib AWSM_LEAN_WGS_PER_CU=$n timeout -k 10 200 python bench.py --allow-variant-lib --steps 300 --warmup 30 --no-cpu-baseline "$@" 2>&1 | python -c "import sys,json
+  AWSM_HIP_LIB=$lib AWSM_LEAN_WGS_PER_CU=$n timeout -k 10 200 python bench.py --full --allow-variant-lib --steps 300 --warmup 30 --no-cpu-baseline "$@" 2>&1 | python -c "import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         j=json.loads(l); print(j['value'], j['ms_per_step'], j['roofline']['launch_ms'], j['roofline'].get('all_kernels_ms'))" >> gpurun_out/r2i/ab.log

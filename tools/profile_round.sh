@@ -6,7 +6,7 @@ TAG=${1:-r01_x}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 tail -c 600 $OUT/bench.json; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --no-overlap --no-cpu-baseline --steps 100 --warmup 10 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 2
 echo "stats done"
