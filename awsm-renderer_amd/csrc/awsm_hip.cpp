@@ -28,6 +28,7 @@ void awsm_launch_transform(const DevScene* sc, const FrameDev* f, uint32_t n_blo
 void awsm_launch_hud_merge(const unsigned long long* world, const unsigned long long* hud, unsigned long long* out, size_t first, size_t n, hipStream_t s);
 void awsm_launch_transform_forward(const DevScene* sc, const FrameDev* f, uint32_t n_blocks, hipStream_t s);
 void awsm_launch_forward(const DevScene* sc, const FrameDev* f, hipStream_t s);
+void awsm_launch_post(const void* args, uint32_t flags, uint32_t msaa, void* bloom_a, void* bloom_b, hipStream_t s);
 void awsm_launch_upload_words(void* dst, const void* src_pinned, uint32_t n_words, hipStream_t s);
 void awsm_launch_bin_count(const FrameDev* f, hipStream_t s);
 void awsm_launch_bin_scan(const FrameDev* f, hipStream_t s);
@@ -199,6 +200,14 @@ struct AwsmHipCtx {
     bool transparent_done = false, hud_transparent_done = false;
     FrameBufs htr[kSlots];
     DevBuf comp16, comp32;       // composite image (after the transparent pass) + parity tap
+    // the effects + display passes (awsm_hip_post_pass): the display image per frame slot (or the caller's), the effects image (parity tap only),
+    // the bloom chain's two f16 images and the per-pixel DoF terms — the last four per context: a post pass waits for the other slot's to end
+    DevBuf display8[kSlots], effects16, bloom_a, bloom_b, dof_lc, dof_blur;
+    void* bound_display = nullptr;
+    size_t bound_display_bytes = 0;
+    void* last_display = nullptr;     // what the last post pass wrote
+    bool post_done = false;           // a post pass of the current frame was enqueued: awsm_hip_frame_end enqueues it again after replaying the frame
+    AwsmPostParams post_params{};     // ... with these parameters
     DevBuf lights_pre[kSlots];        // per frame slot: per-light constants (k_resolve_draws), sized with the lights buffer
     void* bound_comp = nullptr;
     size_t bound_comp_bytes = 0;
@@ -1106,6 +1115,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->tex) fr(b);
     for (auto& b : c->merged_vis) fr(b);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
+    for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 4 * kSlots; k++) {
         FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : c->htr[k - 3 * kSlots]));
         fr(b.vis); fr(b.wpos); fr(b.frag_rec); fr(b.frag_color); fr(b.frag_first); fr(b.tex_slots); fr(b.draw_mat); fr(b.clip); fr(b.nrm); fr(b.tan); fr(b.tri_rec); fr(b.tri_flags); fr(b.tri_shade); fr(b.draw_lean); fr(b.draws_dev); fr(b.draw_shade); fr(b.tile_count); fr(b.tile_offset);
@@ -1202,7 +1212,8 @@ int awsm_hip_resize(AwsmHipCtx* c, uint32_t width, uint32_t height, uint32_t msa
     c->width = width; c->height = height;
     c->y0 = c->y1 = 0;
     c->band_n = 1; c->band_r = 0; c->band_compact = 0;
-    c->geometry_done = c->opaque_done = c->transparent_done = c->hud_transparent_done = false;
+    c->geometry_done = c->opaque_done = c->transparent_done = c->hud_transparent_done = c->post_done = false;
+    c->last_display = nullptr;      // the images are sized for the old frame
     return AWSM_OK;
 }
 
@@ -1458,7 +1469,7 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
     ht.mark("geometry_pass: reserve + draw-list upload");
     if ((rc = enqueue_geometry(c))) return rc;
     c->camera_written_since_snapshot = false;
-    c->geometry_done = true; c->opaque_done = false; c->transparent_done = false; c->hud_transparent_done = false; c->hud_geometry_done = false;
+    c->geometry_done = true; c->opaque_done = false; c->transparent_done = false; c->hud_transparent_done = false; c->hud_geometry_done = false; c->post_done = false;
     return AWSM_OK;
 }
 
@@ -1698,6 +1709,7 @@ int awsm_hip_frame_flush(AwsmHipCtx* c) {
     return AWSM_OK;
 }
 
+static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& p);
 int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1760,6 +1772,7 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
                 if (rc) return rc;
             }
         }
+        if (c->post_done && (rc = enqueue_post(c, c->post_params))) return rc;     // the effects + display of the replayed images (and fragment lists)
     }
     if (still_over) return fail(c, AWSM_ERR_DEVICE, "bin / fragment list overflow persisted after retries");
     if (out) {
@@ -1966,6 +1979,85 @@ int awsm_hip_read_composite_f32(AwsmHipCtx* c, float* out) {
     HIPCHK(c, hipMemcpy(out, c->comp32.ptr, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
+
+// EffectsRenderPass::render + DisplayRenderPass::render (render.rs:339-356); the kernels and the contract: kernels_post.hip, DESIGN.md §11
+int awsm_hip_post_pass(AwsmHipCtx* c, const AwsmPostParams* p) {
+    if (!c || !p) return AWSM_ERR_INVALID_ARGUMENT;
+    if (p->struct_size != sizeof(AwsmPostParams)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: struct_size %u, this library's AwsmPostParams is %zu bytes", p->struct_size, sizeof(AwsmPostParams));
+    if (p->tonemapping > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: tonemapping %u (0 None, 1 KhronosNeutralPbr, 2 Aces)", p->tonemapping);
+    if (p->flags & ~(AWSM_POST_SMAA | AWSM_POST_BLOOM | AWSM_POST_DOF)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: unknown flags 0x%x", p->flags);
+    const bool sharded = c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height));
+    if (sharded) return fail(c, AWSM_ERR_UNSUPPORTED, "post_pass on a sharded context: the SMAA / bloom / DoF stencils read neighbouring rows (no halo exchange)");
+    if (c->width == 0 || !c->geometry_done || !c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "post_pass needs the frame's opaque pass first");
+    return enqueue_post(c, *p);
+}
+
+// the post pass of the current frame with the context's images as they are bound now; awsm_hip_frame_end enqueues it again after a replay
+static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& pp) {
+    const AwsmPostParams* p = &pp;
+    const size_t px = (size_t)c->width * c->height;
+    if (c->bound_display && c->bound_display_bytes < px * 4) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: bound display image holds %zu bytes, the frame needs %zu", c->bound_display_bytes, px * 4);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = AWSM_OK;
+    if (!c->bound_display && (rc = dev_reserve(c, c->display8[c->slot], px * 4))) return rc;
+    const bool bloom = p->flags & AWSM_POST_BLOOM, dof = p->flags & AWSM_POST_DOF, tap = c->flags & AWSM_CFG_PARITY_TAP;
+    if (tap && (rc = dev_reserve(c, c->effects16, px * 8))) return rc;
+    if (bloom && ((rc = dev_reserve(c, c->bloom_a, px * 8)) || (rc = dev_reserve(c, c->bloom_b, px * 8)))) return rc;
+    if (dof && ((rc = dev_reserve(c, c->dof_lc, px * 8)) || (rc = dev_reserve(c, c->dof_blur, px * 16)))) return rc;
+    PostArgs a{};
+    a.width = c->width; a.height = c->height;
+    if (c->transparent_done) a.src = (const uint2*)(c->bound_comp ? c->bound_comp : c->comp16.ptr);
+    else a.src = (const uint2*)(c->bound_out ? (const uint8_t*)c->bound_out - (size_t)c->out_first_row * c->width * 8 : (const uint8_t*)c->out16[c->slot].ptr);
+    a.vis = (const unsigned long long*)FB(c).vis.ptr;       // the world's keys (not the merged hud ones): hud_depth plays no part
+    const FrameBufs& t = c->tr[c->slot];
+    if (dof && c->transparent_done && c->tr_total_tris[0] && t.frag_first.ptr) {
+        a.frag_first = (const uint32_t*)t.frag_first.ptr; a.frag_rec = (const uint4*)t.frag_rec.ptr; a.frag_cap = t.frag_cap; a.tri_rec = (const TriRec*)t.tri_rec.ptr;
+    }
+    a.camera = (const float*)FB(c).camera.ptr;
+    a.dof_lc = (float2*)c->dof_lc.ptr; a.dof_blur = (float4*)c->dof_blur.ptr;
+    a.effects = tap ? (uint2*)c->effects16.ptr : nullptr;
+    a.display = (uint32_t*)(c->bound_display ? c->bound_display : c->display8[c->slot].ptr);
+    a.tonemap = p->tonemapping; a.dof = dof ? 1u : 0u;
+    a.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr; a.frame_serial = c->frame_serial;   // a frame a hand-off gate dropped is not post-processed
+    if (!a.src || !a.vis || !a.camera) return fail(c, AWSM_ERR_NOT_READY, "post_pass: the frame's images are missing");
+    hipStream_t ss = shade_stream_of(c);          // in order after the opaque / transparent passes of the frame
+    // the bloom / DoF scratch and the effects image are per context: behind the other slot's passes (its post pass among them)
+    if (c->overlap && c->shade_recorded[prev_slot(c)]) HIPCHK(c, wait_prev_slot(c, ss));
+    awsm_launch_post(&a, p->flags, c->msaa == 4 ? 4u : 1u, c->bloom_a.ptr, c->bloom_b.ptr, ss);
+    HIPCHK(c, hipGetLastError());
+    if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));       // the slot's next geometry pass waits for this too
+    c->last_display = a.display;
+    c->post_params = pp;
+    c->post_done = true;
+    return AWSM_OK;
+}
+
+int awsm_hip_read_display(AwsmHipCtx* c, uint8_t* out) {
+    if (!c || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!c->last_display) return fail(c, AWSM_ERR_NOT_READY, "read_display before post_pass");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    HIPCHK(c, hipMemcpy(out, c->last_display, (size_t)c->width * c->height * 4, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+int awsm_hip_read_effects(AwsmHipCtx* c, uint16_t* out) {
+    if (!c || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!(c->flags & AWSM_CFG_PARITY_TAP) || !c->effects16.ptr || !c->last_display) return fail(c, AWSM_ERR_NOT_READY, "read_effects needs AWSM_CFG_PARITY_TAP and a post_pass");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    HIPCHK(c, hipMemcpy(out, c->effects16.ptr, (size_t)c->width * c->height * 8, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+int awsm_hip_bind_display(AwsmHipCtx* c, void* device_ptr, size_t bytes) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    if (device_ptr && bytes == 0) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "bind_display: zero-sized image");
+    c->bound_display = device_ptr; c->bound_display_bytes = bytes;
+    return AWSM_OK;
+}
+
+void* awsm_hip_display_device_ptr(AwsmHipCtx* c) { return c ? c->last_display : nullptr; }
 
 int awsm_hip_read_transformed_forward(AwsmHipCtx* c, float* clip_out, float* nt_out, float* wpos_out, uint32_t max_vertices) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;

@@ -255,6 +255,28 @@ struct FrameDev {
     uint32_t frag_cap;
 };
 
+// The effects + display passes (kernels_post.hip, awsm_hip_post_pass): what one launch sequence reads and writes.
+struct PostArgs {
+    uint32_t width, height;
+    const uint2* src;                    // composite (or the opaque image when the frame had no transparent pass): RGBA16F
+    const unsigned long long* vis;       // the world geometry pass's keys (x4 with MSAA)
+    const uint32_t* frag_first;          // the world transparent pass's fragment lists (null: no transparent fragments this frame)
+    const uint4* frag_rec;
+    uint32_t frag_cap;
+    const TriRec* tri_rec;
+    const float* camera;                 // the frame's camera snapshot (512 B): proj at floats 16..31, viewport at 120..123, dof at 124..125
+    float2* dof_lc;                      // per pixel: linear depth, CoC
+    float4* dof_blur;                    // per pixel: disk blur rgb, blend factor (w < 0: CoC < 0.5, no blur)
+    const uint2* stage_in;               // bloom: the previous stage (f16 RGBA)
+    uint2* stage_out;                    // bloom: this stage's output; the last stage: the effects image (may be null there)
+    uint2* effects;                      // bloom off: the effects image (null: not kept)
+    uint32_t* display;                   // RGBA8
+    uint32_t tonemap;                    // 0 None, 1 KhronosNeutralPbr, 2 Aces
+    uint32_t dof;
+    const uint32_t* poison;              // FrameDev.poison / frame_serial: a frame whose hand-off gate timed out is dropped here too
+    uint32_t frame_serial;
+};
+
 #ifdef __HIPCC__
 // A hand-off gate that gave up (its signal never came within the time budget) has poisoned the frame it guarded: its kernels must not run on
 // buffers that are half written, or still being read.  Wave-uniform, one scalar load.

@@ -32,7 +32,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_read_visibility_unpacked", "awsm_hip_read_opaque", "awsm_hip_read_opaque_f32", "awsm_hip_read_transformed",
            "awsm_hip_device_info", "awsm_hip_transparent_pass", "awsm_hip_read_composite", "awsm_hip_read_composite_f32", "awsm_hip_bind_composite",
            "awsm_hip_read_transformed_forward", "awsm_hip_visibility_digest", "awsm_hip_bind_output_rows", "awsm_hip_env_cube_upload", "awsm_hip_bind_opaque_source", "awsm_hip_msaa_halo_bands", "awsm_hip_msaa_halo_export", "awsm_hip_msaa_halo_bind",
-           "awsm_hip_frame_trace", "awsm_hip_read_frame_trace", "awsm_hip_hud_geometry_pass", "awsm_hip_hud_transparent_pass"]
+           "awsm_hip_frame_trace", "awsm_hip_read_frame_trace", "awsm_hip_hud_geometry_pass", "awsm_hip_hud_transparent_pass",
+           "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr"]
 
 
 class AwsmConfig(C.Structure):
@@ -46,6 +47,14 @@ class AwsmDraw(C.Structure):
 
 class AwsmOpaqueParams(C.Structure):
     _fields_ = [("mipmap", C.c_uint32), ("has_opaque", C.c_uint32)]
+
+
+class AwsmPostParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("tonemapping", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+AWSM_POST_SMAA, AWSM_POST_BLOOM, AWSM_POST_DOF = 1, 2, 4
+TONEMAP = {"none": 0, "khronos": 1, "aces": 2}
 
 
 class AwsmSampler(C.Structure):
@@ -134,6 +143,12 @@ def load_library():
     lib.awsm_hip_hud_geometry_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.awsm_hip_hud_transparent_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.awsm_hip_frame_trace.argtypes = [C.c_void_p, C.c_uint32]
+    lib.awsm_hip_post_pass.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_display.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_effects.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_bind_display.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.awsm_hip_display_device_ptr.restype = C.c_void_p
+    lib.awsm_hip_display_device_ptr.argtypes = [C.c_void_p]
     lib.awsm_hip_read_frame_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
@@ -413,6 +428,29 @@ class HipDevice:
 
     def bind_composite(self, device_ptr: Optional[int], nbytes: int = 0):
         self._chk(self.lib.awsm_hip_bind_composite(self.ctx, device_ptr, nbytes), "bind_composite")
+
+    # ---- effects + display passes (awsm_hip_post_pass) ----
+    def post_pass(self, tonemapping: int = 1, smaa: bool = False, bloom: bool = False, dof: bool = False, struct_size: Optional[int] = None):
+        """Effects pass + display pass of the current frame (after opaque_pass / transparent_pass, before the next geometry_pass)."""
+        flags = (AWSM_POST_SMAA if smaa else 0) | (AWSM_POST_BLOOM if bloom else 0) | (AWSM_POST_DOF if dof else 0)
+        p = AwsmPostParams(C.sizeof(AwsmPostParams) if struct_size is None else struct_size, tonemapping, flags, 0)
+        self._chk(self.lib.awsm_hip_post_pass(self.ctx, C.byref(p)), "post_pass")
+
+    def read_display(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._chk(self.lib.awsm_hip_read_display(self.ctx, out.ctypes.data_as(C.c_void_p)), "read_display")
+        return out
+
+    def read_effects(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), dtype=np.uint16)
+        self._chk(self.lib.awsm_hip_read_effects(self.ctx, out.ctypes.data_as(C.c_void_p)), "read_effects")
+        return out
+
+    def bind_display(self, device_ptr: Optional[int], nbytes: int = 0):
+        self._chk(self.lib.awsm_hip_bind_display(self.ctx, device_ptr, nbytes), "bind_display")
+
+    def display_device_ptr(self) -> Optional[int]:
+        return self.lib.awsm_hip_display_device_ptr(self.ctx)
 
     def read_transformed_forward(self, n_vertices: int):
         clip = np.zeros((max(1, n_vertices), 4), dtype=np.float32)

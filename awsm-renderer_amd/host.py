@@ -96,6 +96,9 @@ def load_library():
         "awsm_host_set_shard_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_set_shard_bands": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_set_render_timings": (C.c_int, [vp, C.c_int]),
         "awsm_host_pick": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
         "awsm_host_set_anti_aliasing": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+        "awsm_host_set_post_processing": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_int]),
+        "awsm_host_clear_post_processing": (C.c_int, [vp]),
+        "awsm_host_camera_set_dof": (C.c_int, [vp, C.c_float, C.c_float]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
         "awsm_host_texture_insert_kind": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_update_transforms": (C.c_int, [vp]),
         "awsm_host_render": (C.c_int, [vp, C.c_int, vp]), "awsm_host_mirror": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
@@ -338,6 +341,19 @@ class Host:
     def set_anti_aliasing(self, msaa_sample_count: int = 0, mipmap: bool = False):
         """AwsmRenderer::set_anti_aliasing: msaa 0 (None) or 4, gradient mipmaps on/off (the reference's default: 4, True)."""
         self._chk(self.lib.awsm_host_set_anti_aliasing(self.h, msaa_sample_count, 1 if mipmap else 0), "set_anti_aliasing")
+
+    def set_post_processing(self, tonemapping: int = 1, bloom: bool = False, dof: bool = False, smaa: bool = False):
+        """AwsmRenderer::set_post_processing + AntiAliasing.smaa: render() then ends with the effects + display passes (off by default here;
+        the reference's default is KhronosNeutralPbr (1) without bloom or DoF).  tonemapping: 0 None, 1 KhronosNeutralPbr, 2 Aces."""
+        self._chk(self.lib.awsm_host_set_post_processing(self.h, tonemapping, int(bloom), int(dof), int(smaa)), "set_post_processing")
+
+    def clear_post_processing(self):
+        """No post pass again (this library's default)."""
+        self._chk(self.lib.awsm_host_clear_post_processing(self.h), "clear_post_processing")
+
+    def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
+        """CameraMatrices.focus_distance / .aperture (camera bytes 496-503; the reference's defaults 10.0 and 5.6)."""
+        self._chk(self.lib.awsm_host_camera_set_dof(self.h, focus_distance, aperture), "camera_set_dof")
 
     def pick(self, x: int, y: int):
         """AwsmRenderer::pick: the MeshKey under pixel (x, y) of the last rendered frame, or None (PickResult::Miss)."""
@@ -609,6 +625,15 @@ class Renderer:
 
     def render(self, sync: bool = True):
         return self.host.render(sync)
+
+    def set_post_processing(self, tonemapping: int = 1, bloom: bool = False, dof: bool = False, smaa: bool = False):
+        self.host.set_post_processing(tonemapping, bloom, dof, smaa)
+
+    def clear_post_processing(self):
+        self.host.clear_post_processing()
+
+    def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
+        self.host.camera_set_dof(focus_distance, aperture)
 
     def close(self):
         self.host.close()

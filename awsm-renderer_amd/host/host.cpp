@@ -62,6 +62,7 @@ struct Backend {
     int (*hud_geometry_pass)(AwsmHipCtx*, const AwsmDraw*, uint32_t) = nullptr;
     int (*hud_transparent_pass)(AwsmHipCtx*, const AwsmDraw*, uint32_t) = nullptr;
     int (*frame_end)(AwsmHipCtx*, AwsmFrameStats*) = nullptr;
+    int (*post_pass)(AwsmHipCtx*, const AwsmPostParams*) = nullptr;     // optional: a backend without it cannot post-process
 };
 
 struct Transform { Vec3 t; Quat r; Vec3 s; };
@@ -188,6 +189,11 @@ struct AwsmHost {
     // ---- camera.rs ----
     uint8_t camera_raw[512] = {};
     bool camera_dirty = true, camera_created = false, have_camera = false;
+    float dof_params[2] = {0.0f, 0.0f};        // focus_distance, aperture (camera bytes 496-503): 0, 0 until awsm_host_camera_set_dof
+    // ---- post_process.rs + AntiAliasing.smaa: off until awsm_host_set_post_processing ----
+    bool post_on = false;
+    AwsmPostParams post{};
+    bool sharded = false;                      // awsm_host_set_shard_rows / _bands gave this host a part of the frame (the post pass needs all of it)
     Mat4 cam_view = mat4_identity(), cam_proj = mat4_identity();
     uint32_t frame_count = 0;
     uint32_t width = 0, height = 0;
@@ -501,6 +507,7 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
               load_sym(h.get(), b.hud_geometry_pass, "awsm_hip_hud_geometry_pass") && load_sym(h.get(), b.hud_transparent_pass, "awsm_hip_hud_transparent_pass") &&
               load_sym(h.get(), b.frame_end, "awsm_hip_frame_end");
     if (!ok) { fprintf(stderr, "awsm_host: %s\n", h->last_error.c_str()); dlclose(b.dl); return AWSM_ERR_NOT_READY; }
+    b.post_pass = reinterpret_cast<decltype(b.post_pass)>(dlsym(b.dl, "awsm_hip_post_pass"));      // optional (awsm_host_set_post_processing)
     if (b.abi_version() != AWSM_HIP_ABI_VERSION) { dlclose(b.dl); return AWSM_ERR_INVALID_ARGUMENT; }
     AwsmConfig cfg{};
     cfg.struct_size = sizeof cfg; cfg.abi_version = AWSM_HIP_ABI_VERSION; cfg.device = device; cfg.flags = cfg_flags; cfg.stream = stream;
@@ -932,7 +939,7 @@ int awsm_host_camera_update(AwsmHost* h, const float view[16], const float proje
     }
     const float viewport[4] = {0.0f, 0.0f, (float)h->width, (float)h->height};
     memcpy(o + 480, viewport, 16);
-    const float dof[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float dof[4] = {h->dof_params[0], h->dof_params[1], 0.0f, 0.0f};
     memcpy(o + 496, dof, 16);
     h->cam_view = v; h->cam_proj = p; h->have_camera = true; h->camera_dirty = true;
     return AWSM_OK;
@@ -961,7 +968,14 @@ int awsm_host_set_anti_aliasing(AwsmHost* h, uint32_t msaa_sample_count, uint32_
     h->msaa_sample_count = msaa_sample_count;
     return h->width ? awsm_host_resize(h, h->width, h->height) : AWSM_OK;
 }
-int awsm_host_set_shard_rows(AwsmHost* h, uint32_t y0, uint32_t y1) { int rc = h->be.set_shard_rows(h->ctx, y0, y1); return rc ? dev_fail(h, rc, "set_shard_rows") : AWSM_OK; }
+int awsm_host_set_shard_rows(AwsmHost* h, uint32_t y0, uint32_t y1) {
+    const bool part = !(y0 == 0 && (y1 == 0 || y1 >= h->height));
+    if (part && h->post_on) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shard_rows: post-processing is on and needs the whole frame (awsm_host_clear_post_processing first)");
+    int rc = h->be.set_shard_rows(h->ctx, y0, y1);
+    if (rc) return dev_fail(h, rc, "set_shard_rows");
+    h->sharded = part;
+    return AWSM_OK;
+}
 // picker.rs:55-121: PickResult::Hit(MeshKey) / Miss for the pixel under the cursor, from the last rendered frame
 int awsm_host_pick(AwsmHost* h, int32_t x, int32_t y, uint32_t* hit, uint64_t* mesh_key) {
     if (!h || !hit || !mesh_key) return AWSM_ERR_INVALID_ARGUMENT;
@@ -973,7 +987,13 @@ int awsm_host_pick(AwsmHost* h, int32_t x, int32_t y, uint32_t* hit, uint64_t* m
     return AWSM_OK;
 }
 int awsm_host_set_render_timings(AwsmHost* h, int enabled) { int rc = h->be.set_stage_timers(h->ctx, enabled); return rc ? dev_fail(h, rc, "set_stage_timers") : AWSM_OK; }
-int awsm_host_set_shard_bands(AwsmHost* h, uint32_t n, uint32_t r, uint32_t compact) { int rc = h->be.set_shard_bands(h->ctx, n, r, compact); return rc ? dev_fail(h, rc, "set_shard_bands") : AWSM_OK; }
+int awsm_host_set_shard_bands(AwsmHost* h, uint32_t n, uint32_t r, uint32_t compact) {
+    if (n > 1 && h->post_on) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shard_bands: post-processing is on and needs the whole frame (awsm_host_clear_post_processing first)");
+    int rc = h->be.set_shard_bands(h->ctx, n, r, compact);
+    if (rc) return dev_fail(h, rc, "set_shard_bands");
+    h->sharded = n > 1;
+    return AWSM_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ frame
 int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes.rs:872-939
@@ -1085,7 +1105,37 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     if (h->has_transparent_meshes || h->has_hud_meshes) { if ((rc = h->be.transparent_pass(h->ctx, h->last_transparent_draws.data(), (uint32_t)h->last_transparent_draws.size()))) return dev_fail(h, rc, "transparent_pass"); }
     // ---- the HUD transparent pass over the composite (render.rs:301-312) ----
     if (h->has_hud_meshes && (rc = h->be.hud_transparent_pass(h->ctx, h->last_hud_transparent_draws.data(), (uint32_t)h->last_hud_transparent_draws.size()))) return dev_fail(h, rc, "hud_transparent_pass");
+    // ---- the effects + display passes (render.rs:339-356), when post-processing was turned on ----
+    if (h->post_on && (rc = h->be.post_pass(h->ctx, &h->post))) return dev_fail(h, rc, "post_pass");
     if (sync) { if ((rc = h->be.frame_end(h->ctx, stats))) return dev_fail(h, rc, "frame_end"); }   // gpu.submit_commands (render.rs:370)
+    return AWSM_OK;
+}
+
+// AwsmRenderer::set_post_processing (post_process.rs) + AntiAliasing.smaa (anti_alias.rs): from now on awsm_host_render ends with the post pass
+int awsm_host_set_post_processing(AwsmHost* h, uint32_t tonemapping, int bloom, int dof, int smaa) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.post_pass) return fail(h, AWSM_ERR_UNSUPPORTED, "set_post_processing: the backend library has no awsm_hip_post_pass");
+    if (tonemapping > 2u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_post_processing: tonemapping %u (0 None, 1 KhronosNeutralPbr, 2 Aces)", tonemapping);
+    if (h->sharded) return fail(h, AWSM_ERR_UNSUPPORTED, "set_post_processing: this host renders a shard of the frame; the post pass needs all of it");
+    h->post.struct_size = sizeof(AwsmPostParams); h->post.tonemapping = tonemapping; h->post.reserved = 0;
+    h->post.flags = (smaa ? AWSM_POST_SMAA : 0u) | (bloom ? AWSM_POST_BLOOM : 0u) | (dof ? AWSM_POST_DOF : 0u);
+    h->post_on = true;
+    return AWSM_OK;
+}
+
+// back to no post pass (this library's default; the reference always runs the effects and display passes)
+int awsm_host_clear_post_processing(AwsmHost* h) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    h->post_on = false;
+    return AWSM_OK;
+}
+
+// CameraMatrices.focus_distance / .aperture (camera.rs:40-52, written at bytes 496-503 by camera.rs:200-215)
+int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    h->dof_params[0] = focus_distance; h->dof_params[1] = aperture;
+    memcpy(h->camera_raw + 496, h->dof_params, 8);
+    h->camera_dirty = true;
     return AWSM_OK;
 }
 

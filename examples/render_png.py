@@ -3,7 +3,9 @@
 
     python examples/render_png.py {box,helmet,skinned,atrium,zoo,instanced,transparent} out.png [--width W --height H --msaa 4 --mipmap]
 
-The output image of the opaque pass is linear HDR RGBA16F; the PNG is Reinhard tone-mapped and gamma-encoded for viewing.
+The output image of the opaque pass is linear HDR RGBA16F; the PNG is Reinhard tone-mapped and gamma-encoded for viewing.  With any of
+--tonemap {khronos,aces,none}, --bloom, --dof, --smaa the frame ends with the effects + display passes instead, and the PNG is the device's
+RGBA8 display image as it stands (--dof uses the reference's focus distance 10 and aperture 5.6 unless --focus / --aperture say otherwise).
 """
 import argparse
 import os
@@ -25,6 +27,12 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--msaa", type=int, default=0, choices=(0, 4))
     ap.add_argument("--mipmap", action="store_true")
+    ap.add_argument("--tonemap", choices=["khronos", "aces", "none"], help="run the post pass with this tone map (the reference's default: khronos)")
+    ap.add_argument("--bloom", action="store_true")
+    ap.add_argument("--dof", action="store_true")
+    ap.add_argument("--smaa", action="store_true")
+    ap.add_argument("--focus", type=float, default=10.0)
+    ap.add_argument("--aperture", type=float, default=5.6)
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -37,8 +45,21 @@ def main():
         gltf = os.path.splitext(a.out)[0] + ".glb"
         gltf_export.write_glb(sc, gltf)
     r = Renderer(sc, msaa=a.msaa, mipmap=a.mipmap, gltf=gltf)
+    post = a.tonemap is not None or a.bloom or a.dof or a.smaa
+    if post:
+        from awsm_renderer_amd.hip_backend import TONEMAP
+        r.set_post_processing(TONEMAP[a.tonemap or "khronos"], bloom=a.bloom, dof=a.dof, smaa=a.smaa)
+        if a.dof:
+            r.camera_set_dof(a.focus, a.aperture)
     stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
+    if post:
+        rgba = dev.read_display()
+        r.close()
+        from PIL import Image
+        Image.fromarray(rgba[..., :3]).save(a.out)
+        print(f"{a.out}: {W}x{H}, post pass {a.tonemap or 'khronos'} bloom={a.bloom} dof={a.dof} smaa={a.smaa}, the device's RGBA8 display image")
+        return
     final = dev.read_composite() if stats["forward_triangles"] else dev.read_opaque()      # the image after the transparent pass, when the scene has one
     img = final.view(np.float16).astype(np.float32)[..., :3]
     r.close()

@@ -379,6 +379,41 @@ int awsm_hip_bind_composite(AwsmHipCtx* ctx, void* device_ptr, size_t bytes);
  * {world N xyz, pad, world T xyzw} (32 B), world position xyz1 (16 B) == vert_main outputs (material_transparent_wgsl/vertex.wgsl) */
 int awsm_hip_read_transformed_forward(AwsmHipCtx* ctx, float* clip_out, float* normal_tangent_out, float* world_pos_out, uint32_t max_vertices);
 int awsm_hip_read_opaque_f32(AwsmHipCtx* ctx, float* rgba32f_out);  /* needs AWSM_CFG_PARITY_TAP */
+
+/* ---- the effects pass + the display pass of the current frame (crates/renderer/src/render.rs:339-356):
+ * EffectsRenderPass::render (render_passes/effects/{render_pass,pipeline}.rs, effects_wgsl/compute.wgsl + helpers/{smaa,bloom,dof}.wgsl) then
+ * DisplayRenderPass::render (render_passes/display/render_pass.rs, display_wgsl/fragment.wgsl + helpers/tonemap.wgsl, shared_wgsl/color_space.wgsl).
+ * tonemapping: ToneMapping (post_process.rs) 0 None, 1 KhronosNeutralPbr (the reference's default), 2 Aces.
+ * flags: PostProcessing.bloom / .dof (post_process.rs) and AntiAliasing.smaa (anti_alias.rs).
+ * The effects pass always runs: SMAA, then DoF, stored as vec4(rgb, 1.0) in RGBA16F; with bloom it is five dispatches (extract, three blurs,
+ * blend), each compiled with the SMAA and DoF flags — so SMAA has no effect under bloom and DoF mixes into every bloom stage (the reference's
+ * quirks, kept).  DoF reads the world depth as the transparent pass left it (min over the MSAA samples) and camera bytes 496-503
+ * (focus_distance, aperture: camera.rs:200-215).  The display pass tone-maps the effects RGB, encodes sRGB and writes 8-bit RGBA (alpha 1.0).
+ * Where WebGPU leaves it open (edge texels, float -> unorm8, the blur tables, operation order, f16 at every former dispatch boundary) the
+ * rules are DESIGN.md §11's.
+ * Valid from the point where the frame's opaque pass (and its transparent passes, if any) are enqueued until the next geometry pass, also
+ * after awsm_hip_frame_end.  Reads the composite when the frame ran awsm_hip_transparent_pass, else the opaque image.  Enqueued on the shade
+ * stream; with AWSM_CFG_OVERLAP_FRAMES the slot's images and depth are read before a later geometry pass reuses the slot.
+ * AWSM_ERR_UNSUPPORTED on a sharded context (row strips or bands: the stencils need neighbouring rows), AWSM_ERR_NOT_READY before the opaque
+ * pass, AWSM_ERR_INVALID_ARGUMENT for a struct_size other than sizeof(AwsmPostParams), a tonemapping value above 2 or unknown flags. ---- */
+typedef struct AwsmPostParams {
+    uint32_t struct_size;   /* sizeof(AwsmPostParams) */
+    uint32_t tonemapping;   /* 0 None, 1 KhronosNeutralPbr, 2 Aces */
+    uint32_t flags;         /* AWSM_POST_* */
+    uint32_t reserved;      /* 0 */
+} AwsmPostParams;
+#define AWSM_POST_SMAA 1u
+#define AWSM_POST_BLOOM 2u
+#define AWSM_POST_DOF 4u
+int awsm_hip_post_pass(AwsmHipCtx* ctx, const AwsmPostParams* p);
+/* the display image of the last post pass: width*height*4 bytes, R G B A byte order, row 0 first (synchronous) */
+int awsm_hip_read_display(AwsmHipCtx* ctx, uint8_t* rgba8_out);
+/* the effects image of the last post pass: RGBA16F, width*height*8 bytes.  Needs AWSM_CFG_PARITY_TAP (the effects image need not exist otherwise). */
+int awsm_hip_read_effects(AwsmHipCtx* ctx, uint16_t* rgba16f_out);
+/* the display image's memory (width*height*4 bytes, checked when the post pass is enqueued); NULL = internal, one image per frame slot */
+int awsm_hip_bind_display(AwsmHipCtx* ctx, void* device_ptr, size_t bytes);
+/* the image the last post pass wrote (NULL before the first) */
+void* awsm_hip_display_device_ptr(AwsmHipCtx* ctx);
 /* ---- picking (crates/renderer/src/picker.rs:55-121 + picker/shader/picker_wgsl/compute.wgsl): the mesh under pixel
  * (x, y) of the last geometry pass, read from the visibility buffer: key -> draw -> geometry meta -> material mesh meta
  * -> mesh key words.  valid = 0 for background and for coordinates outside the frame (or outside this shard).

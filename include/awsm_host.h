@@ -152,6 +152,17 @@ int awsm_host_resize(AwsmHost* h, uint32_t width, uint32_t height);
 /* AwsmRenderer::set_anti_aliasing (anti_alias.rs:9-45): msaa_sample_count 0 (None) or 4 (recreates the render targets);
  * mipmap != 0 selects MipmapMode::Gradient in the opaque pass.  The reference's default is {Some(4), mipmap: true}. */
 int awsm_host_set_anti_aliasing(AwsmHost* h, uint32_t msaa_sample_count, uint32_t mipmap);
+/* AwsmRenderer::set_post_processing (post_process.rs: PostProcessing {tonemapping, bloom, dof}) with AntiAliasing.smaa (anti_alias.rs):
+ * after this call awsm_host_render enqueues awsm_hip_post_pass after the last transparent pass (read the result with awsm_hip_read_display).
+ * Off by default here; the reference's default is {KhronosNeutralPbr (1), bloom off, dof off}.  tonemapping: 0 None, 1 KhronosNeutralPbr,
+ * 2 Aces.  AWSM_ERR_UNSUPPORTED when the backend library has no awsm_hip_post_pass, or when the host renders a shard of the frame
+ * (awsm_host_set_shard_rows / _bands; those are refused the other way round while post-processing is on).  Calling it again replaces the
+ * settings; awsm_host_clear_post_processing turns the post pass off again. */
+int awsm_host_set_post_processing(AwsmHost* h, uint32_t tonemapping, int bloom, int dof, int smaa);
+int awsm_host_clear_post_processing(AwsmHost* h);
+/* CameraMatrices.focus_distance / .aperture (camera.rs:40-52; the reference's defaults are 10.0 and 5.6): camera bytes 496-503, uploaded with
+ * the next frame.  Until this is called the host writes 0 and 0. */
+int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture);
 int awsm_host_set_shard_rows(AwsmHost* h, uint32_t y0, uint32_t y1);
 /* GPU instancing (meshes.rs:176-290, instances.rs): n transforms of 10 floats each (translation xyz, rotation xyzw, scale xyz);
  * the first call enables instancing for the mesh (enable_mesh_instancing), later calls replace the list (set_mesh_instances);
