@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <string>
@@ -16,6 +17,7 @@
 
 #include "frame_params.hpp"
 #include "dirty_log.hpp"
+#include "env_cube.hpp"
 
 using namespace awsm;
 
@@ -48,6 +50,9 @@ void awsm_launch_vis_digest(const unsigned long long* vis, size_t n, unsigned lo
 void awsm_launch_brdf_lut(uint32_t* out_rg16f, uint32_t w, uint32_t h, hipStream_t s);
 void awsm_launch_cube_border(const awsm::CubeDev* cd, uint2* out, uint32_t total, hipStream_t s);
 void awsm_launch_rgba16f_to_rg16f(const uint16_t* in, uint32_t* out, uint32_t n, hipStream_t s);
+void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s);
+void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, uint2* dst, uint32_t n, hipStream_t s);
+void awsm_launch_env_mips(const awsm::EnvMipArgs* a, hipStream_t s);
 }
 
 namespace {
@@ -127,6 +132,10 @@ struct AwsmHipCtx {
     DevBuf tex[kMaxTexArrays];
     DevBuf lut;
     DevBuf cube_tex[3], cube_bordered[3];      // the uploaded chains; the same with a one-texel apron per face (CubeDev.bordered)
+    // awsm_hip_env_cube_write_* / fill_*: the source bytes on the device (grow-only, reused), the 8-bit -> f16 tables, the fills' row table,
+    // and the event a write waits on when it copied straight from the caller's memory
+    DevBuf env_stage, env_tables, env_rows;
+    hipEvent_t ev_env_copy = nullptr;
 
     // frame targets
     uint32_t width = 0, height = 0;
@@ -1114,6 +1123,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->bufs) fr(b);
     for (auto& b : c->tex) fr(b);
     for (auto& b : c->merged_vis) fr(b);
+    fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 4 * kSlots; k++) {
@@ -1356,6 +1366,27 @@ int awsm_hip_env_upload(AwsmHipCtx* c, const AwsmEnv* env) {
     return AWSM_OK;
 }
 
+namespace {
+
+// The chain and the aproned chain of a size^2 cube with `mips` levels: (re)allocates c->cube_tex / c->cube_bordered[which] (contents undefined; the old
+// allocation is kept when the byte size is unchanged) and describes them in cd; cd.bordered stays null until the caller has filled the apron.
+int cube_reserve(AwsmHipCtx* c, int which, uint32_t size, uint32_t mips, CubeDev& cd, size_t& total, size_t& b_total, bool& aproned) {
+    cd = CubeDev{};
+    total = 0;
+    for (uint32_t l = 0; l < mips; l++) { cd.level_off[l] = (uint32_t)total; const size_t n = std::max(1u, size >> l); total += 6 * n * n; }
+    int rc = dev_realloc(c, c->cube_tex[which], total * 8, false);
+    if (rc) return rc;
+    b_total = 0;
+    for (uint32_t l = 0; l < mips; l++) { cd.b_level_off[l] = (uint32_t)b_total; const size_t n = std::max(1u, size >> l) + 2; b_total += 6 * n * n; }
+    aproned = b_total < (1ull << 29);      // byte offsets into the aproned chain are 32-bit; a larger cube keeps the general sampler on the lean route too
+    rc = dev_realloc(c, c->cube_bordered[which], aproned ? b_total * 8 : 0, false);
+    if (rc) return rc;
+    cd.texels = (const uint2*)c->cube_tex[which].ptr; cd.size = size; cd.mips = mips;
+    return AWSM_OK;
+}
+
+}  // namespace
+
 int awsm_hip_env_cube_upload(AwsmHipCtx* c, AwsmCube which, uint32_t size, uint32_t mips, const uint16_t* texels) {
     if (!c || (int)which < 0 || (int)which > 2) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_upload: bad cube id %d", (int)which);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1373,22 +1404,276 @@ int awsm_hip_env_cube_upload(AwsmHipCtx* c, AwsmCube which, uint32_t size, uint3
     }
     if (size == 0 || size > 8192 || mips == 0 || mips > (uint32_t)kMaxMipLevels || mips > mip_levels_full(size, size))
         return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_upload: %u mip levels of a %u^2 cube (1..8192 per side, at most %u levels)", mips, size, size ? mip_levels_full(size, size) : 0u);
-    size_t total = 0;
-    for (uint32_t l = 0; l < mips; l++) { cd.level_off[l] = (uint32_t)total; const size_t n = std::max(1u, size >> l); total += 6 * n * n; }
-    int rc = dev_realloc(c, c->cube_tex[which], total * 8, false);
-    if (rc) return rc;
-    size_t b_total = 0;
-    for (uint32_t l = 0; l < mips; l++) { cd.b_level_off[l] = (uint32_t)b_total; const size_t n = std::max(1u, size >> l) + 2; b_total += 6 * n * n; }
-    const bool aproned = b_total < (1ull << 29);      // byte offsets into the aproned chain are 32-bit; a larger cube keeps the general sampler on the lean route too
-    rc = dev_realloc(c, c->cube_bordered[which], aproned ? b_total * 8 : 0, false);
+    size_t total, b_total; bool aproned;
+    int rc = cube_reserve(c, which, size, mips, cd, total, b_total, aproned);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->cube_tex[which].ptr, texels, total * 8, hipMemcpyHostToDevice, c->stream));
-    cd.texels = (const uint2*)c->cube_tex[which].ptr; cd.size = size; cd.mips = mips;
     if (aproned) awsm_launch_cube_border(&cd, (uint2*)c->cube_bordered[which].ptr, (uint32_t)b_total, c->stream);      // the apron, from the faces across the edges
     HIPCHK(c, hipStreamSynchronize(c->stream));      // `texels` is not retained
     cd.bordered = aproned ? (const uint2*)c->cube_bordered[which].ptr : nullptr;
     c->scene.cube[which] = cd;
     c->scene_dirty = true;
+    return AWSM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ environment cubes at run time
+namespace {
+
+// double -> f16 bits, one rounding to nearest even, for v in [0, 1] (the 8-bit tables: "built on the host in double precision and rounded to f16")
+uint16_t f16_bits_from_unit_double(double v) {
+    if (!(v > 0.0)) return 0;
+    int e2;
+    (void)std::frexp(v, &e2);                       // v = m * 2^e2, m in [0.5, 1)
+    const int e = e2 - 1;                           // v = 1.f * 2^e
+    if (e < -14) return (uint16_t)std::nearbyint(std::ldexp(v, 24));       // denormal steps of 2^-24 (1024 = the smallest normal's bits)
+    const double m = std::nearbyint(std::ldexp(v, 10 - e));                // 1024 .. 2048, ties to even (the default rounding mode)
+    return (uint16_t)(((uint32_t)(e + 15) << 10) + ((uint32_t)m - 1024u)); // m == 2048 carries into the exponent
+}
+
+int env_tables(AwsmHipCtx* c) {
+    if (c->env_tables.ptr) return AWSM_OK;
+    uint16_t t[512];
+    for (int q = 0; q < 256; q++) {
+        const double u = (double)q / 255.0;
+        t[q] = f16_bits_from_unit_double(u);
+        t[256 + q] = f16_bits_from_unit_double(u <= 0.04045 ? u / 12.92 : std::pow((u + 0.055) / 1.055, 2.4));
+    }
+    int rc = dev_realloc(c, c->env_tables, sizeof t, false);
+    if (!rc) rc = upload_small(c, c->env_tables.ptr, t, sizeof t);
+    if (rc && c->env_tables.ptr) { (void)hipFree(c->env_tables.ptr); c->env_tables = DevBuf{}; }
+    return rc;
+}
+
+// The reference's colours are f64 (Color), written as decimal literals; here they cross the C ABI as f32.  A colour component is therefore read as
+// the shortest decimal that names the float — 0.35f means 0.35, not 0.3499999940395355 — so that the 8-bit quantisation below, which the reference
+// does in f64, lands on the reference's bytes (the default sky gradient has two exact .5 ties that the float's own value would round the other way).
+double color_component(float f) {
+    if (!std::isfinite(f)) return (double)f;
+    char buf[40];
+    for (int digits = 1; digits <= 9; digits++) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)f);
+        if (strtof(buf, nullptr) == f) return strtod(buf, nullptr);
+    }
+    return (double)f;
+}
+double clamp_unit(double v) { return v != v ? 0.0 : std::min(std::max(v, 0.0), 1.0); }      // f64::clamp keeps NaN, and `NaN as u8` is 0
+// create_color (image/bitmap.rs:183-193): (c.clamp(0.0, 1.0) * 255.0) as u8 per channel — truncated
+uint32_t color_rgba8(const float* col) {
+    uint32_t w = 0;
+    for (int ch = 0; ch < 4; ch++) w |= (uint32_t)(uint8_t)(clamp_unit(color_component(col[ch])) * 255.0) << (8 * ch);
+    return w;
+}
+
+uint32_t cube_format_bytes(AwsmCubeFormat f) {
+    switch (f) {
+    case AWSM_CUBE_RGBA16F: return 8;
+    case AWSM_CUBE_RGBA32F: return 16;
+    case AWSM_CUBE_RGBA8_UNORM: case AWSM_CUBE_RGBA8_SRGB: case AWSM_CUBE_BGRA8_UNORM: case AWSM_CUBE_BGRA8_SRGB:
+    case AWSM_CUBE_B10G11R11_UFLOAT: case AWSM_CUBE_E5B9G9R9_UFLOAT: return 4;
+    }
+    return 0;
+}
+
+// the apron of levels [first, end) again, by the seam rule of k_cube_border: the kernel sees those levels as a chain of their own
+void cube_reborder(AwsmHipCtx* c, int which, uint32_t first, uint32_t end) {
+    const CubeDev& cd = c->scene.cube[which];
+    if (!c->cube_bordered[which].ptr || first >= end) return;
+    CubeDev sub{};
+    sub.texels = cd.texels; sub.size = std::max(1u, cd.size >> first); sub.mips = end - first;
+    const size_t p_last = std::max(1u, cd.size >> (end - 1)) + 2, b_end = cd.b_level_off[end - 1] + 6 * p_last * p_last;
+    for (uint32_t l = first; l < end; l++) { sub.level_off[l - first] = cd.level_off[l]; sub.b_level_off[l - first] = cd.b_level_off[l] - cd.b_level_off[first]; }
+    awsm_launch_cube_border(&sub, (uint2*)c->cube_bordered[which].ptr + cd.b_level_off[first], (uint32_t)(b_end - cd.b_level_off[first]), c->stream);
+}
+
+// levels 1.. of the plain chain from level 0, five levels per launch
+void cube_mips(AwsmHipCtx* c, int which) {
+    const CubeDev& cd = c->scene.cube[which];
+    for (uint32_t l = 0; l + 1 < cd.mips; l += 5) {
+        EnvMipArgs a{};
+        a.chain = (uint2*)c->cube_tex[which].ptr; a.src_off = cd.level_off[l]; a.src_n = std::max(1u, cd.size >> l);
+        a.n_levels = std::min(5u, cd.mips - 1 - l);
+        for (uint32_t k = 0; k < a.n_levels; k++) a.dst_off[k] = cd.level_off[l + 1 + k];
+        awsm_launch_env_mips(&a, c->stream);
+    }
+}
+
+int cube_id_ok(AwsmHipCtx* c, AwsmCube which, const char* where) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    if ((int)which < 0 || (int)which > 2) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: bad cube id %d", where, (int)which);
+    return AWSM_OK;
+}
+
+// a zero-filled (or to-be-filled) cube in place of whatever the binding held; keeps the allocation when the shape is unchanged
+int cube_create(AwsmHipCtx* c, AwsmCube which, uint32_t size, uint32_t mips, bool zero, const char* where) {
+    if (size == 0 || size > 8192 || mips == 0 || mips > (uint32_t)kMaxMipLevels || mips > mip_levels_full(size, size))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: %u mip levels of a %u^2 cube (1..8192 per side, at most %u levels)", where, mips, size, size ? mip_levels_full(size, size) : 0u);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    CubeDev cd; size_t total, b_total; bool aproned;
+    int rc = cube_reserve(c, which, size, mips, cd, total, b_total, aproned);
+    if (!rc) rc = env_tables(c);
+    if (rc) { c->scene.cube[which] = CubeDev{}; c->scene_dirty = true; return rc; }      // a half-made cube is no cube
+    if (zero) {
+        HIPCHK(c, hipMemsetAsync(c->cube_tex[which].ptr, 0, total * 8, c->stream));
+        if (aproned) HIPCHK(c, hipMemsetAsync(c->cube_bordered[which].ptr, 0, b_total * 8, c->stream));      // the apron of zeros is zeros
+    }
+    cd.bordered = aproned ? (const uint2*)c->cube_bordered[which].ptr : nullptr;
+    c->scene.cube[which] = cd;
+    c->scene_dirty = true;
+    return AWSM_OK;
+}
+
+int cube_write(AwsmHipCtx* c, AwsmCube which, uint32_t face, uint32_t layers, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+               const void* data, size_t data_len, const AwsmCubeLayout* layout, const char* where) {
+    { int rc = cube_id_ok(c, which, where); if (rc) return rc; }
+    if (!data || !layout || layout->struct_size != sizeof(AwsmCubeLayout))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: data, or a layout with struct_size %zu, is missing", where, sizeof(AwsmCubeLayout));
+    if (face > 5u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: face %u (0..5 = +X -X +Y -Y +Z -Z)", where, face);
+    // validate_dimensions, validate_layout (cubemap.rs:265-323)
+    if (width == 0 || height == 0) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update dimensions must be non-zero", where);
+    if (width != height) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap faces must be square, got %ux%u", where, width, height);
+    if (layout->bytes_per_row == 0) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update bytes_per_row must be non-zero", where);
+    if (layout->rows_per_image == 0) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update rows_per_image must be non-zero", where);
+    unsigned long long per_layer, total_bytes, required;
+    if (__builtin_mul_overflow((unsigned long long)layout->bytes_per_row, (unsigned long long)layout->rows_per_image, &per_layer))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update layout overflow while calculating layer byte size", where);
+    if (__builtin_mul_overflow(per_layer, (unsigned long long)layers, &total_bytes))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update layout overflow while calculating total byte size", where);
+    if (__builtin_add_overflow((unsigned long long)layout->offset, total_bytes, &required))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update layout overflow while applying data offset", where);
+    if ((unsigned long long)data_len < required)
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: Cubemap update buffer is too small: need at least %llu bytes, got %zu", where, required, data_len);
+    // the destination, and what writeTexture itself would refuse
+    const CubeDev cd = c->scene.cube[which];
+    if (!cd.texels) return fail(c, AWSM_ERR_NOT_READY, "%s: cube %d was never created or uploaded", where, (int)which);
+    if (mip >= cd.mips) return fail(c, AWSM_ERR_OUT_OF_RANGE, "%s: mip level %u, the cube has %u", where, mip, cd.mips);
+    const uint32_t bpt = cube_format_bytes(format);
+    if (!bpt) return fail(c, AWSM_ERR_UNSUPPORTED, "%s: unknown AwsmCubeFormat %d", where, (int)format);
+    const uint32_t n = std::max(1u, cd.size >> mip);
+    if (width != n) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: %ux%u texels for mip level %u of a %u^2 cube, which is %ux%u", where, width, height, mip, cd.size, n, n);
+    if ((unsigned long long)layout->bytes_per_row < (unsigned long long)width * bpt)
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: bytes_per_row %u, a row of %u texels takes %llu bytes", where, layout->bytes_per_row, width, (unsigned long long)width * bpt);
+    if (layout->rows_per_image < height) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: rows_per_image %u for %u rows", where, layout->rows_per_image, height);
+
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    int rc = env_tables(c);
+    if (rc) return rc;
+    // only the bytes the gather reads: up to the end of the last row of the last image
+    const size_t used = (size_t)per_layer * (layers - 1) + (size_t)layout->bytes_per_row * (height - 1) + (size_t)width * bpt;
+    if ((rc = dev_reserve(c, c->env_stage, used))) return rc;      // grows (and then waits for the stream) only until it fits the largest source seen
+    const uint8_t* src = (const uint8_t*)data + layout->offset;
+    if (used <= (4u << 20)) {
+        uint8_t* st;
+        if ((rc = stage_alloc(c, used, &st))) return rc;
+        memcpy(st, src, used);
+        HIPCHK(c, hipMemcpyAsync(c->env_stage.ptr, st, used, hipMemcpyHostToDevice, c->stream));
+    } else {
+        if (!c->ev_env_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_env_copy, hipEventDisableTiming));
+        HIPCHK(c, hipMemcpyAsync(c->env_stage.ptr, src, used, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_env_copy, c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev_env_copy));      // the one wait: `data` may be pageable and is not retained
+    }
+    EnvWriteArgs a{};
+    a.src = (const uint8_t*)c->env_stage.ptr;
+    a.dst = (uint2*)c->cube_tex[which].ptr + cd.level_off[mip] + (size_t)face * n * n;
+    a.tables = (const uint16_t*)c->env_tables.ptr;
+    a.n = n; a.layers = layers; a.format = (uint32_t)format; a.bytes_per_row = layout->bytes_per_row; a.image_stride = per_layer;
+    awsm_launch_env_write(&a, c->stream);
+    cube_reborder(c, which, mip, mip + 1);      // the whole level: a face's edge texels are the apron of its four neighbours
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+// level 0 from one RGBA8 colour per face row, then the full chain (CubemapImage::Images { mipmaps: true })
+int cube_fill(AwsmHipCtx* c, AwsmCube which, uint32_t size, const std::vector<uint32_t>& rows, const char* where) {
+    int rc = cube_create(c, which, size, size ? mip_levels_full(size, size) : 0u, false, where);
+    if (rc) return rc;
+    if ((rc = dev_reserve(c, c->env_rows, rows.size() * 4))) return rc;
+    if ((rc = upload_small(c, c->env_rows.ptr, rows.data(), rows.size() * 4))) return rc;
+    awsm_launch_env_expand_rows((const uint32_t*)c->env_rows.ptr, (const uint16_t*)c->env_tables.ptr, (uint2*)c->cube_tex[which].ptr, size, c->stream);
+    cube_mips(c, which);
+    cube_reborder(c, which, 0, c->scene.cube[which].mips);
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+}  // namespace
+
+int awsm_hip_env_cube_create(AwsmHipCtx* c, AwsmCube which, uint32_t size, uint32_t mips) {
+    { int rc = cube_id_ok(c, which, "env_cube_create"); if (rc) return rc; }
+    return cube_create(c, which, size, mips, true, "env_cube_create");
+}
+
+int awsm_hip_env_cube_write_face(AwsmHipCtx* c, AwsmCube which, uint32_t face, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                 const void* data, size_t data_len, const AwsmCubeLayout* layout) {
+    return cube_write(c, which, face, 1, mip, width, height, format, data, data_len, layout, "env_cube_write_face");
+}
+
+int awsm_hip_env_cube_write_all_faces(AwsmHipCtx* c, AwsmCube which, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                      const void* data, size_t data_len, const AwsmCubeLayout* layout) {
+    return cube_write(c, which, 0, 6, mip, width, height, format, data, data_len, layout, "env_cube_write_all_faces");
+}
+
+int awsm_hip_env_cube_generate_mips(AwsmHipCtx* c, AwsmCube which) {
+    { int rc = cube_id_ok(c, which, "env_cube_generate_mips"); if (rc) return rc; }
+    const CubeDev& cd = c->scene.cube[which];
+    if (!cd.texels) return fail(c, AWSM_ERR_NOT_READY, "env_cube_generate_mips: cube %d was never created or uploaded", (int)which);
+    if (cd.mips < 2) return AWSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    cube_mips(c, which);
+    cube_reborder(c, which, 1, cd.mips);
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+int awsm_hip_env_cube_fill_colors(AwsmHipCtx* c, AwsmCube which, uint32_t size, const float rgba[24]) {
+    { int rc = cube_id_ok(c, which, "env_cube_fill_colors"); if (rc) return rc; }
+    if (!rgba || size == 0 || size > 8192) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_fill_colors: colours missing or size %u (1..8192)", size);
+    std::vector<uint32_t> rows((size_t)6 * size);
+    for (int f = 0; f < 6; f++) std::fill(rows.begin() + (size_t)f * size, rows.begin() + (size_t)(f + 1) * size, color_rgba8(rgba + f * 4));
+    return cube_fill(c, which, size, rows, "env_cube_fill_colors");
+}
+
+int awsm_hip_env_cube_fill_sky_gradient(AwsmHipCtx* c, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]) {
+    { int rc = cube_id_ok(c, which, "env_cube_fill_sky_gradient"); if (rc) return rc; }
+    if (!zenith || !nadir || size == 0 || size > 8192) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_fill_sky_gradient: colours missing or size %u (1..8192)", size);
+    std::vector<uint32_t> rows((size_t)6 * size);
+    const double height_f = size > 1 ? (double)(size - 1) : 1.0;      // create_vertical_gradient (image/bitmap.rs:229-267)
+    for (uint32_t y = 0; y < size; y++) {
+        const double t = (double)y / height_f;
+        uint32_t w = 0;
+        for (int ch = 0; ch < 4; ch++) {      // lerp a + (b - a) * t, then (clamp * 255.0).round(): half away from zero
+            const double a = color_component(zenith[ch]), b = color_component(nadir[ch]);
+            w |= (uint32_t)(uint8_t)std::round(clamp_unit(a + (b - a) * t) * 255.0) << (8 * ch);
+        }
+        for (int f : {0, 1, 4, 5}) rows[(size_t)f * size + y] = w;
+    }
+    std::fill(rows.begin() + (size_t)2 * size, rows.begin() + (size_t)3 * size, color_rgba8(zenith));      // +Y: create_color(zenith)
+    std::fill(rows.begin() + (size_t)3 * size, rows.begin() + (size_t)4 * size, color_rgba8(nadir));       // -Y: create_color(nadir)
+    return cube_fill(c, which, size, rows, "env_cube_fill_sky_gradient");
+}
+
+int awsm_hip_env_cube_info(AwsmHipCtx* c, AwsmCube which, uint32_t* size, uint32_t* mips) {
+    { int rc = cube_id_ok(c, which, "env_cube_info"); if (rc) return rc; }
+    const CubeDev& cd = c->scene.cube[which];
+    if (!cd.texels) return fail(c, AWSM_ERR_NOT_READY, "env_cube_info: cube %d is a uniform colour", (int)which);
+    if (size) *size = cd.size;
+    if (mips) *mips = cd.mips;
+    return AWSM_OK;
+}
+
+int awsm_hip_env_cube_read_level(AwsmHipCtx* c, AwsmCube which, uint32_t level, uint16_t* out) {
+    { int rc = cube_id_ok(c, which, "env_cube_read_level"); if (rc) return rc; }
+    if (!out) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_read_level: no destination");
+    const CubeDev& cd = c->scene.cube[which];
+    if (!cd.texels) return fail(c, AWSM_ERR_NOT_READY, "env_cube_read_level: cube %d was never created or uploaded", (int)which);
+    if (level >= cd.mips) return fail(c, AWSM_ERR_OUT_OF_RANGE, "env_cube_read_level: level %u, the cube has %u", level, cd.mips);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = std::max(1u, cd.size >> level);
+    HIPCHK(c, hipMemcpy(out, cd.texels + cd.level_off[level], 6 * n * n * 8, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 

@@ -33,7 +33,9 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_device_info", "awsm_hip_transparent_pass", "awsm_hip_read_composite", "awsm_hip_read_composite_f32", "awsm_hip_bind_composite",
            "awsm_hip_read_transformed_forward", "awsm_hip_visibility_digest", "awsm_hip_bind_output_rows", "awsm_hip_env_cube_upload", "awsm_hip_bind_opaque_source", "awsm_hip_msaa_halo_bands", "awsm_hip_msaa_halo_export", "awsm_hip_msaa_halo_bind",
            "awsm_hip_frame_trace", "awsm_hip_read_frame_trace", "awsm_hip_hud_geometry_pass", "awsm_hip_hud_transparent_pass",
-           "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr"]
+           "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr",
+           "awsm_hip_env_cube_create", "awsm_hip_env_cube_write_face", "awsm_hip_env_cube_write_all_faces", "awsm_hip_env_cube_generate_mips",
+           "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level"]
 
 
 class AwsmConfig(C.Structure):
@@ -51,6 +53,26 @@ class AwsmOpaqueParams(C.Structure):
 
 class AwsmPostParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tonemapping", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AwsmCubeLayout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bytes_per_row", C.c_uint32), ("rows_per_image", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64)]
+
+
+# AwsmCubeFormat: name -> (value, bytes per texel)
+CUBE_FORMATS = {"rgba16f": (0, 8), "rgba32f": (1, 16), "rgba8unorm": (2, 4), "rgba8unorm-srgb": (3, 4), "bgra8unorm": (4, 4), "bgra8unorm-srgb": (5, 4),
+                "rg11b10ufloat": (6, 4), "rgb9e5ufloat": (7, 4)}
+CUBE_FORMAT_NAMES = {v[0]: k for k, v in CUBE_FORMATS.items()}
+DEFAULT_SKY_ZENITH, DEFAULT_SKY_NADIR = (0.4, 0.65, 1.0, 1.0), (0.55, 0.45, 0.35, 1.0)      # CubemapSkyGradient::default (cubemap/images.rs:54-61)
+
+
+def cube_source(data, fmt, width, bytes_per_row=None, rows_per_image=None, offset=0):
+    """(format value, contiguous uint8 view of `data`, AwsmCubeLayout) for the cube writes; the layout defaults to the tight one."""
+    value, bpt = CUBE_FORMATS[fmt] if isinstance(fmt, str) else (int(fmt), {0: 8, 1: 16}.get(int(fmt), 4))
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    layout = AwsmCubeLayout(C.sizeof(AwsmCubeLayout), width * bpt if bytes_per_row is None else bytes_per_row,
+                            width if rows_per_image is None else rows_per_image, 0, offset)
+    return value, raw, layout
 
 
 AWSM_POST_SMAA, AWSM_POST_BLOOM, AWSM_POST_DOF = 1, 2, 4
@@ -150,6 +172,14 @@ def load_library():
     lib.awsm_hip_display_device_ptr.restype = C.c_void_p
     lib.awsm_hip_display_device_ptr.argtypes = [C.c_void_p]
     lib.awsm_hip_read_frame_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_env_cube_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+    lib.awsm_hip_env_cube_write_face.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.awsm_hip_env_cube_write_all_faces.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.awsm_hip_env_cube_generate_mips.argtypes = [C.c_void_p, C.c_int]
+    lib.awsm_hip_env_cube_fill_colors.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+    lib.awsm_hip_env_cube_fill_sky_gradient.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_env_cube_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_env_cube_read_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     _lib = lib
     return lib
 
@@ -262,6 +292,58 @@ class HipDevice:
             return
         flat = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a, dtype=np.float16).reshape(-1) for a in levels])).view(np.uint16)
         self._chk(self.lib.awsm_hip_env_cube_upload(self.ctx, which, levels[0].shape[1], len(levels), flat.ctypes.data), "env_cube_upload")
+
+    # ---- environment cubes at run time (environment.rs, textures.rs:118-165; awsm_hip.h) ----
+    def env_cube_create(self, which: int, size: int, mips: int):
+        """A zero-filled RGBA16F chain of `mips` levels in place of whatever the binding held."""
+        self._chk(self.lib.awsm_hip_env_cube_create(self.ctx, which, size, mips), "env_cube_create")
+
+    def env_cube_write_face(self, which: int, face: int, mip: int, data, fmt="rgba16f", width: Optional[int] = None, height: Optional[int] = None,
+                            bytes_per_row: Optional[int] = None, rows_per_image: Optional[int] = None, offset: int = 0):
+        """One face (0..5 = +X -X +Y -Y +Z -Z) of one level, in place.  data: an (N, N, 4) array of the format's element type (float16 / float32 / uint8),
+        an (N, N) uint32 array for the packed formats, or raw bytes with width / height and, if not tight, the byte layout."""
+        width = np.asarray(data).shape[1] if width is None else width
+        value, raw, layout = cube_source(data, fmt, width, bytes_per_row, rows_per_image, offset)
+        self._chk(self.lib.awsm_hip_env_cube_write_face(self.ctx, which, face, mip, width, width if height is None else height, value,
+                                                        raw.ctypes.data_as(C.c_void_p), raw.nbytes, C.byref(layout)), "env_cube_write_face")
+
+    def env_cube_write_all_faces(self, which: int, mip: int, data, fmt="rgba16f", width: Optional[int] = None, height: Optional[int] = None,
+                                 bytes_per_row: Optional[int] = None, rows_per_image: Optional[int] = None, offset: int = 0):
+        """All six faces of one level from one buffer in face order: a (6, N, N, 4) array ((6, N, N) uint32 for the packed formats) or raw bytes."""
+        width = np.asarray(data).shape[2] if width is None else width
+        value, raw, layout = cube_source(data, fmt, width, bytes_per_row, rows_per_image, offset)
+        self._chk(self.lib.awsm_hip_env_cube_write_all_faces(self.ctx, which, mip, width, width if height is None else height, value,
+                                                             raw.ctypes.data_as(C.c_void_p), raw.nbytes, C.byref(layout)), "env_cube_write_all_faces")
+
+    def env_cube_generate_mips(self, which: int):
+        """Levels 1.. from level 0 on the device (regenerate_skybox_mipmaps / regenerate_cubemap_texture_mipmaps)."""
+        self._chk(self.lib.awsm_hip_env_cube_generate_mips(self.ctx, which), "env_cube_generate_mips")
+
+    def env_cube_fill_colors(self, which: int, size: int, colors):
+        """Skybox::new_colors / IblTexture::new_colors: one RGBA colour for all faces, or six in face order; full mip chain."""
+        c = np.asarray(colors, dtype=np.float32).reshape(-1, 4)
+        c = np.ascontiguousarray(np.tile(c, (6, 1)) if c.shape[0] == 1 else c)
+        assert c.shape == (6, 4), "one RGBA colour or six"
+        self._chk(self.lib.awsm_hip_env_cube_fill_colors(self.ctx, which, size, c.ctypes.data_as(C.c_void_p)), "env_cube_fill_colors")
+
+    def env_cube_fill_sky_gradient(self, which: int, size: int, zenith=DEFAULT_SKY_ZENITH, nadir=DEFAULT_SKY_NADIR):
+        """CubemapImage::new_sky_gradient: the side faces blend zenith (row 0) to nadir, +Y is the zenith, -Y the nadir colour; full mip chain."""
+        z, n = (C.c_float * 4)(*zenith), (C.c_float * 4)(*nadir)
+        self._chk(self.lib.awsm_hip_env_cube_fill_sky_gradient(self.ctx, which, size, z, n), "env_cube_fill_sky_gradient")
+
+    def env_cube_info(self, which: int):
+        """(size, mips) of a texel cube."""
+        size, mips = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.awsm_hip_env_cube_info(self.ctx, which, C.byref(size), C.byref(mips)), "env_cube_info")
+        return int(size.value), int(mips.value)
+
+    def env_cube_read_level(self, which: int, level: int) -> np.ndarray:
+        """One level of the cube as it is stored: (6, N, N, 4) float16."""
+        size, mips = self.env_cube_info(which)
+        n = max(size >> level, 1)
+        out = np.zeros((6, n, n, 4), dtype=np.float16)
+        self._chk(self.lib.awsm_hip_env_cube_read_level(self.ctx, which, level, out.ctypes.data_as(C.c_void_p)), "env_cube_read_level")
+        return out
 
     def env_upload(self, skybox=(0, 0, 0, 1), prefiltered=(1, 1, 1), irradiance=(1, 1, 1), lut_rgba16f: Optional[np.ndarray] = None):
         env = AwsmEnv()

@@ -91,6 +91,15 @@ def load_library():
         "awsm_host_set_ibl_mip_counts": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "awsm_host_camera_update": (C.c_int, [vp, F32P, F32P, F32P]), "awsm_host_env": (C.c_int, [vp, vp]),
         "awsm_host_env_cube": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, vp]),
+        "awsm_host_env_cube_create": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32]),
+        "awsm_host_env_cube_update_face": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, sz, vp]),
+        "awsm_host_env_cube_update_all_faces": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, sz, vp]),
+        "awsm_host_env_cube_regenerate_mipmaps": (C.c_int, [vp, C.c_int]),
+        "awsm_host_env_cube_colors": (C.c_int, [vp, C.c_int, C.c_uint32, vp]),
+        "awsm_host_env_cube_sky_gradient": (C.c_int, [vp, C.c_int, C.c_uint32, vp, vp]),
+        "awsm_host_ktx2_parse": (C.c_int, [vp, sz, vp, C.c_char_p, sz]),
+        "awsm_host_env_cube_load_ktx2": (C.c_int, [vp, C.c_int, C.c_char_p, vp, C.c_char_p, sz]),
+        "awsm_host_env_cube_load_ktx2_memory": (C.c_int, [vp, C.c_int, vp, sz, vp, C.c_char_p, sz]),
         "awsm_host_set_render_hooks": (C.c_int, [vp, vp, vp, vp, vp]),
         "awsm_host_brdf_lut_generate": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_resize": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "awsm_host_set_shard_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_set_shard_bands": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_set_render_timings": (C.c_int, [vp, C.c_int]),
@@ -121,7 +130,35 @@ def _f(arr):
 
 
 class HostError(RuntimeError):
-    pass
+    code = None      # the AwsmStatus, where the failure came with one
+
+
+class Ktx2Level(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64)]
+
+
+class Ktx2Info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("vk_format", C.c_uint32), ("format", C.c_uint32), ("size", C.c_uint32), ("faces", C.c_uint32),
+                ("layers", C.c_uint32), ("levels", C.c_uint32), ("mips", C.c_uint32), ("level", Ktx2Level * 16)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("vk_format", "format", "size", "faces", "layers", "levels", "mips")}
+        d["format_name"] = hip_backend.CUBE_FORMAT_NAMES.get(d["format"])
+        d["level"] = [(int(self.level[i].offset), int(self.level[i].length)) for i in range(d["levels"])]
+        return d
+
+
+def ktx2_parse(data: bytes) -> dict:
+    """awsm_host_ktx2_parse: the header and level index of a KTX2 cube map (no host, no device); raises HostError with the reason."""
+    info = Ktx2Info(struct_size=C.sizeof(Ktx2Info))
+    err = C.create_string_buffer(512)
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
+    rc = load_library().awsm_host_ktx2_parse(buf, len(data), C.byref(info), err, 512)
+    if rc != 0:
+        e = HostError(f"ktx2_parse failed ({rc}): {err.value.decode(errors='replace')}")
+        e.code = rc
+        raise e
+    return info.as_dict()
 
 
 class Host:
@@ -143,7 +180,9 @@ class Host:
 
     def _chk(self, rc, where):
         if rc != 0:
-            raise HostError(f"{where} failed ({rc}): {(self.lib.awsm_host_last_error(self.h) or b'').decode()}")
+            e = HostError(f"{where} failed ({rc}): {(self.lib.awsm_host_last_error(self.h) or b'').decode()}")
+            e.code = rc
+            raise e
 
     def close(self):
         if getattr(self, "h", None):
@@ -311,6 +350,56 @@ class Host:
             return
         flat = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a, dtype=np.float16).reshape(-1) for a in levels])).view(np.uint16)
         self._chk(self.lib.awsm_host_env_cube(self.h, which, levels[0].shape[1], len(levels), flat.ctypes.data), "env_cube")
+
+    # ---- environment cubes at run time (environment.rs, textures.rs:118-165, cubemap/ktx.rs) ----
+    def env_cube_create(self, which: int, size: int, mips: int):
+        self._chk(self.lib.awsm_host_env_cube_create(self.h, which, size, mips), "env_cube_create")
+
+    def env_cube_update_face(self, which: int, face: int, mip: int, data, fmt="rgba16f", width: Optional[int] = None, height: Optional[int] = None,
+                             bytes_per_row: Optional[int] = None, rows_per_image: Optional[int] = None, offset: int = 0):
+        """update_skybox_face / update_cubemap_texture_face: an (N, N, 4) array ((N, N) uint32 for the packed formats) or raw bytes + layout."""
+        width = np.asarray(data).shape[1] if width is None else width
+        value, raw, layout = hip_backend.cube_source(data, fmt, width, bytes_per_row, rows_per_image, offset)
+        self._chk(self.lib.awsm_host_env_cube_update_face(self.h, which, face, mip, width, width if height is None else height, value,
+                                                          raw.ctypes.data, raw.nbytes, C.byref(layout)), "env_cube_update_face")
+
+    def env_cube_update_all_faces(self, which: int, mip: int, data, fmt="rgba16f", width: Optional[int] = None, height: Optional[int] = None,
+                                  bytes_per_row: Optional[int] = None, rows_per_image: Optional[int] = None, offset: int = 0):
+        """update_skybox_all_faces / update_cubemap_texture_all_faces: a (6, N, N, 4) array ((6, N, N) uint32 for the packed formats) or raw bytes + layout."""
+        width = np.asarray(data).shape[2] if width is None else width
+        value, raw, layout = hip_backend.cube_source(data, fmt, width, bytes_per_row, rows_per_image, offset)
+        self._chk(self.lib.awsm_host_env_cube_update_all_faces(self.h, which, mip, width, width if height is None else height, value,
+                                                               raw.ctypes.data, raw.nbytes, C.byref(layout)), "env_cube_update_all_faces")
+
+    def env_cube_regenerate_mipmaps(self, which: int):
+        self._chk(self.lib.awsm_host_env_cube_regenerate_mipmaps(self.h, which), "env_cube_regenerate_mipmaps")
+
+    def env_cube_colors(self, which: int, size: int, colors):
+        """Skybox::new_colors / IblTexture::new_colors: one RGBA colour or six in face order."""
+        c = np.asarray(colors, dtype=np.float32).reshape(-1, 4)
+        c = np.ascontiguousarray(np.tile(c, (6, 1)) if c.shape[0] == 1 else c)
+        assert c.shape == (6, 4), "one RGBA colour or six"
+        self._chk(self.lib.awsm_host_env_cube_colors(self.h, which, size, c.ctypes.data), "env_cube_colors")
+
+    def env_cube_sky_gradient(self, which: int, size: int, zenith=hip_backend.DEFAULT_SKY_ZENITH, nadir=hip_backend.DEFAULT_SKY_NADIR):
+        """CubemapImage::new_sky_gradient (the defaults are CubemapSkyGradient::default)."""
+        z, n = (C.c_float * 4)(*zenith), (C.c_float * 4)(*nadir)
+        self._chk(self.lib.awsm_host_env_cube_sky_gradient(self.h, which, size, z, n), "env_cube_sky_gradient")
+
+    def env_cube_load_ktx2(self, which: int, source) -> dict:
+        """A KTX2 cube map from a path or from bytes; returns the parsed header (pass info["mips"] to set_ibl_mip_counts for an IBL cube)."""
+        info = Ktx2Info(struct_size=C.sizeof(Ktx2Info))
+        err = C.create_string_buffer(512)
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            buf = (C.c_uint8 * max(1, len(source))).from_buffer_copy(bytes(source) or b"\0")
+            rc = self.lib.awsm_host_env_cube_load_ktx2_memory(self.h, which, buf, len(source), C.byref(info), err, 512)
+        else:
+            rc = self.lib.awsm_host_env_cube_load_ktx2(self.h, which, os.fsencode(source), C.byref(info), err, 512)
+        if rc != 0:
+            e = HostError(f"env_cube_load_ktx2 failed ({rc}): {err.value.decode(errors='replace')}")
+            e.code = rc
+            raise e
+        return info.as_dict()
 
     def brdf_lut_generate(self, w: int, h: int):
         self._chk(self.lib.awsm_host_brdf_lut_generate(self.h, w, h), "brdf_lut_generate")

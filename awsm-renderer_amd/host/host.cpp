@@ -32,6 +32,7 @@
 
 #include "buffers.hpp"
 #include "glam.hpp"
+#include "ktx2.hpp"
 
 using namespace awsm_host;
 
@@ -63,6 +64,13 @@ struct Backend {
     int (*hud_transparent_pass)(AwsmHipCtx*, const AwsmDraw*, uint32_t) = nullptr;
     int (*frame_end)(AwsmHipCtx*, AwsmFrameStats*) = nullptr;
     int (*post_pass)(AwsmHipCtx*, const AwsmPostParams*) = nullptr;     // optional: a backend without it cannot post-process
+    // optional: environment cubes at run time (awsm_host_env_cube_*)
+    int (*env_cube_create)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t) = nullptr;
+    int (*env_cube_write_face)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
+    int (*env_cube_write_all_faces)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
+    int (*env_cube_generate_mips)(AwsmHipCtx*, AwsmCube) = nullptr;
+    int (*env_cube_fill_colors)(AwsmHipCtx*, AwsmCube, uint32_t, const float*) = nullptr;
+    int (*env_cube_fill_sky_gradient)(AwsmHipCtx*, AwsmCube, uint32_t, const float*, const float*) = nullptr;
 };
 
 struct Transform { Vec3 t; Quat r; Vec3 s; };
@@ -508,6 +516,12 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
               load_sym(h.get(), b.frame_end, "awsm_hip_frame_end");
     if (!ok) { fprintf(stderr, "awsm_host: %s\n", h->last_error.c_str()); dlclose(b.dl); return AWSM_ERR_NOT_READY; }
     b.post_pass = reinterpret_cast<decltype(b.post_pass)>(dlsym(b.dl, "awsm_hip_post_pass"));      // optional (awsm_host_set_post_processing)
+    b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
+    b.env_cube_write_face = reinterpret_cast<decltype(b.env_cube_write_face)>(dlsym(b.dl, "awsm_hip_env_cube_write_face"));
+    b.env_cube_write_all_faces = reinterpret_cast<decltype(b.env_cube_write_all_faces)>(dlsym(b.dl, "awsm_hip_env_cube_write_all_faces"));
+    b.env_cube_generate_mips = reinterpret_cast<decltype(b.env_cube_generate_mips)>(dlsym(b.dl, "awsm_hip_env_cube_generate_mips"));
+    b.env_cube_fill_colors = reinterpret_cast<decltype(b.env_cube_fill_colors)>(dlsym(b.dl, "awsm_hip_env_cube_fill_colors"));
+    b.env_cube_fill_sky_gradient = reinterpret_cast<decltype(b.env_cube_fill_sky_gradient)>(dlsym(b.dl, "awsm_hip_env_cube_fill_sky_gradient"));
     if (b.abi_version() != AWSM_HIP_ABI_VERSION) { dlclose(b.dl); return AWSM_ERR_INVALID_ARGUMENT; }
     AwsmConfig cfg{};
     cfg.struct_size = sizeof cfg; cfg.abi_version = AWSM_HIP_ABI_VERSION; cfg.device = device; cfg.flags = cfg_flags; cfg.stream = stream;
@@ -950,6 +964,73 @@ int awsm_host_env_cube(AwsmHost* h, AwsmCube which, uint32_t size, uint32_t mips
     int rc = h->be.env_cube_upload(h->ctx, which, size, mips, texels_rgba16f);
     return rc ? dev_fail(h, rc, "env_cube_upload") : AWSM_OK;
 }
+// Environment cubes at run time (environment.rs, textures.rs:118-165): the backend does the work; its symbols are optional
+#define AWSM_ENV_CUBE_CALL(fn, symbol, ...)                                                                                             \
+    do {                                                                                                                                \
+        if (!h) return AWSM_ERR_INVALID_ARGUMENT;                                                                                       \
+        if (!h->be.fn) return fail(h, AWSM_ERR_UNSUPPORTED, "the backend library has no %s", symbol);                                   \
+        const int rc_ = h->be.fn(h->ctx, __VA_ARGS__);                                                                                  \
+        return rc_ ? dev_fail(h, rc_, symbol + 9) : AWSM_OK;                                                                            \
+    } while (0)
+int awsm_host_env_cube_create(AwsmHost* h, AwsmCube which, uint32_t size, uint32_t mips) { AWSM_ENV_CUBE_CALL(env_cube_create, "awsm_hip_env_cube_create", which, size, mips); }
+int awsm_host_env_cube_update_face(AwsmHost* h, AwsmCube which, uint32_t face, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                   const void* data, size_t data_len, const AwsmCubeLayout* layout) {
+    AWSM_ENV_CUBE_CALL(env_cube_write_face, "awsm_hip_env_cube_write_face", which, face, mip, width, height, format, data, data_len, layout);
+}
+int awsm_host_env_cube_update_all_faces(AwsmHost* h, AwsmCube which, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                        const void* data, size_t data_len, const AwsmCubeLayout* layout) {
+    AWSM_ENV_CUBE_CALL(env_cube_write_all_faces, "awsm_hip_env_cube_write_all_faces", which, mip, width, height, format, data, data_len, layout);
+}
+int awsm_host_env_cube_regenerate_mipmaps(AwsmHost* h, AwsmCube which) { AWSM_ENV_CUBE_CALL(env_cube_generate_mips, "awsm_hip_env_cube_generate_mips", which); }
+int awsm_host_env_cube_colors(AwsmHost* h, AwsmCube which, uint32_t size, const float rgba[24]) { AWSM_ENV_CUBE_CALL(env_cube_fill_colors, "awsm_hip_env_cube_fill_colors", which, size, rgba); }
+int awsm_host_env_cube_sky_gradient(AwsmHost* h, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]) {
+    AWSM_ENV_CUBE_CALL(env_cube_fill_sky_gradient, "awsm_hip_env_cube_fill_sky_gradient", which, size, zenith, nadir);
+}
+#undef AWSM_ENV_CUBE_CALL
+
+int awsm_host_ktx2_parse(const uint8_t* data, size_t len, AwsmKtx2Info* out, char* err_out, size_t err_cap) { return ktx2::parse(data, len, out, err_out, err_cap); }
+
+// cubemap/ktx.rs:39-191: parse, create the texture with the file's level count, one write per level
+int awsm_host_env_cube_load_ktx2_memory(AwsmHost* h, AwsmCube which, const uint8_t* data, size_t len, AwsmKtx2Info* info_out, char* err_out, size_t err_cap) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    AwsmKtx2Info info{};
+    info.struct_size = sizeof info;
+    int rc = ktx2::parse(data, len, &info, err_out, err_cap);
+    if (rc) { h->last_error = (err_out && err_cap) ? err_out : "ktx2: the file was refused"; return rc; }
+    if ((rc = awsm_host_env_cube_create(h, which, info.size, info.mips)) == AWSM_OK) {
+        for (uint32_t l = 0; l < info.levels && rc == AWSM_OK; l++) {
+            const uint32_t n = std::max(1u, info.size >> l);
+            AwsmCubeLayout layout{};
+            layout.struct_size = sizeof layout; layout.bytes_per_row = (uint32_t)(info.level[l].length / (6u * n)); layout.rows_per_image = n;      // tight: the parser checked the length
+            rc = awsm_host_env_cube_update_all_faces(h, which, l, n, n, (AwsmCubeFormat)info.format, data + info.level[l].offset, (size_t)info.level[l].length, &layout);
+        }
+        if (rc == AWSM_OK && info.mips > info.levels) rc = awsm_host_env_cube_regenerate_mipmaps(h, which);      // levelCount 0
+    }
+    if (rc) { if (err_out && err_cap) snprintf(err_out, err_cap, "%s", h->last_error.c_str()); return rc; }
+    if (info_out) { const uint32_t theirs = info_out->struct_size; memcpy(info_out, &info, std::min<size_t>(theirs, sizeof info)); info_out->struct_size = std::min<uint32_t>(theirs, sizeof info); }
+    return AWSM_OK;
+}
+
+int awsm_host_env_cube_load_ktx2(AwsmHost* h, AwsmCube which, const char* path, AwsmKtx2Info* info_out, char* err_out, size_t err_cap) {
+    if (!h || !path) return AWSM_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> bytes;
+    FILE* f = fopen(path, "rb");
+    bool ok = f != nullptr;
+    if (ok) {
+        uint8_t chunk[65536];
+        size_t got;
+        while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) bytes.insert(bytes.end(), chunk, chunk + got);
+        ok = !ferror(f);
+        fclose(f);
+    }
+    if (!ok) {
+        fail(h, AWSM_ERR_INVALID_ARGUMENT, "ktx2: cannot read %s", path);
+        if (err_out && err_cap) snprintf(err_out, err_cap, "%s", h->last_error.c_str());
+        return AWSM_ERR_INVALID_ARGUMENT;
+    }
+    return awsm_host_env_cube_load_ktx2_memory(h, which, bytes.data(), bytes.size(), info_out, err_out, err_cap);
+}
+
 int awsm_host_env(AwsmHost* h, const AwsmEnv* env) { int rc = h->be.env_upload(h->ctx, env); return rc ? dev_fail(h, rc, "env_upload") : AWSM_OK; }
 int awsm_host_brdf_lut_generate(AwsmHost* h, uint32_t w, uint32_t ht) { int rc = h->be.brdf_lut_generate(h->ctx, w, ht); return rc ? dev_fail(h, rc, "brdf_lut_generate") : AWSM_OK; }
 int awsm_host_resize(AwsmHost* h, uint32_t w, uint32_t ht) {

@@ -432,6 +432,46 @@ int awsm_hip_read_transformed(AwsmHipCtx* ctx, float* clip_out, float* normal_ta
 /* ---- device information for the measurement harness ---- */
 int awsm_hip_device_info(AwsmHipCtx* ctx, char* name_out, size_t name_cap, uint32_t* cu_count, uint64_t* hbm_bytes);
 
+/* ---- environment cubes at run time (crates/renderer/src/environment.rs, textures.rs:118-165; renderer-core/src/cubemap.rs:180-323,
+ * cubemap/images.rs, texture/mipmap.rs).  Storage is what awsm_hip_env_cube_upload makes: an RGBA16F chain plus its aproned copy; these entries
+ * fill and change it in place on the device.  The arithmetic (one rounding to f16, nearest even, per conversion; the 2x2 mip filter) is DESIGN.md §12.
+ *   create            a zero-filled chain of `mips` levels (1 .. the full chain); may reallocate, like awsm_hip_env_cube_upload.
+ *   write_face        update_skybox_face / update_cubemap_texture_face: `width` x `height` texels of `format` into level `mip` of one face, read
+ *                     from data[layout.offset + row * bytes_per_row ...]; write_all_faces: six images, rows_per_image rows apart, in face order.
+ *                     Validation follows cubemap.rs:265-323, then WebGPU's own rules for writeTexture (the extent is the level's, bytes_per_row
+ *                     covers a row, rows_per_image covers the image); a refused write leaves the cube as it was.  AWSM_ERR_NOT_READY for a cube
+ *                     never created or uploaded, AWSM_ERR_OUT_OF_RANGE for a level past the chain, AWSM_ERR_UNSUPPORTED for an unknown format.
+ *   generate_mips     regenerate_skybox_mipmaps / regenerate_cubemap_texture_mipmaps: levels 1.. from level 0, each from the stored level above.
+ *   fill_colors       Skybox::new_colors / IblTexture::new_colors: six solid faces (8-bit quantised as create_color does) + the full mip chain.
+ *   fill_sky_gradient CubemapImage::new_sky_gradient: +-X / +-Z carry the gradient (row 0 = zenith), +Y the zenith, -Y the nadir colour + full chain.
+ * Everything is enqueued on the context's stream behind the opaque passes in flight: a frame submitted earlier (AWSM_CFG_OVERLAP_FRAMES) keeps
+ * the old texels, the next one sees the new.  write_* and generate_mips neither reallocate the cube nor synchronise the stream: a source of up
+ * to 4 MiB is copied to the pinned staging ring before the call returns; a larger one is copied from the caller's memory and the call waits for
+ * that copy alone (one event), so `data` is never retained. ---- */
+typedef enum AwsmCubeFormat {
+    AWSM_CUBE_RGBA16F = 0, AWSM_CUBE_RGBA32F = 1, AWSM_CUBE_RGBA8_UNORM = 2, AWSM_CUBE_RGBA8_SRGB = 3,
+    AWSM_CUBE_BGRA8_UNORM = 4, AWSM_CUBE_BGRA8_SRGB = 5, AWSM_CUBE_B10G11R11_UFLOAT = 6, AWSM_CUBE_E5B9G9R9_UFLOAT = 7
+} AwsmCubeFormat;
+/* CubemapBytesLayout (cubemap.rs): where the texels lie in `data` */
+typedef struct AwsmCubeLayout {
+    uint32_t struct_size;      /* sizeof(AwsmCubeLayout) */
+    uint32_t bytes_per_row;
+    uint32_t rows_per_image;
+    uint32_t reserved;         /* 0 */
+    uint64_t offset;
+} AwsmCubeLayout;
+int awsm_hip_env_cube_create(AwsmHipCtx* ctx, AwsmCube which, uint32_t size, uint32_t mips);
+int awsm_hip_env_cube_write_face(AwsmHipCtx* ctx, AwsmCube which, uint32_t face /* 0..5 = +X -X +Y -Y +Z -Z */, uint32_t mip, uint32_t width, uint32_t height,
+                                 AwsmCubeFormat format, const void* data, size_t data_len, const AwsmCubeLayout* layout);
+int awsm_hip_env_cube_write_all_faces(AwsmHipCtx* ctx, AwsmCube which, uint32_t mip, uint32_t width, uint32_t height,
+                                      AwsmCubeFormat format, const void* data, size_t data_len, const AwsmCubeLayout* layout);
+int awsm_hip_env_cube_generate_mips(AwsmHipCtx* ctx, AwsmCube which);
+int awsm_hip_env_cube_fill_colors(AwsmHipCtx* ctx, AwsmCube which, uint32_t size, const float rgba[24] /* six RGBA colours in face order */);
+int awsm_hip_env_cube_fill_sky_gradient(AwsmHipCtx* ctx, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]);
+int awsm_hip_env_cube_info(AwsmHipCtx* ctx, AwsmCube which, uint32_t* size, uint32_t* mips);   /* AWSM_ERR_NOT_READY while the binding is a uniform colour */
+/* one level of the plain chain back to the host (tests): 6 * N * N * 4 halfs, N = max(size >> level, 1); synchronous */
+int awsm_hip_env_cube_read_level(AwsmHipCtx* ctx, AwsmCube which, uint32_t level, uint16_t* rgba16f_out);
+
 #ifdef __cplusplus
 }
 #endif

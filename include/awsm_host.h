@@ -147,6 +147,39 @@ int awsm_host_env(AwsmHost* h, const AwsmEnv* env);
  * [mip][face][y][x][4], faces +X -X +Y -Y +Z -Z; NULL = back to the colour.  The mip counts the shader scales roughness by are the ones of
  * awsm_host_set_ibl_mip_counts (lights.rs:300-305). */
 int awsm_host_env_cube(AwsmHost* h, AwsmCube which, uint32_t size, uint32_t mips, const uint16_t* texels_rgba16f);
+/* Environment cubes at run time: thin wrappers over awsm_hip_env_cube_create / _write_face / _write_all_faces / _generate_mips / _fill_colors /
+ * _fill_sky_gradient (awsm_hip.h has the rules).  The reference's call sites: Skybox::new_colors / IblTexture::new_colors, CubemapImage::new_sky_gradient,
+ * update_skybox_face / update_skybox_all_faces / update_cubemap_texture_face / _all_faces, regenerate_skybox_mipmaps / regenerate_cubemap_texture_mipmaps
+ * (environment.rs, textures.rs:118-165).  The backend's symbols are optional: with a backend library that lacks one, the host still loads and the
+ * call returns AWSM_ERR_UNSUPPORTED, naming the missing symbol.  None of these changes the IBL mip counts (awsm_host_set_ibl_mip_counts). */
+int awsm_host_env_cube_create(AwsmHost* h, AwsmCube which, uint32_t size, uint32_t mips);
+int awsm_host_env_cube_update_face(AwsmHost* h, AwsmCube which, uint32_t face, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                   const void* data, size_t data_len, const AwsmCubeLayout* layout);
+int awsm_host_env_cube_update_all_faces(AwsmHost* h, AwsmCube which, uint32_t mip, uint32_t width, uint32_t height, AwsmCubeFormat format,
+                                        const void* data, size_t data_len, const AwsmCubeLayout* layout);
+int awsm_host_env_cube_regenerate_mipmaps(AwsmHost* h, AwsmCube which);
+int awsm_host_env_cube_colors(AwsmHost* h, AwsmCube which, uint32_t size, const float rgba[24]);
+int awsm_host_env_cube_sky_gradient(AwsmHost* h, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]);
+/* KTX2 cube maps (renderer-core/src/cubemap/ktx.rs:39-147; the rules and their reasons are restated in host/ktx2.hpp).  Accepted vkFormats: 37, 43,
+ * 44, 50 (RGBA8 / BGRA8, UNORM / SRGB), 97 (RGBA16F), 109 (RGBA32F), 122 (B10G11R11), 123 (E5B9G9R9); any other format — block-compressed and
+ * depth formats among them — is AWSM_ERR_UNSUPPORTED with the vkFormat number in the message; every other rejection is AWSM_ERR_INVALID_ARGUMENT.
+ * awsm_host_ktx2_parse is a pure function: no host, no device.  The loaders parse, create the cube with info.mips levels, write each stored
+ * level with the tight layout, and — levelCount 0, "generate the chain" — make the other levels on the device.  The caller passes
+ * info.mips to awsm_host_set_ibl_mip_counts, as it does for awsm_host_env_cube. */
+typedef struct AwsmKtx2Level { uint64_t offset, length; } AwsmKtx2Level;
+typedef struct AwsmKtx2Info {
+    uint32_t struct_size;     /* IN: sizeof(AwsmKtx2Info) */
+    uint32_t vk_format;       /* as stored */
+    uint32_t format;          /* the AwsmCubeFormat it maps to */
+    uint32_t size;            /* pixelWidth == pixelHeight */
+    uint32_t faces, layers;   /* faceCount (6), layerCount (0) */
+    uint32_t levels;          /* levels stored in the file: levelCount, or 1 when it is 0 */
+    uint32_t mips;            /* levels of the cube made from it: levelCount, or the full chain when it is 0 */
+    AwsmKtx2Level level[16];  /* byte range of each stored level, level 0 (the largest) first */
+} AwsmKtx2Info;
+int awsm_host_ktx2_parse(const uint8_t* data, size_t len, AwsmKtx2Info* out, char* err_out, size_t err_cap);
+int awsm_host_env_cube_load_ktx2(AwsmHost* h, AwsmCube which, const char* path, AwsmKtx2Info* info_out, char* err_out, size_t err_cap);
+int awsm_host_env_cube_load_ktx2_memory(AwsmHost* h, AwsmCube which, const uint8_t* data, size_t len, AwsmKtx2Info* info_out, char* err_out, size_t err_cap);
 int awsm_host_brdf_lut_generate(AwsmHost* h, uint32_t w, uint32_t height);
 int awsm_host_resize(AwsmHost* h, uint32_t width, uint32_t height);
 /* AwsmRenderer::set_anti_aliasing (anti_alias.rs:9-45): msaa_sample_count 0 (None) or 4 (recreates the render targets);
