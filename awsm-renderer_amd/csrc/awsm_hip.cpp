@@ -18,6 +18,7 @@
 #include "frame_params.hpp"
 #include "dirty_log.hpp"
 #include "env_cube.hpp"
+#include "env_filter_table.hpp"
 
 using namespace awsm;
 
@@ -53,6 +54,8 @@ void awsm_launch_rgba16f_to_rg16f(const uint16_t* in, uint32_t* out, uint32_t n,
 void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s);
 void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, uint2* dst, uint32_t n, hipStream_t s);
 void awsm_launch_env_mips(const awsm::EnvMipArgs* a, hipStream_t s);
+void awsm_launch_env_filter(const awsm::EnvFilterArgs* a, uint32_t blocks, hipStream_t s);
+void awsm_launch_env_filter_level0(const awsm::EnvFilterLevel0Args* a, hipStream_t s);
 }
 
 namespace {
@@ -134,7 +137,7 @@ struct AwsmHipCtx {
     DevBuf cube_tex[3], cube_bordered[3];      // the uploaded chains; the same with a one-texel apron per face (CubeDev.bordered)
     // awsm_hip_env_cube_write_* / fill_*: the source bytes on the device (grow-only, reused), the 8-bit -> f16 tables, the fills' row table,
     // and the event a write waits on when it copied straight from the caller's memory
-    DevBuf env_stage, env_tables, env_rows;
+    DevBuf env_stage, env_tables, env_rows, env_filter_tab;      // env_filter_tab: the sample tables of awsm_hip_env_cube_filter
     hipEvent_t ev_env_copy = nullptr;
 
     // frame targets
@@ -1123,7 +1126,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->bufs) fr(b);
     for (auto& b : c->tex) fr(b);
     for (auto& b : c->merged_vis) fr(b);
-    fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
+    fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 4 * kSlots; k++) {
@@ -1674,6 +1677,59 @@ int awsm_hip_env_cube_read_level(AwsmHipCtx* c, AwsmCube which, uint32_t level, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n = std::max(1u, cd.size >> level);
     HIPCHK(c, hipMemcpy(out, cd.texels + cd.level_off[level], 6 * n * n * 8, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+// DESIGN.md §13.  The destination's levels are made from the source alone: level 0 by k_env_filter_level0, every other prefiltered level (or the one
+// irradiance level) by one launch of k_env_filter over tables built here in f64 (env_filter_table.hpp) and uploaded through the staging ring.
+int awsm_hip_env_cube_filter(AwsmHipCtx* c, AwsmCube src, AwsmCube dst, const AwsmEnvFilter* f) {
+    { int rc = cube_id_ok(c, src, "env_cube_filter"); if (rc) return rc; }
+    { int rc = cube_id_ok(c, dst, "env_cube_filter"); if (rc) return rc; }
+    if (!f || f->struct_size != sizeof(AwsmEnvFilter)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_filter: a filter with struct_size %zu is missing", sizeof(AwsmEnvFilter));
+    if (src == dst) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_filter: cube %d cannot be filtered into itself", (int)src);
+    const uint32_t samples = f->sample_count ? f->sample_count : 1024u;
+    if (f->kind > 1u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_filter: kind %u (0 GGX chain, 1 Lambert)", f->kind);
+    if (samples < 16u || samples > 4096u || (samples & (samples - 1u))) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_filter: %u samples (a power of two, 16..4096)", samples);
+    if (f->size == 0 || f->size > 8192 || f->mips == 0 || f->mips > (uint32_t)kMaxMipLevels || f->mips > mip_levels_full(f->size, f->size) || (f->kind == 1u && f->mips != 1u))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_filter: %u mip levels of a %u^2 cube (1..8192 per side; GGX: at most %u levels, Lambert: 1)", f->mips, f->size,
+                    f->size ? mip_levels_full(f->size, f->size) : 0u);
+    if (!c->scene.cube[src].texels) return fail(c, AWSM_ERR_NOT_READY, "env_cube_filter: source cube %d is a uniform colour", (int)src);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->scene.cube[dst].texels && c->scene.cube[dst].size == f->size && c->scene.cube[dst].mips == f->mips) {
+        int rcb = scene_write_barrier(c); if (rcb) return rcb;
+    } else {
+        int rc = cube_create(c, dst, f->size, f->mips, false, "env_cube_filter"); if (rc) return rc;      // every level is written below
+    }
+    const CubeDev sd = c->scene.cube[src], dd = c->scene.cube[dst];      // after the create: a reallocation does not move the source
+    uint2* out = (uint2*)c->cube_tex[dst].ptr;
+
+    EnvFilterArgs a{};
+    a.src = sd; a.dst = out; a.lambert = f->kind; a.k = (float)(kEnvFilterPi / (double)samples);
+    std::vector<EnvFilterEntry> tab;
+    uint32_t blocks = 0;
+    for (uint32_t l = f->kind == 1u ? 0u : 1u; l < f->mips; l++) {
+        const std::vector<EnvFilterEntry> t = env_filter_table(f->kind, l, f->mips, samples, sd.size);
+        EnvFilterLevel& lv = a.level[a.n_levels++];
+        lv.dst_off = dd.level_off[l]; lv.n = std::max(1u, f->size >> l); lv.first_block = blocks;
+        lv.table_off = (uint32_t)tab.size(); lv.count = (uint32_t)t.size();
+        blocks += (6u * lv.n * lv.n + 3u) / 4u;
+        tab.insert(tab.end(), t.begin(), t.end());
+    }
+    if (!tab.empty()) {
+        int rc = dev_reserve(c, c->env_filter_tab, tab.size() * sizeof(EnvFilterEntry));
+        if (!rc) rc = upload_small(c, c->env_filter_tab.ptr, tab.data(), tab.size() * sizeof(EnvFilterEntry));
+        if (rc) return rc;
+        a.tables = (const float*)c->env_filter_tab.ptr;
+    }
+    if (f->kind == 0u) {
+        EnvFilterLevel0Args z{};
+        z.src = sd; z.dst = out; z.n = f->size;
+        z.lod = (float)std::max(0.0, std::log2((double)sd.size / (double)f->size));
+        awsm_launch_env_filter_level0(&z, c->stream);
+    }
+    awsm_launch_env_filter(&a, blocks, c->stream);
+    cube_reborder(c, dst, 0, f->mips);
+    HIPCHK(c, hipGetLastError());
     return AWSM_OK;
 }
 

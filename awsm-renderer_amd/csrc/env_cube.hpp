@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "frame_params.hpp"
 
 namespace awsm {
 
@@ -24,6 +25,31 @@ struct EnvMipArgs {
     uint32_t src_n;             // its side
     uint32_t n_levels;          // levels made by this launch, 1..5
     uint32_t dst_off[5];        // first texel of each
+};
+
+// k_env_filter / k_env_filter_level0 (awsm_hip_env_cube_filter): a source cube filtered into levels of a destination chain
+constexpr uint32_t kEnvFilterChunk = 1024;      // table entries staged in LDS at a time (20 KB)
+struct EnvFilterLevel {
+    uint32_t dst_off;           // first texel of the level in the destination's plain chain
+    uint32_t n;                 // its side
+    uint32_t first_block;       // the level's workgroups are [first_block, first_block + ceil(6 n^2 / 4))
+    uint32_t table_off;         // first entry of the level's table
+    uint32_t count;             // entries (those with a positive weight), <= 4096
+};
+struct EnvFilterArgs {
+    CubeDev src;                // bordered null: the plain chain with the seam rule
+    uint2* dst;                 // the destination's plain chain
+    const float* tables;        // EnvFilterEntry records (env_filter_table.hpp), five floats each
+    uint32_t n_levels;          // levels made by this launch
+    uint32_t lambert;           // 0: sum(w s) / sum(w), directions mirrored about the half vector; 1: k * sum(s)
+    float k;
+    EnvFilterLevel level[kMaxMipLevels];
+};
+struct EnvFilterLevel0Args {
+    CubeDev src;
+    uint2* dst;                 // level 0 of the destination
+    uint32_t n;                 // its side
+    float lod;                  // max(0, log2(src.size / n)); unused when n == src.size (the bits are copied)
 };
 
 }  // namespace awsm

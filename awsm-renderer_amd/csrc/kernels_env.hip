@@ -1,6 +1,7 @@
 // kernels_env.hip — environment cubes at run time (include/awsm_hip.h: awsm_hip_env_cube_write_face / _write_all_faces / _generate_mips /
 // _fill_colors / _fill_sky_gradient): source texels of eight formats -> RGBA16F, the 2x2 mip filter through five levels per launch, and the
-// expansion of a per-row colour table.  The reference's counterparts are gpu.write_texture (renderer-core/src/cubemap.rs:180-228) and the mip
+// expansion of a per-row colour table; and awsm_hip_env_cube_filter: a source cube filtered into a GGX-prefiltered chain or a
+// Lambert irradiance level.  The reference's counterparts are gpu.write_texture (renderer-core/src/cubemap.rs:180-228) and the mip
 // compute pass (renderer-core/src/texture/mipmap.rs:143-232, filter_simple for MipmapTextureKind::Albedo).  The arithmetic is DESIGN.md §12:
 // every conversion rounds to f16 once, to nearest even; nothing here may be contracted into an fma (-ffp-contract=off).
 // The apron of the changed levels is rebuilt afterwards by k_cube_border (kernels_shade.hip), which owns the seam rule.
@@ -134,8 +135,145 @@ __global__ __launch_bounds__(256) void k_env_mips(EnvMipArgs a) {
     }
 }
 
+// ---------------- filtering a source cube into the split-sum inputs (awsm_hip_env_cube_filter) ----------------
+// textureSampleLevel on the source by sample_cube's contract (kernels_shade.hip, restated: that file's code objects stay as they are): the major
+// axis picks the face, bilinear on the level's N x N faces, a tap off the face comes from the face across that edge, the level is clamped to the
+// chain and its two nearest levels are blended.  Divisions and square roots are IEEE here; nothing is clamped, so a non-finite texel propagates.
+__device__ const uint8_t kEnvCubeEdge[6][4] = {{44, 13, 58, 43}, {45, 12, 10, 27}, {1, 16, 21, 4}, {49, 32, 36, 53}, {41, 8, 34, 3}, {40, 9, 18, 51}};
+AWSM_DI uint2 env_texel_seam(const CubeDev& c, uint32_t level_base, int N, uint32_t face, int i, int j) {      // cube_texel_raw
+    if (i < 0 || i >= N) j = min(max(j, 0), N - 1);     // corner taps keep their row
+    if (i < 0 || i >= N || j < 0 || j >= N) {
+        const uint32_t e = i < 0 ? 0u : (i >= N ? 1u : (j < 0 ? 2u : 3u));
+        const uint32_t t = kEnvCubeEdge[face][e];
+        int k = e < 2u ? j : i;
+        if (t & 16u) k = N - 1 - k;
+        const int far = (t & 32u) ? N - 1 : 0;
+        face = t & 7u;
+        if (t & 8u) { i = far; j = k; } else { i = k; j = far; }
+    }
+    return c.texels[level_base + ((size_t)face * (size_t)N + (size_t)j) * (size_t)N + (size_t)i];
+}
+AWSM_DI f3 env_lerp3(f3 a, f3 b, float t) { const float s = 1.0f - t; return {a.x * s + b.x * t, a.y * s + b.y * t, a.z * s + b.z * t}; }
+AWSM_DI f3 env_rgb(uint2 h) { return {f16_bits_to_f32((unsigned short)(h.x & 0xFFFFu)), f16_bits_to_f32((unsigned short)(h.x >> 16)), f16_bits_to_f32((unsigned short)(h.y & 0xFFFFu))}; }
+// one level; sn, tn = 0.5 (sc / ma) + 0.5 on `face`
+AWSM_DI f3 env_cube_level(const CubeDev& c, uint32_t level, uint32_t face, float sn, float tn) {
+    const int N = (int)max(c.size >> level, 1u);
+    float x = sn * (float)N - 0.5f, y = tn * (float)N - 0.5f;
+    if (!(x >= -0.5f)) x = -0.5f;                 // also NaN (zero / non-finite direction): the face's first texel
+    if (!(y >= -0.5f)) y = -0.5f;
+    x = fminf(x, (float)N - 0.5f); y = fminf(y, (float)N - 0.5f);
+    const float flx = floorf(x), fly = floorf(y), fx = x - flx, fy = y - fly;
+    const int i0 = (int)flx, j0 = (int)fly;      // -1 .. N - 1
+    uint2 t00, t10, t01, t11;
+    if (c.bordered) {                             // the footprint lies inside the face's (N + 2)^2 array: two adjacent texels of two rows
+        const uint32_t P = (uint32_t)N + 2u;
+        const uint2* r0 = c.bordered + c.b_level_off[level] + ((size_t)face * P + (uint32_t)(j0 + 1)) * P + (uint32_t)(i0 + 1);
+        t00 = r0[0]; t10 = r0[1]; t01 = r0[P]; t11 = r0[P + 1u];
+    } else {
+        const uint32_t base = c.level_off[level];
+        t00 = env_texel_seam(c, base, N, face, i0, j0); t10 = env_texel_seam(c, base, N, face, i0 + 1, j0);
+        t01 = env_texel_seam(c, base, N, face, i0, j0 + 1); t11 = env_texel_seam(c, base, N, face, i0 + 1, j0 + 1);
+    }
+    return env_lerp3(env_lerp3(env_rgb(t00), env_rgb(t10), fx), env_lerp3(env_rgb(t01), env_rgb(t11), fx), fy);
+}
+AWSM_DI f3 env_sample_cube(const CubeDev& c, f3 d, float level) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    uint32_t face; float sc, tc, ma;
+    if (az >= ax && az >= ay) { face = d.z < 0.0f ? 5u : 4u; sc = d.z < 0.0f ? -d.x : d.x; tc = -d.y; ma = az; }
+    else if (ay >= ax) { face = d.y < 0.0f ? 3u : 2u; sc = d.x; tc = d.y < 0.0f ? -d.z : d.z; ma = ay; }
+    else { face = d.x < 0.0f ? 1u : 0u; sc = d.x < 0.0f ? d.z : -d.z; tc = -d.y; ma = ax; }
+    const float inv = 1.0f / ma;
+    const float sn = 0.5f * (sc * inv) + 0.5f, tn = 0.5f * (tc * inv) + 0.5f;
+    const float top = (float)(c.mips - 1u);
+    float lod = level > 0.0f ? level : 0.0f;          // also NaN
+    lod = fminf(lod, top);
+    const float fl = floorf(lod), fr = lod - fl;
+    const uint32_t l0 = (uint32_t)fl, l1 = min(l0 + 1u, c.mips - 1u);
+    f3 r = env_cube_level(c, l0, face, sn, tn);
+    if (fr > 0.0f && l1 != l0) r = env_lerp3(r, env_cube_level(c, l1, face, sn, tn), fr);
+    return r;
+}
+// the direction through the centre of texel (i, j) of `face` on a level of side n: the inverse of sample_cube's face table
+AWSM_DI f3 env_texel_dir(uint32_t face, uint32_t i, uint32_t j, uint32_t n) {
+    const float s = (2.0f * ((float)i + 0.5f)) / (float)n - 1.0f, t = (2.0f * ((float)j + 0.5f)) / (float)n - 1.0f;
+    f3 d;
+    switch (face) {
+    case 0: d = {1.0f, -t, -s}; break;
+    case 1: d = {-1.0f, -t, s}; break;
+    case 2: d = {s, 1.0f, t}; break;
+    case 3: d = {s, -1.0f, -t}; break;
+    case 4: d = {s, -t, 1.0f}; break;
+    default: d = {-s, -t, -1.0f}; break;
+    }
+    return normalize(d);
+}
+
+// One wavefront per output texel, four texels of one level per workgroup.  The level's table goes through LDS in chunks of kEnvFilterChunk entries;
+// lane l takes entries l, l + 64, ... in that order (a chunk is a multiple of 64 long, so the order does not depend on the chunking), accumulates in
+// f32, and the 64 partial sums meet in a fixed xor butterfly — no atomics: the same input gives the same bits.
+__global__ __launch_bounds__(256) void k_env_filter(EnvFilterArgs a) {
+    __shared__ float tab[kEnvFilterChunk * 5u];
+    uint32_t li = 0u;
+    while (li + 1u < a.n_levels && blockIdx.x >= a.level[li + 1u].first_block) li++;
+    const EnvFilterLevel lv = a.level[li];
+    const uint32_t lane = threadIdx.x & 63u, per_face = lv.n * lv.n;
+    const uint32_t texel = (blockIdx.x - lv.first_block) * 4u + (threadIdx.x >> 6);
+    const bool live = texel < 6u * per_face;      // the padding of the level's last workgroup still stages the table
+    const uint32_t face = live ? texel / per_face : 0u, q = live ? texel - face * per_face : 0u;
+    const f3 n = env_texel_dir(face, q % lv.n, q / lv.n, lv.n);
+    const f3 up = fabsf(n.z) < 0.999f ? mk3(0.0f, 0.0f, 1.0f) : mk3(1.0f, 0.0f, 0.0f);
+    const f3 T = normalize(cross(up, n)), B = cross(n, T);
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
+    for (uint32_t base = 0u; base < lv.count; base += kEnvFilterChunk) {
+        const uint32_t m = min(kEnvFilterChunk, lv.count - base);
+        __syncthreads();
+        const float* src = a.tables + (size_t)(lv.table_off + base) * 5u;
+        for (uint32_t k = threadIdx.x; k < m * 5u; k += 256u) tab[k] = src[k];
+        __syncthreads();
+        if (live) {
+            for (uint32_t e = lane; e < m; e += 64u) {
+                const float hx = tab[e * 5u], hy = tab[e * 5u + 1u], hz = tab[e * 5u + 2u], w = tab[e * 5u + 3u], lod = tab[e * 5u + 4u];
+                f3 L = {(T.x * hx + B.x * hy) + n.x * hz, (T.y * hx + B.y * hy) + n.y * hz, (T.z * hx + B.z * hy) + n.z * hz};
+                if (!a.lambert) { const float c2 = 2.0f * hz; L = {c2 * L.x - n.x, c2 * L.y - n.y, c2 * L.z - n.z}; }      // V = N mirrored about H
+                const f3 s = env_sample_cube(a.src, L, lod);
+                sr += w * s.x; sg += w * s.y; sb += w * s.z; sw += w;
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sr += __shfl_xor(sr, off); sg += __shfl_xor(sg, off); sb += __shfl_xor(sb, off); sw += __shfl_xor(sw, off);
+    }
+    if (lane == 0u) {
+        const float r = a.lambert ? a.k * sr : sr / sw, g = a.lambert ? a.k * sg : sg / sw, b = a.lambert ? a.k * sb : sb / sw;
+        a.dst[lv.dst_off + texel] = pack_half4(f16_bits(r), f16_bits(g), f16_bits(b), kHalfOne);
+    }
+}
+
+// level 0 of a prefiltered chain (roughness 0): the source's own texels, or the source resampled when the sides differ
+__global__ __launch_bounds__(256) void k_env_filter_level0(EnvFilterLevel0Args a) {
+    const uint32_t per_face = a.n * a.n, idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= 6u * per_face) return;
+    if (a.n == a.src.size) {
+        const uint2 t = a.src.texels[idx];
+        a.dst[idx] = make_uint2(t.x, (t.y & 0xFFFFu) | kHalfOne << 16);
+        return;
+    }
+    const uint32_t face = idx / per_face, q = idx - face * per_face;
+    const f3 s = env_sample_cube(a.src, env_texel_dir(face, q % a.n, q / a.n, a.n), a.lod);
+    a.dst[idx] = pack_half4(f16_bits(s.x), f16_bits(s.y), f16_bits(s.z), kHalfOne);
+}
+
 }  // namespace awsm
 
+extern "C" void awsm_launch_env_filter(const awsm::EnvFilterArgs* a, uint32_t blocks, hipStream_t s) {
+    if (blocks) hipLaunchKernelGGL(awsm::k_env_filter, dim3(blocks), dim3(256), 0, s, *a);
+}
+extern "C" void awsm_launch_env_filter_level0(const awsm::EnvFilterLevel0Args* a, hipStream_t s) {
+    const uint32_t total = 6u * a->n * a->n;
+    hipLaunchKernelGGL(awsm::k_env_filter_level0, dim3((total + 255u) / 256u), dim3(256), 0, s, *a);
+}
 extern "C" void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s) {
     const uint32_t total = a->n * a->n * a->layers;
     if (total) hipLaunchKernelGGL(awsm::k_env_write, dim3((total + 255u) / 256u), dim3(256), 0, s, *a);

@@ -35,7 +35,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_frame_trace", "awsm_hip_read_frame_trace", "awsm_hip_hud_geometry_pass", "awsm_hip_hud_transparent_pass",
            "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr",
            "awsm_hip_env_cube_create", "awsm_hip_env_cube_write_face", "awsm_hip_env_cube_write_all_faces", "awsm_hip_env_cube_generate_mips",
-           "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level"]
+           "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level",
+           "awsm_hip_env_cube_filter"]
 
 
 class AwsmConfig(C.Structure):
@@ -58,6 +59,12 @@ class AwsmPostParams(C.Structure):
 class AwsmCubeLayout(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bytes_per_row", C.c_uint32), ("rows_per_image", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64)]
 
+
+class AwsmEnvFilter(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("size", C.c_uint32), ("mips", C.c_uint32), ("sample_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ENV_FILTER_KINDS = {"ggx": 0, "lambert": 1}
 
 # AwsmCubeFormat: name -> (value, bytes per texel)
 CUBE_FORMATS = {"rgba16f": (0, 8), "rgba32f": (1, 16), "rgba8unorm": (2, 4), "rgba8unorm-srgb": (3, 4), "bgra8unorm": (4, 4), "bgra8unorm-srgb": (5, 4),
@@ -180,6 +187,7 @@ def load_library():
     lib.awsm_hip_env_cube_fill_sky_gradient.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.awsm_hip_env_cube_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.awsm_hip_env_cube_read_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+    lib.awsm_hip_env_cube_filter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -344,6 +352,17 @@ class HipDevice:
         out = np.zeros((6, n, n, 4), dtype=np.float16)
         self._chk(self.lib.awsm_hip_env_cube_read_level(self.ctx, which, level, out.ctypes.data_as(C.c_void_p)), "env_cube_read_level")
         return out
+
+    def env_cube_filter(self, src: int, dst: int, kind="ggx", size: int = 0, mips: Optional[int] = None, sample_count: int = 0):
+        """Cube `src` filtered into cube `dst`: kind "ggx" makes the prefiltered chain of `mips` levels (default: the full chain of
+        `size`), "lambert" one level of irradiance.  size 0 takes the source's side; sample_count 0 means 1024.  The source should carry its mip chain."""
+        k = ENV_FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if not size:
+            size = self.env_cube_info(src)[0]
+        if mips is None:
+            mips = 1 if k == 1 else int(size).bit_length()
+        f = AwsmEnvFilter(C.sizeof(AwsmEnvFilter), k, size, mips, sample_count, 0)
+        self._chk(self.lib.awsm_hip_env_cube_filter(self.ctx, src, dst, C.byref(f)), "env_cube_filter")
 
     def env_upload(self, skybox=(0, 0, 0, 1), prefiltered=(1, 1, 1), irradiance=(1, 1, 1), lut_rgba16f: Optional[np.ndarray] = None):
         env = AwsmEnv()

@@ -97,6 +97,7 @@ def load_library():
         "awsm_host_env_cube_regenerate_mipmaps": (C.c_int, [vp, C.c_int]),
         "awsm_host_env_cube_colors": (C.c_int, [vp, C.c_int, C.c_uint32, vp]),
         "awsm_host_env_cube_sky_gradient": (C.c_int, [vp, C.c_int, C.c_uint32, vp, vp]),
+        "awsm_host_env_bake_ibl": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "awsm_host_ktx2_parse": (C.c_int, [vp, sz, vp, C.c_char_p, sz]),
         "awsm_host_env_cube_load_ktx2": (C.c_int, [vp, C.c_int, C.c_char_p, vp, C.c_char_p, sz]),
         "awsm_host_env_cube_load_ktx2_memory": (C.c_int, [vp, C.c_int, vp, sz, vp, C.c_char_p, sz]),
@@ -385,6 +386,13 @@ class Host:
         """CubemapImage::new_sky_gradient (the defaults are CubemapSkyGradient::default)."""
         z, n = (C.c_float * 4)(*zenith), (C.c_float * 4)(*nadir)
         self._chk(self.lib.awsm_host_env_cube_sky_gradient(self.h, which, size, z, n), "env_cube_sky_gradient")
+
+    def env_bake_ibl(self, prefiltered_size: int = 128, prefiltered_mips: Optional[int] = None, irradiance_size: int = 32, sample_count: int = 0):
+        """The prefiltered chain and the irradiance cube filtered on the device from the skybox as it is now; sets the IBL mip counts.  Call again
+        whenever the skybox changes.  prefiltered_mips defaults to the chain down to 4^2 texels (the last levels hold almost no detail)."""
+        if prefiltered_mips is None:
+            prefiltered_mips = max(1, int(prefiltered_size).bit_length() - 2)
+        self._chk(self.lib.awsm_host_env_bake_ibl(self.h, prefiltered_size, prefiltered_mips, irradiance_size, sample_count), "env_bake_ibl")
 
     def env_cube_load_ktx2(self, which: int, source) -> dict:
         """A KTX2 cube map from a path or from bytes; returns the parsed header (pass info["mips"] to set_ibl_mip_counts for an IBL cube)."""

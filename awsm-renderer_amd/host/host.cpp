@@ -71,6 +71,7 @@ struct Backend {
     int (*env_cube_generate_mips)(AwsmHipCtx*, AwsmCube) = nullptr;
     int (*env_cube_fill_colors)(AwsmHipCtx*, AwsmCube, uint32_t, const float*) = nullptr;
     int (*env_cube_fill_sky_gradient)(AwsmHipCtx*, AwsmCube, uint32_t, const float*, const float*) = nullptr;
+    int (*env_cube_filter)(AwsmHipCtx*, AwsmCube, AwsmCube, const AwsmEnvFilter*) = nullptr;      // optional (awsm_host_env_bake_ibl)
 };
 
 struct Transform { Vec3 t; Quat r; Vec3 s; };
@@ -522,6 +523,7 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.env_cube_generate_mips = reinterpret_cast<decltype(b.env_cube_generate_mips)>(dlsym(b.dl, "awsm_hip_env_cube_generate_mips"));
     b.env_cube_fill_colors = reinterpret_cast<decltype(b.env_cube_fill_colors)>(dlsym(b.dl, "awsm_hip_env_cube_fill_colors"));
     b.env_cube_fill_sky_gradient = reinterpret_cast<decltype(b.env_cube_fill_sky_gradient)>(dlsym(b.dl, "awsm_hip_env_cube_fill_sky_gradient"));
+    b.env_cube_filter = reinterpret_cast<decltype(b.env_cube_filter)>(dlsym(b.dl, "awsm_hip_env_cube_filter"));
     if (b.abi_version() != AWSM_HIP_ABI_VERSION) { dlclose(b.dl); return AWSM_ERR_INVALID_ARGUMENT; }
     AwsmConfig cfg{};
     cfg.struct_size = sizeof cfg; cfg.abi_version = AWSM_HIP_ABI_VERSION; cfg.device = device; cfg.flags = cfg_flags; cfg.stream = stream;
@@ -987,6 +989,17 @@ int awsm_host_env_cube_sky_gradient(AwsmHost* h, AwsmCube which, uint32_t size, 
     AWSM_ENV_CUBE_CALL(env_cube_fill_sky_gradient, "awsm_hip_env_cube_fill_sky_gradient", which, size, zenith, nadir);
 }
 #undef AWSM_ENV_CUBE_CALL
+// The two cubes the opaque pass lights with, filtered on the device from the skybox as it is now (the reference loads them ready-made: ibl.rs:19-28)
+int awsm_host_env_bake_ibl(AwsmHost* h, uint32_t prefiltered_size, uint32_t prefiltered_mips, uint32_t irradiance_size, uint32_t sample_count) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.env_cube_filter) return fail(h, AWSM_ERR_UNSUPPORTED, "the backend library has no %s", "awsm_hip_env_cube_filter");
+    const AwsmEnvFilter ggx = {(uint32_t)sizeof(AwsmEnvFilter), 0u, prefiltered_size, prefiltered_mips, sample_count, 0u};
+    const AwsmEnvFilter lambert = {(uint32_t)sizeof(AwsmEnvFilter), 1u, irradiance_size, 1u, sample_count, 0u};
+    int rc = h->be.env_cube_filter(h->ctx, AWSM_CUBE_SKYBOX, AWSM_CUBE_PREFILTERED, &ggx);
+    if (!rc) rc = h->be.env_cube_filter(h->ctx, AWSM_CUBE_SKYBOX, AWSM_CUBE_IRRADIANCE, &lambert);
+    if (rc) return dev_fail(h, rc, "env_cube_filter");
+    return awsm_host_set_ibl_mip_counts(h, prefiltered_mips, 1u);
+}
 
 int awsm_host_ktx2_parse(const uint8_t* data, size_t len, AwsmKtx2Info* out, char* err_out, size_t err_cap) { return ktx2::parse(data, len, out, err_out, err_cap); }
 

@@ -7,7 +7,8 @@ The output image of the opaque pass is linear HDR RGBA16F; the PNG is Reinhard t
 --tonemap {khronos,aces,none}, --bloom, --dof, --smaa the frame ends with the effects + display passes instead, and the PNG is the device's
 RGBA8 display image as it stands (--dof uses the reference's focus distance 10 and aperture 5.6 unless --focus / --aperture say otherwise).
 --sky-gradient makes the skybox the reference's default gradient sky (CubemapImage::new_sky_gradient, 256^2 with its mip chain, built on the
-device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefiltered environment of the IBL.
+device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefiltered environment of the IBL.  With --bake-ibl the scene is lit
+by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
 """
 import argparse
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--aperture", type=float, default=5.6)
     ap.add_argument("--sky-gradient", action="store_true", help="skybox = the default zenith / nadir gradient cube")
     ap.add_argument("--env-ktx2", metavar="PATH", help="a KTX2 cube map for the skybox and the prefiltered environment")
+    ap.add_argument("--bake-ibl", action="store_true", help="with --sky-gradient / --env-ktx2: filter the IBL cubes from the skybox on the device")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -51,11 +53,16 @@ def main():
     r = Renderer(sc, msaa=a.msaa, mipmap=a.mipmap, gltf=gltf)
     if a.sky_gradient:
         r.host.env_cube_sky_gradient(0, 256)
+    if a.bake_ibl and not (a.sky_gradient or a.env_ktx2):
+        ap.error("--bake-ibl filters the skybox cube: give --sky-gradient or --env-ktx2")
     if a.env_ktx2:
         info = r.host.env_cube_load_ktx2(0, a.env_ktx2)
-        r.host.env_cube_load_ktx2(1, a.env_ktx2)
-        r.host.set_ibl_mip_counts(info["mips"], sc.irradiance_mip_count)      # the prefiltered lookup scales roughness by the file's level count
+        if not a.bake_ibl:
+            r.host.env_cube_load_ktx2(1, a.env_ktx2)
+            r.host.set_ibl_mip_counts(info["mips"], sc.irradiance_mip_count)      # the prefiltered lookup scales roughness by the file's level count
         print(f"{a.env_ktx2}: {info['size']}^2 {info['format_name']}, {info['levels']} stored level(s), {info['mips']} in the cube")
+    if a.bake_ibl:
+        r.host.env_bake_ibl(128, 6, 32)                                           # 128 64 32 16 8 4; sets the IBL mip counts
     post = a.tonemap is not None or a.bloom or a.dof or a.smaa
     if post:
         from awsm_renderer_amd.hip_backend import TONEMAP

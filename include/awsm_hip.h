@@ -472,6 +472,26 @@ int awsm_hip_env_cube_info(AwsmHipCtx* ctx, AwsmCube which, uint32_t* size, uint
 /* one level of the plain chain back to the host (tests): 6 * N * N * 4 halfs, N = max(size >> level, 1); synchronous */
 int awsm_hip_env_cube_read_level(AwsmHipCtx* ctx, AwsmCube which, uint32_t level, uint16_t* rgba16f_out);
 
+/* ---- image-based lighting from a source cube (the reference takes its filtered cubes from an offline tool) ----
+ * Filters cube `src` into cube `dst`, which becomes an RGBA16F chain of `size`^2 x `mips` (alpha 1.0), reallocated like awsm_hip_env_cube_create when
+ * its shape differs:
+ *   kind 0  the GGX-prefiltered chain the opaque pass samples at roughness * (mips - 1): level m holds roughness m / (mips - 1), alpha = roughness^2,
+ *           importance-sampled with the BRDF LUT's Hammersley set; level 0 is the source itself (its bits when the sides are equal, else resampled).
+ *   kind 1  one level of cosine-weighted irradiance (the integral of L cos over the hemisphere: the shader multiplies by base_color / pi).
+ * Samples read the source at a level chosen from their density, so the source should carry its full mip chain: call awsm_hip_env_cube_generate_mips
+ * on it first (a short chain simply clamps the level).  The source is not modified.  Non-finite source texels propagate; nothing is clamped.
+ * Enqueued on the context's stream like the other env_cube writes, with no stream synchronise unless the destination is reallocated; two calls on the
+ * same input give the same bits.  AWSM_ERR_NOT_READY: the source is a uniform colour; AWSM_ERR_INVALID_ARGUMENT: src == dst, bad counts or sizes. ---- */
+typedef struct AwsmEnvFilter {
+    uint32_t struct_size;  /* sizeof(AwsmEnvFilter) */
+    uint32_t kind;         /* 0 GGX chain, 1 Lambert */
+    uint32_t size;         /* 1..8192 */
+    uint32_t mips;         /* GGX: 1..full chain of size; Lambert: 1 */
+    uint32_t sample_count; /* power of two, 16..4096; 0 = 1024 */
+    uint32_t reserved;     /* 0 */
+} AwsmEnvFilter;
+int awsm_hip_env_cube_filter(AwsmHipCtx* ctx, AwsmCube src, AwsmCube dst, const AwsmEnvFilter* filter);
+
 #ifdef __cplusplus
 }
 #endif

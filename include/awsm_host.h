@@ -160,6 +160,12 @@ int awsm_host_env_cube_update_all_faces(AwsmHost* h, AwsmCube which, uint32_t mi
 int awsm_host_env_cube_regenerate_mipmaps(AwsmHost* h, AwsmCube which);
 int awsm_host_env_cube_colors(AwsmHost* h, AwsmCube which, uint32_t size, const float rgba[24]);
 int awsm_host_env_cube_sky_gradient(AwsmHost* h, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]);
+/* Image-based lighting from the skybox: AWSM_CUBE_PREFILTERED becomes the GGX chain (prefiltered_size^2, prefiltered_mips levels) and
+ * AWSM_CUBE_IRRADIANCE one level of irradiance_size^2, both filtered on the device from AWSM_CUBE_SKYBOX as it is at the call
+ * (awsm_hip_env_cube_filter, twice; sample_count 0 = 1024), then awsm_host_set_ibl_mip_counts(prefiltered_mips, 1).  The skybox must be a texel cube
+ * and should carry its mip chain (the fills and the KTX2 loader make one).  Call it again whenever the skybox changes.  AWSM_ERR_UNSUPPORTED, naming
+ * the symbol, with a backend library that lacks awsm_hip_env_cube_filter. */
+int awsm_host_env_bake_ibl(AwsmHost* h, uint32_t prefiltered_size, uint32_t prefiltered_mips, uint32_t irradiance_size, uint32_t sample_count);
 /* KTX2 cube maps (renderer-core/src/cubemap/ktx.rs:39-147; the rules and their reasons are restated in host/ktx2.hpp).  Accepted vkFormats: 37, 43,
  * 44, 50 (RGBA8 / BGRA8, UNORM / SRGB), 97 (RGBA16F), 109 (RGBA32F), 122 (B10G11R11), 123 (E5B9G9R9); any other format — block-compressed and
  * depth formats among them — is AWSM_ERR_UNSUPPORTED with the vkFormat number in the message; every other rejection is AWSM_ERR_INVALID_ARGUMENT.
