@@ -19,6 +19,7 @@
 #include "dirty_log.hpp"
 #include "env_cube.hpp"
 #include "env_filter_table.hpp"
+#include "tex_pool.hpp"
 
 using namespace awsm;
 
@@ -56,6 +57,8 @@ void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, u
 void awsm_launch_env_mips(const awsm::EnvMipArgs* a, hipStream_t s);
 void awsm_launch_env_filter(const awsm::EnvFilterArgs* a, uint32_t blocks, hipStream_t s);
 void awsm_launch_env_filter_level0(const awsm::EnvFilterLevel0Args* a, hipStream_t s);
+void awsm_launch_tex_write(const awsm::TexWriteArgs* a, hipStream_t s);
+void awsm_launch_tex_mips(const awsm::TexMipArgs* a, hipStream_t s);
 }
 
 namespace {
@@ -139,6 +142,11 @@ struct AwsmHipCtx {
     // and the event a write waits on when it copied straight from the caller's memory
     DevBuf env_stage, env_tables, env_rows, env_filter_tab;      // env_filter_tab: the sample tables of awsm_hip_env_cube_filter
     hipEvent_t ev_env_copy = nullptr;
+    // the texture pool at run time (awsm_hip_texture_array_write_layers / _generate_mips_layers): MipmapTextureKind per layer of each array, on the
+    // device and written in stream order; the sRGB table, made once
+    DevBuf tex_kinds[kMaxTexArrays];
+    uint32_t tex_srgb[64] = {};
+    bool tex_srgb_made = false;
 
     // frame targets
     uint32_t width = 0, height = 0;
@@ -1125,6 +1133,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     auto fr = [](DevBuf& b) { if (b.ptr) (void)hipFree(b.ptr); b.ptr = nullptr; b.size = 0; };
     for (auto& b : c->bufs) fr(b);
     for (auto& b : c->tex) fr(b);
+    for (auto& b : c->tex_kinds) fr(b);
     for (auto& b : c->merged_vis) fr(b);
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
@@ -1332,6 +1341,181 @@ int awsm_hip_texture_array_read_level(AwsmHipCtx* c, uint32_t array_idx, uint32_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)t.layers * std::max(1u, t.width >> level) * std::max(1u, t.height >> level) * 4;
     HIPCHK(c, hipMemcpy(out, t.texels + (size_t)t.level_off[level] * 4, n, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+// ---- the texture pool at run time ----
+namespace {
+
+// first texel of each level of a w x h x layers array -> texels in all; false past 2^32 texels
+bool tex_level_offsets(uint32_t w, uint32_t h, uint32_t layers, uint32_t mips, uint32_t* level_off, size_t* total) {
+    size_t n = 0;
+    for (uint32_t l = 0; l < mips; l++) { level_off[l] = (uint32_t)n; n += (size_t)layers * std::max(1u, w >> l) * std::max(1u, h >> l); }
+    *total = n;
+    return n <= 0xFFFFFFFFull;
+}
+// The per-array kinds buffer holds a word per layer.  An array made by awsm_hip_texture_array_upload gets its buffer here, zero-filled, at the first
+// call that needs it: a fresh allocation, nothing to wait for.  (After an _upload with more layers than before the old buffer is replaced, which
+// waits like any reallocation; _create and _resize_layers size it themselves.)
+int tex_kinds_ready(AwsmHipCtx* c, uint32_t array_idx, uint32_t layers) {
+    DevBuf& k = c->tex_kinds[array_idx];
+    if (k.ptr && k.size >= (size_t)layers * 4) return AWSM_OK;
+    return dev_realloc(c, k, (size_t)layers * 4, true);
+}
+const TexArrayDev* tex_array(AwsmHipCtx* c, uint32_t array_idx, const char* where, int* rc) {
+    if (!c) { *rc = AWSM_ERR_INVALID_ARGUMENT; return nullptr; }
+    if (array_idx >= (uint32_t)kMaxTexArrays) { *rc = fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: array %u (0..%d)", where, array_idx, kMaxTexArrays - 1); return nullptr; }
+    const TexArrayDev* t = &c->scene.tex[array_idx];
+    if (!t->texels) { *rc = fail(c, AWSM_ERR_NOT_READY, "%s: array %u was never created or uploaded", where, array_idx); return nullptr; }
+    return t;
+}
+
+}  // namespace
+
+int awsm_hip_texture_array_create(AwsmHipCtx* c, uint32_t array_idx, uint32_t width, uint32_t height, uint32_t layers, uint32_t mips) {
+    if (!c || array_idx >= (uint32_t)kMaxTexArrays || width == 0 || height == 0 || layers == 0)
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "texture_array_create: bad argument");
+    if (layers > 65536u) return fail(c, AWSM_ERR_UNSUPPORTED, "texture_array_create: %u layers (the per-draw texture records hold a 16-bit layer)", layers);
+    const uint32_t full = mip_levels_full(width, height);
+    if (mips == 0) mips = 1;
+    if (mips > full || mips > (uint32_t)kMaxMipLevels) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "texture_array_create: %u mip levels, a %ux%u texture has at most %u", mips, width, height, full);
+    TexArrayDev t{};
+    size_t texels_total = 0;
+    if (!tex_level_offsets(width, height, layers, mips, t.level_off, &texels_total)) return fail(c, AWSM_ERR_UNSUPPORTED, "texture_array_create: array larger than 2^32 texels");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    int rc = dev_realloc(c, c->tex[array_idx], texels_total * 4 + 16, true);   // +16: as awsm_hip_texture_array_upload
+    if (rc) return rc;
+    if ((rc = dev_realloc(c, c->tex_kinds[array_idx], (size_t)layers * 4, true))) return rc;
+    t.texels = (const uint8_t*)c->tex[array_idx].ptr; t.width = width; t.height = height; t.layers = layers; t.mips = mips;
+    c->scene.tex[array_idx] = t;
+    c->scene.n_tex = std::max(c->scene.n_tex, array_idx + 1);
+    c->scene_dirty = true;
+    return AWSM_OK;
+}
+
+int awsm_hip_texture_array_resize_layers(AwsmHipCtx* c, uint32_t array_idx, uint32_t layers) {
+    int rc = AWSM_OK;
+    const TexArrayDev* tp = tex_array(c, array_idx, "texture_array_resize_layers", &rc);
+    if (!tp) return rc;
+    const TexArrayDev old = *tp;
+    if (layers < old.layers) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "texture_array_resize_layers: %u layers, the array holds %u (layers are never removed)", layers, old.layers);
+    if (layers > 65536u) return fail(c, AWSM_ERR_UNSUPPORTED, "texture_array_resize_layers: %u layers (the per-draw texture records hold a 16-bit layer)", layers);
+    if (layers == old.layers) return AWSM_OK;
+    TexArrayDev t = old;
+    size_t texels_total = 0;
+    if (!tex_level_offsets(old.width, old.height, layers, old.mips, t.level_off, &texels_total)) return fail(c, AWSM_ERR_UNSUPPORTED, "texture_array_resize_layers: array larger than 2^32 texels");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    // the new chain and the new kinds, filled on the device in stream order: each level's layers go to their new offset, the rest is zero
+    DevBuf chain{}, kinds{};
+    const size_t chain_bytes = texels_total * 4 + 16;
+    HIPCHK(c, hipMalloc(&chain.ptr, chain_bytes));
+    chain.size = chain_bytes;
+    hipError_t e = hipMalloc(&kinds.ptr, (size_t)layers * 4);
+    if (e != hipSuccess) { (void)hipFree(chain.ptr); return fail(c, e == hipErrorOutOfMemory ? AWSM_ERR_OUT_OF_MEMORY : AWSM_ERR_DEVICE, "texture_array_resize_layers: hipMalloc failed: %s", hipGetErrorString(e)); }
+    kinds.size = (size_t)layers * 4;
+    auto step = [&](hipError_t err) { if (e == hipSuccess) e = err; };
+    for (uint32_t l = 0; l < old.mips; l++) {
+        const size_t per_layer = (size_t)std::max(1u, old.width >> l) * std::max(1u, old.height >> l) * 4;
+        uint8_t* dst = (uint8_t*)chain.ptr + (size_t)t.level_off[l] * 4;
+        step(hipMemcpyAsync(dst, old.texels + (size_t)old.level_off[l] * 4, per_layer * old.layers, hipMemcpyDeviceToDevice, c->stream));
+        step(hipMemsetAsync(dst + per_layer * old.layers, 0, per_layer * (layers - old.layers), c->stream));
+    }
+    step(hipMemsetAsync((uint8_t*)chain.ptr + texels_total * 4, 0, 16, c->stream));
+    step(hipMemsetAsync(kinds.ptr, 0, kinds.size, c->stream));
+    if (c->tex_kinds[array_idx].ptr)
+        step(hipMemcpyAsync(kinds.ptr, c->tex_kinds[array_idx].ptr, std::min(c->tex_kinds[array_idx].size, (size_t)old.layers * 4), hipMemcpyDeviceToDevice, c->stream));
+    // as a reallocation in awsm_hip_texture_array_upload: nothing in flight may still read the old chain when it is freed
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = sync_shade_streams(c);
+    if (e != hipSuccess) {
+        (void)hipFree(chain.ptr); (void)hipFree(kinds.ptr);
+        return fail(c, AWSM_ERR_DEVICE, "texture_array_resize_layers: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(c->tex[array_idx].ptr);
+    if (c->tex_kinds[array_idx].ptr) (void)hipFree(c->tex_kinds[array_idx].ptr);
+    c->tex[array_idx] = chain;
+    c->tex_kinds[array_idx] = kinds;
+    t.texels = (const uint8_t*)chain.ptr; t.layers = layers;
+    c->scene.tex[array_idx] = t;
+    c->scene_dirty = true;      // k_resolve_draws forms the lean records again: their closed-form level offsets multiply by `layers`
+    return AWSM_OK;
+}
+
+int awsm_hip_texture_array_write_layers(AwsmHipCtx* c, uint32_t array_idx, uint32_t first_layer, uint32_t n_layers, const void* data, size_t data_len,
+                                        const AwsmTexWrite* write) {
+    int rc = AWSM_OK;
+    const TexArrayDev* tp = tex_array(c, array_idx, "texture_array_write_layers", &rc);
+    if (!tp) return rc;
+    const TexArrayDev t = *tp;
+    static_assert(sizeof(TexWriteDesc) == sizeof(AwsmTexWrite), "TexWriteDesc mirrors AwsmTexWrite");
+    size_t used = 0;
+    char why[128];
+    if ((rc = tex_write_validate(t.width, t.height, t.layers, first_layer, n_layers, data != nullptr, data_len, reinterpret_cast<const TexWriteDesc*>(write), &used, why, sizeof why)))
+        return fail(c, rc, "texture_array_write_layers: %s (array %u: %ux%u x %u layers; layers [%u, +%u), %zu bytes)", why, array_idx, t.width, t.height, t.layers, first_layer, n_layers, data_len);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = tex_kinds_ready(c, array_idx, t.layers))) return rc;
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    if (!c->tex_srgb_made) { tex_srgb_table(reinterpret_cast<uint8_t*>(c->tex_srgb)); c->tex_srgb_made = true; }
+    const uint8_t* src = (const uint8_t*)data + write->offset;
+    TexWriteArgs a{};
+    if (used <= (4u << 20)) {      // the kernel gathers from the pinned ring itself (device-visible at the same address): no device copy of the source
+        uint8_t* st;
+        if ((rc = stage_alloc(c, used, &st))) return rc;
+        memcpy(st, src, used);
+        a.src = st;
+    } else {
+        if ((rc = dev_reserve(c, c->env_stage, used))) return rc;      // grows (and then waits for the stream) only until it fits the largest source seen
+        if (!c->ev_env_copy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_env_copy, hipEventDisableTiming));
+        HIPCHK(c, hipMemcpyAsync(c->env_stage.ptr, src, used, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_env_copy, c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev_env_copy));      // the one wait: `data` may be pageable and is not retained
+        a.src = (const uint8_t*)c->env_stage.ptr;
+    }
+    a.dst = (uint32_t*)c->tex[array_idx].ptr + (size_t)first_layer * t.width * t.height;
+    a.width = t.width; a.height = t.height; a.n_layers = n_layers; a.flags = write->flags;
+    a.bytes_per_row = write->bytes_per_row; a.image_stride = (uint64_t)write->bytes_per_row * write->rows_per_image;
+    memcpy(a.srgb, c->tex_srgb, sizeof a.srgb);
+    awsm_launch_tex_write(&a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> kinds(n_layers, write->mipmap_kind);
+    return upload_small(c, (uint32_t*)c->tex_kinds[array_idx].ptr + first_layer, kinds.data(), kinds.size() * 4);
+}
+
+int awsm_hip_texture_array_generate_mips_layers(AwsmHipCtx* c, uint32_t array_idx, uint32_t first_layer, uint32_t n_layers) {
+    int rc = AWSM_OK;
+    const TexArrayDev* tp = tex_array(c, array_idx, "texture_array_generate_mips_layers", &rc);
+    if (!tp) return rc;
+    const TexArrayDev t = *tp;
+    if (n_layers == 0) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "texture_array_generate_mips_layers: n_layers must be non-zero");
+    if ((uint64_t)first_layer + n_layers > t.layers)
+        return fail(c, AWSM_ERR_OUT_OF_RANGE, "texture_array_generate_mips_layers: layers [%u, +%u) of an array of %u", first_layer, n_layers, t.layers);
+    if (t.mips < 2) return AWSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = tex_kinds_ready(c, array_idx, t.layers))) return rc;
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    for (uint32_t l = 1; l < t.mips; l += 5u) {      // five levels per launch, each launch from the stored level above its first
+        TexMipArgs a{};
+        a.chain = (uint32_t*)c->tex[array_idx].ptr; a.kinds = (const uint32_t*)c->tex_kinds[array_idx].ptr;
+        a.layers = t.layers; a.first_layer = first_layer; a.n_layers = n_layers;
+        a.src_off = t.level_off[l - 1]; a.sw = std::max(1u, t.width >> (l - 1)); a.sh = std::max(1u, t.height >> (l - 1));
+        a.n_levels = std::min(5u, t.mips - l);
+        for (uint32_t k = 0; k < a.n_levels; k++) a.dst_off[k] = t.level_off[l + k];
+        awsm_launch_tex_mips(&a, c->stream);
+    }
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+int awsm_hip_texture_array_info(AwsmHipCtx* c, uint32_t array_idx, uint32_t* width, uint32_t* height, uint32_t* layers, uint32_t* mips) {
+    int rc = AWSM_OK;
+    const TexArrayDev* t = tex_array(c, array_idx, "texture_array_info", &rc);
+    if (!t) return rc;
+    if (width) *width = t->width;
+    if (height) *height = t->height;
+    if (layers) *layers = t->layers;
+    if (mips) *mips = t->mips;
     return AWSM_OK;
 }
 

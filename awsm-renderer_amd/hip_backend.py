@@ -36,7 +36,9 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr",
            "awsm_hip_env_cube_create", "awsm_hip_env_cube_write_face", "awsm_hip_env_cube_write_all_faces", "awsm_hip_env_cube_generate_mips",
            "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level",
-           "awsm_hip_env_cube_filter"]
+           "awsm_hip_env_cube_filter",
+           "awsm_hip_texture_array_create", "awsm_hip_texture_array_resize_layers", "awsm_hip_texture_array_write_layers",
+           "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info"]
 
 
 class AwsmConfig(C.Structure):
@@ -63,6 +65,13 @@ class AwsmCubeLayout(C.Structure):
 class AwsmEnvFilter(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("size", C.c_uint32), ("mips", C.c_uint32), ("sample_count", C.c_uint32), ("reserved", C.c_uint32)]
 
+
+class AwsmTexWrite(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("mipmap_kind", C.c_uint32),
+                ("bytes_per_row", C.c_uint32), ("rows_per_image", C.c_uint32), ("offset", C.c_uint64)]
+
+
+AWSM_TEX_PREMULTIPLY_ALPHA, AWSM_TEX_SRGB_TO_LINEAR = 1, 2
 
 ENV_FILTER_KINDS = {"ggx": 0, "lambert": 1}
 
@@ -145,6 +154,11 @@ def load_library():
     lib.awsm_hip_pick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.awsm_hip_texture_array_generate_mips.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.awsm_hip_texture_array_read_level.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.awsm_hip_texture_array_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.awsm_hip_texture_array_resize_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.awsm_hip_texture_array_write_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.awsm_hip_texture_array_generate_mips_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.awsm_hip_texture_array_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.awsm_hip_texture_array_upload.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
     lib.awsm_hip_sampler_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.awsm_hip_env_upload.argtypes = [C.c_void_p, C.c_void_p]
@@ -282,8 +296,42 @@ class HipDevice:
         k = None if kinds is None else (C.c_uint32 * layers)(*[int(x) for x in kinds])
         self._chk(self.lib.awsm_hip_texture_array_generate_mips(self.ctx, index, k), "texture_array_generate_mips")
 
+    # ---- the texture pool at run time ----
+    def texture_array_create(self, index: int, width: int, height: int, layers: int, mips: int = 1):
+        """A zero-filled array; `mips` levels are reserved."""
+        self._chk(self.lib.awsm_hip_texture_array_create(self.ctx, index, width, height, layers, mips), "texture_array_create")
+
+    def texture_array_resize_layers(self, index: int, layers: int):
+        """More layers: the existing ones keep every level, the new ones read zero."""
+        self._chk(self.lib.awsm_hip_texture_array_resize_layers(self.ctx, index, layers), "texture_array_resize_layers")
+
+    def texture_array_write_layers(self, index: int, first_layer: int, data, n_layers: Optional[int] = None, flags: int = 0, mip_kind: int = 0,
+                                   bytes_per_row: Optional[int] = None, rows_per_image: Optional[int] = None, offset: int = 0, fmt: int = 0,
+                                   struct_size: Optional[int] = None):
+        """Level 0 of layers [first_layer, +n): an (n, h, w, 4) uint8 array, or raw bytes with a layout; flags = AWSM_TEX_*."""
+        w, h, _, _ = self.texture_array_info(index)
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            raw = np.frombuffer(data, dtype=np.uint8)
+        else:
+            if n_layers is None and getattr(data, "ndim", 0) == 4:
+                n_layers = data.shape[0]
+            raw = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        wr = AwsmTexWrite(C.sizeof(AwsmTexWrite) if struct_size is None else struct_size, fmt, flags, mip_kind, w * 4 if bytes_per_row is None else bytes_per_row,
+                          h if rows_per_image is None else rows_per_image, offset)
+        self._chk(self.lib.awsm_hip_texture_array_write_layers(self.ctx, index, first_layer, 1 if n_layers is None else n_layers,
+                                                               raw.ctypes.data_as(C.c_void_p) if raw.size else None, raw.nbytes, C.byref(wr)), "texture_array_write_layers")
+
+    def texture_array_generate_mips_layers(self, index: int, first_layer: int, n_layers: int):
+        self._chk(self.lib.awsm_hip_texture_array_generate_mips_layers(self.ctx, index, first_layer, n_layers), "texture_array_generate_mips_layers")
+
+    def texture_array_info(self, index: int):
+        """-> (width, height, layers, mips) of an array the device holds."""
+        v = [C.c_uint32(0) for _ in range(4)]
+        self._chk(self.lib.awsm_hip_texture_array_info(self.ctx, index, *[C.byref(x) for x in v]), "texture_array_info")
+        return tuple(int(x.value) for x in v)
+
     def texture_array_read_level(self, index: int, level: int) -> np.ndarray:
-        layers, h, w = self._tex_shapes[index]
+        w, h, layers, _ = self.texture_array_info(index)      # the device knows: the array may have been created, resized, or be a host's
         out = np.zeros((layers, max(1, h >> level), max(1, w >> level), 4), dtype=np.uint8)
         self._chk(self.lib.awsm_hip_texture_array_read_level(self.ctx, index, level, out.ctypes.data_as(C.c_void_p)), "texture_array_read_level")
         return out

@@ -47,6 +47,17 @@ class HostMaterial(C.Structure):
                 ("iridescence_thickness_max", C.c_float), ("iridescence_tex", TexRef), ("iridescence_thickness_tex", TexRef)]
 
 
+class HostTextureDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mipmap_kind", C.c_uint32), ("srgb_to_linear", C.c_uint32), ("premultiply_alpha", C.c_uint32)]
+
+
+class GltfOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("scene_index", C.c_int32), ("flags", C.c_uint32)]
+
+
+AWSM_GLTF_SRGB_COLOR_TEXTURES = 1
+
+
 class MorphTarget(C.Structure):
     _fields_ = [("positions", F32P), ("normals", F32P), ("tangents", F32P)]
 
@@ -116,6 +127,8 @@ def load_library():
         "awsm_host_decode_image": (C.c_int, [C.c_char_p, C.c_size_t, vp, C.c_size_t, U32P, U32P, C.c_char_p, C.c_size_t]),
         "awsm_host_draw_list": (C.c_int, [vp, vp, C.c_uint32, U32P]), "awsm_host_transparent_draw_list": (C.c_int, [vp, vp, C.c_uint32, U32P]), "awsm_host_texture_array_count": (C.c_uint32, [vp]),
         "awsm_host_texture_array_info": (C.c_int, [vp, C.c_uint32, U32P, U32P, U32P, C.POINTER(vp)]),
+        "awsm_host_texture_insert_ex": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp]), "awsm_host_texture_update": (C.c_int, [vp, C.c_int, vp]),
+        "awsm_host_load_gltf_ex": (C.c_int, [vp, C.c_char_p, vp, vp, C.c_char_p, C.c_size_t]),
         "awsm_host_upload_bytes_last_frame": (u64, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -219,12 +232,22 @@ class Host:
         return out.reshape(4, 4)
 
     # ---- textures / samplers ----
-    def texture_insert(self, image: np.ndarray, mip_kind: int = 0) -> int:
+    def texture_insert(self, image: np.ndarray, mip_kind: int = 0, srgb: bool = False, premultiply: bool = False) -> int:
+        """An (h, w, 4) uint8 image into the pool; srgb / premultiply: converted on the device as it enters (awsm_host_texture_insert_ex)."""
         img = np.ascontiguousarray(image, dtype=np.uint8)
-        r = self.lib.awsm_host_texture_insert_kind(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], mip_kind)
+        if srgb or premultiply:
+            desc = HostTextureDesc(C.sizeof(HostTextureDesc), mip_kind, 1 if srgb else 0, 1 if premultiply else 0)
+            r = self.lib.awsm_host_texture_insert_ex(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], C.byref(desc))
+        else:
+            r = self.lib.awsm_host_texture_insert_kind(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], mip_kind)
         if r < 0:
             self._chk(r, "texture_insert")
         return r
+
+    def texture_update(self, texture_id: int, image: np.ndarray):
+        """New pixels (same extent) for a texture of the pool; the next frame submitted sees them."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        self._chk(self.lib.awsm_host_texture_update(self.h, texture_id, img.ctypes.data_as(C.c_void_p)), "texture_update")
 
     def sampler_insert(self, s: dict) -> int:
         smp = AwsmSampler(s.get("address_mode_u", 1), s.get("address_mode_v", 1), s.get("mag_filter", 1), s.get("min_filter", 1),
@@ -501,11 +524,16 @@ class Host:
         self._chk(self.lib.awsm_host_mirror(self.h, which, C.byref(p), C.byref(n)), "mirror")
         return C.string_at(p, n.value)
 
-    def load_gltf(self, path: str, scene_index: int = -1) -> dict:
-        """Populate this host from a .gltf / .glb file (awsm_host_load_gltf); returns the counts of what was inserted."""
+    def load_gltf(self, path: str, scene_index: int = -1, srgb_textures: bool = False) -> dict:
+        """Populate this host from a .gltf / .glb file (awsm_host_load_gltf); returns the counts of what was inserted.  srgb_textures: colour
+        images (base colour, emissive, specular colour, sheen colour) are decoded from sRGB as they enter the pool (awsm_host_load_gltf_ex)."""
         info = (C.c_uint32 * 12)()
         err = C.create_string_buffer(512)
-        rc = self.lib.awsm_host_load_gltf(self.h, os.fsencode(path), scene_index, info, err, 512)
+        if srgb_textures:
+            opt = GltfOptions(C.sizeof(GltfOptions), scene_index, AWSM_GLTF_SRGB_COLOR_TEXTURES)
+            rc = self.lib.awsm_host_load_gltf_ex(self.h, os.fsencode(path), C.byref(opt), info, err, 512)
+        else:
+            rc = self.lib.awsm_host_load_gltf(self.h, os.fsencode(path), scene_index, info, err, 512)
         if rc != 0:
             raise HostError(f"load_gltf({path}) failed ({rc}): {err.value.decode(errors='replace')}")
         names = ("nodes", "meshes", "materials", "images", "samplers", "skins", "lights", "triangles", "generated_tangents")
@@ -527,6 +555,15 @@ class Host:
             if d.inst_count:
                 e["inst_off"], e["inst_count"] = d.inst_off, d.inst_count
             out.append(e)
+        return out
+
+    def pool_arrays(self) -> List[np.ndarray]:
+        """The pool's content, one (layers, h, w, 4) uint8 array per pool array (awsm_host_texture_array_info: the host's mirror)."""
+        out = []
+        for i in range(self.lib.awsm_host_texture_array_count(self.h)):
+            w, h, n, p = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_void_p()
+            self._chk(self.lib.awsm_host_texture_array_info(self.h, i, C.byref(w), C.byref(h), C.byref(n), C.byref(p)), "texture_array_info")
+            out.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n.value, h.value, w.value, 4)).copy())
         return out
 
     def upload_bytes_last_frame(self) -> int:
@@ -638,11 +675,12 @@ class Populated:
         self.light_keys: List[int] = []
 
 
-def populate(host: Host, scene: SceneDesc) -> Populated:
+def populate(host: Host, scene: SceneDesc, srgb_textures=()) -> Populated:
+    """srgb_textures: indices of scene.textures whose bytes are sRGB-encoded (decoded on the device as they enter the pool)."""
     out = Populated()
     kinds = texture_mip_kinds(scene)
-    for tex, kind in zip(scene.textures, kinds):
-        host.texture_insert(tex, kind)
+    for i, (tex, kind) in enumerate(zip(scene.textures, kinds)):
+        host.texture_insert(tex, kind, srgb=i in srgb_textures)
     for s in scene.samplers:
         host.sampler_insert(s)
     host.set_ibl_mip_counts(scene.prefiltered_mip_count, scene.irradiance_mip_count)
@@ -693,19 +731,20 @@ class Renderer:
 
     def __init__(self, scene: SceneDesc, backend_path: Optional[str] = None, device: int = 0, stream: Optional[int] = None, parity_tap: bool = False,
                  lut_rgba16f: Optional[np.ndarray] = None, lut_size: int = 1024, msaa: int = 0, mipmap: bool = False, overlap_frames: bool = False,
-                 gltf: Optional[str] = None, anisotropic: bool = False):
+                 gltf: Optional[str] = None, anisotropic: bool = False, srgb_textures=None):
         """gltf: path of a .gltf / .glb file to populate from (AwsmRenderer::populate_gltf); `scene` then only supplies the frame size,
-        the camera and the environment."""
+        the camera and the environment.  srgb_textures: with gltf, True decodes the colour images from sRGB (Host.load_gltf); without, the
+        indices of scene.textures that hold sRGB-encoded bytes."""
         self.scene = scene
         self.host = Host(backend_path, device, stream, parity_tap, overlap_frames, anisotropic)      # anisotropic: AWSM_CFG_ANISOTROPIC (include/awsm_hip.h)
         self.host.set_anti_aliasing(msaa, mipmap)   # AwsmRendererBuilder::with_anti_aliasing (off unless asked: BASELINE configs are single-sampled, MipmapMode::None)
         self.host.resize(scene.width, scene.height)
         if gltf is not None:
             self.host.set_ibl_mip_counts(scene.prefiltered_mip_count, scene.irradiance_mip_count)
-            self.gltf_info = self.host.load_gltf(gltf)
+            self.gltf_info = self.host.load_gltf(gltf, srgb_textures=bool(srgb_textures))
             self.keys = None
         else:
-            self.keys = populate(self.host, scene)
+            self.keys = populate(self.host, scene, tuple(srgb_textures or ()))
         if lut_rgba16f is not None:
             self.host.env(scene.skybox_rgba, scene.prefiltered_rgb, scene.irradiance_rgb, lut_rgba16f)
         else:

@@ -45,6 +45,12 @@ struct Loader {
     Value doc;
     std::vector<std::vector<uint8_t>> buffers;
     std::vector<int> image_tex;                       // glTF image -> host texture id
+    // AWSM_GLTF_SRGB_COLOR_TEXTURES: images are kept decoded and enter the pool when a material first uses them, once per
+    // (texture index, mipmap kind, srgb_to_linear) — create_material_cache_key (material.rs:812-857)
+    bool srgb_color_textures = false;
+    struct Decoded { std::vector<uint8_t> rgba; uint32_t w = 0, h = 0; };
+    std::vector<Decoded> decoded;
+    std::map<std::vector<int64_t>, int> tex_cache;
     std::map<std::vector<uint32_t>, uint32_t> sampler_ids;   // AwsmSampler fields -> host sampler id
     std::vector<AwsmKey> node_keys;
     std::map<int, AwsmKey> material_keys;             // glTF material (-1 = default) -> key
@@ -314,6 +320,7 @@ bool load_images(Loader& L) {
     std::vector<int> kinds(images.size(), -1);
     assign_image_kinds(L, kinds);
     L.image_tex.assign(images.size(), -1);
+    L.decoded.assign(L.srgb_color_textures ? images.size() : 0, Loader::Decoded{});
     for (size_t i = 0; i < images.size(); i++) {
         std::vector<uint8_t> bytes, rgba;
         if (!image_bytes(L, images[i], bytes)) return false;
@@ -322,10 +329,11 @@ bool load_images(Loader& L) {
         if (awsm_png::is_png(bytes.data(), bytes.size())) { if (!awsm_png::decode(bytes.data(), bytes.size(), rgba, w, ht, perr)) return L.fail("image %zu: %s", i, perr.c_str()); }
         else if (awsm_jpeg::is_jpeg(bytes.data(), bytes.size())) { if (!awsm_jpeg::decode(bytes.data(), bytes.size(), rgba, w, ht, perr)) return L.fail("image %zu: %s", i, perr.c_str()); }
         else return L.fail("image %zu: this image format is not supported (PNG and baseline JPEG only)", i);
+        L.info.images++;
+        if (L.srgb_color_textures) { L.decoded[i].rgba = std::move(rgba); L.decoded[i].w = w; L.decoded[i].h = ht; continue; }
         const int id = awsm_host_texture_insert_kind(L.h, rgba.data(), w, ht, (uint32_t)(kinds[i] < 0 ? 0 : kinds[i]));
         if (id < 0) return L.fail("image %zu: %s", i, awsm_host_last_error(L.h));
         L.image_tex[i] = id;
-        L.info.images++;
     }
     return true;
 }
@@ -374,7 +382,8 @@ bool load_samplers(Loader& L) {
     return true;
 }
 
-bool tex_ref(Loader& L, const Value& info, AwsmHostTexRef& r) {
+// kind / srgb: the TextureColorInfo of the role (material.rs:128-640); they matter with AWSM_GLTF_SRGB_COLOR_TEXTURES only
+bool tex_ref(Loader& L, const Value& info, AwsmHostTexRef& r, uint32_t kind = 0, bool srgb = false) {
     r.texture = -1; r.sampler = 0; r.uv_index = 0; r.pad = 0; r.transform = 0;
     if (!info.is_object()) return true;
     const int64_t ti = info["index"].integer(-1);
@@ -382,7 +391,18 @@ bool tex_ref(Loader& L, const Value& info, AwsmHostTexRef& r) {
     if (ti < 0 || !tex.is_object()) return true;                         // dangling reference: SkipTexture (materials/writer.rs:100-112)
     const int64_t src = tex["source"].integer(-1);
     if (src < 0 || (size_t)src >= L.image_tex.size()) return true;
-    r.texture = L.image_tex[(size_t)src];
+    if (L.srgb_color_textures) {
+        const std::vector<int64_t> key = {ti, (int64_t)kind, srgb ? 1 : 0};
+        auto it = L.tex_cache.find(key);
+        if (it == L.tex_cache.end()) {
+            const Loader::Decoded& d = L.decoded[(size_t)src];
+            const AwsmHostTextureDesc desc = {(uint32_t)sizeof(AwsmHostTextureDesc), kind, srgb ? 1u : 0u, 0u};      // premultiplied_alpha: Some(false)
+            const int id = awsm_host_texture_insert_ex(L.h, d.rgba.data(), d.w, d.h, &desc);
+            if (id < 0) return L.fail("texture %lld: %s", (long long)ti, awsm_host_last_error(L.h));
+            it = L.tex_cache.emplace(key, id).first;
+        }
+        r.texture = it->second;
+    } else r.texture = L.image_tex[(size_t)src];
     if (!sampler_for_texture(L, tex, &r.sampler)) return false;
     r.uv_index = (uint32_t)info["texCoord"].integer(0);
     const Value& xf = info["extensions"]["KHR_texture_transform"];
@@ -429,8 +449,8 @@ bool material_key(Loader& L, int index, AwsmKey* out) {
     const std::string& am = m["alphaMode"].string();
     hm.alpha_mode = am == "MASK" ? 1u : (am == "BLEND" ? 2u : 0u);
     hm.alpha_cutoff = (float)m["alphaCutoff"].number(0.5);
-    if (!tex_ref(L, pbr["baseColorTexture"], hm.base_color_tex) || !tex_ref(L, pbr["metallicRoughnessTexture"], hm.metallic_roughness_tex) ||
-        !tex_ref(L, m["normalTexture"], hm.normal_tex) || !tex_ref(L, m["occlusionTexture"], hm.occlusion_tex) || !tex_ref(L, m["emissiveTexture"], hm.emissive_tex)) return false;
+    if (!tex_ref(L, pbr["baseColorTexture"], hm.base_color_tex, 0, true) || !tex_ref(L, pbr["metallicRoughnessTexture"], hm.metallic_roughness_tex, 2) ||
+        !tex_ref(L, m["normalTexture"], hm.normal_tex, 1) || !tex_ref(L, m["occlusionTexture"], hm.occlusion_tex, 3) || !tex_ref(L, m["emissiveTexture"], hm.emissive_tex, 4, true)) return false;
     if (m["extras"].has("vertex_color_set")) { hm.has_vertex_color = 1; hm.vertex_color_set = (uint32_t)m["extras"]["vertex_color_set"].integer(0); }
     if (ext.has("KHR_materials_emissive_strength")) { hm.has_emissive_strength = 1; hm.emissive_strength = (float)ext["KHR_materials_emissive_strength"]["emissiveStrength"].number(1.0); }
     if (ext.has("KHR_materials_ior")) { hm.has_ior = 1; hm.ior = (float)ext["KHR_materials_ior"]["ior"].number(1.5); }
@@ -438,33 +458,33 @@ bool material_key(Loader& L, int index, AwsmKey* out) {
         const Value& e = ext["KHR_materials_specular"];
         hm.has_specular = 1; hm.specular_factor = (float)e["specularFactor"].number(1.0);
         vec_n(e["specularColorFactor"], hm.specular_color_factor, 3, one3);
-        if (!tex_ref(L, e["specularTexture"], hm.specular_tex) || !tex_ref(L, e["specularColorTexture"], hm.specular_color_tex)) return false;
+        if (!tex_ref(L, e["specularTexture"], hm.specular_tex, 5) || !tex_ref(L, e["specularColorTexture"], hm.specular_color_tex, 5, true)) return false;
     }
     if (ext.has("KHR_materials_transmission")) {
         const Value& e = ext["KHR_materials_transmission"];
         hm.has_transmission = 1; hm.transmission_factor = (float)e["transmissionFactor"].number(0.0);
-        if (!tex_ref(L, e["transmissionTexture"], hm.transmission_tex)) return false;
+        if (!tex_ref(L, e["transmissionTexture"], hm.transmission_tex, 7)) return false;
     }
     if (ext.has("KHR_materials_volume")) {
         const Value& e = ext["KHR_materials_volume"];
         hm.has_volume = 1; hm.volume_thickness_factor = (float)e["thicknessFactor"].number(0.0);
         hm.volume_attenuation_distance = (float)e["attenuationDistance"].number(0.0);     // glTF's default is +inf; the reference stores 0 for "none"
         vec_n(e["attenuationColor"], hm.volume_attenuation_color, 3, one3);
-        if (!tex_ref(L, e["thicknessTexture"], hm.volume_thickness_tex)) return false;
+        if (!tex_ref(L, e["thicknessTexture"], hm.volume_thickness_tex, 8)) return false;
     }
     if (ext.has("KHR_materials_clearcoat")) {
         const Value& e = ext["KHR_materials_clearcoat"];
         hm.has_clearcoat = 1; hm.clearcoat_factor = (float)e["clearcoatFactor"].number(0.0);
         hm.clearcoat_roughness_factor = (float)e["clearcoatRoughnessFactor"].number(0.0);
         hm.clearcoat_normal_scale = (float)e["clearcoatNormalTexture"]["scale"].number(e["extras"]["normal_scale"].number(1.0));
-        if (!tex_ref(L, e["clearcoatTexture"], hm.clearcoat_tex) || !tex_ref(L, e["clearcoatRoughnessTexture"], hm.clearcoat_roughness_tex) ||
-            !tex_ref(L, e["clearcoatNormalTexture"], hm.clearcoat_normal_tex)) return false;
+        if (!tex_ref(L, e["clearcoatTexture"], hm.clearcoat_tex, 0) || !tex_ref(L, e["clearcoatRoughnessTexture"], hm.clearcoat_roughness_tex, 2) ||
+            !tex_ref(L, e["clearcoatNormalTexture"], hm.clearcoat_normal_tex, 1)) return false;
     }
     if (ext.has("KHR_materials_sheen")) {
         const Value& e = ext["KHR_materials_sheen"];
         hm.has_sheen = 1; hm.sheen_roughness_factor = (float)e["sheenRoughnessFactor"].number(0.0);
         vec_n(e["sheenColorFactor"], hm.sheen_color_factor, 3, zero3);
-        if (!tex_ref(L, e["sheenRoughnessTexture"], hm.sheen_roughness_tex) || !tex_ref(L, e["sheenColorTexture"], hm.sheen_color_tex)) return false;
+        if (!tex_ref(L, e["sheenRoughnessTexture"], hm.sheen_roughness_tex, 2) || !tex_ref(L, e["sheenColorTexture"], hm.sheen_color_tex, 5, true)) return false;
     }
     const AwsmKey k = awsm_host_material_insert(L.h, &hm);
     if (!k) return L.fail("material %d: %s", index, awsm_host_last_error(L.h));
@@ -868,10 +888,16 @@ extern "C" int awsm_host_decode_image(const uint8_t* data, size_t len, uint8_t* 
 }
 
 extern "C" int awsm_host_load_gltf(AwsmHost* h, const char* path, int scene_index, AwsmGltfInfo* info_out, char* err_out, size_t err_cap) {
-    if (!h || !path) return AWSM_ERR_INVALID_ARGUMENT;
+    const AwsmGltfOptions options = {(uint32_t)sizeof(AwsmGltfOptions), scene_index, 0u};      // images are taken as stored
+    return awsm_host_load_gltf_ex(h, path, &options, info_out, err_out, err_cap);
+}
+
+extern "C" int awsm_host_load_gltf_ex(AwsmHost* h, const char* path, const AwsmGltfOptions* options, AwsmGltfInfo* info_out, char* err_out, size_t err_cap) {
+    if (!h || !path || !options || options->struct_size != sizeof(AwsmGltfOptions) || (options->flags & ~(uint32_t)AWSM_GLTF_SRGB_COLOR_TEXTURES)) return AWSM_ERR_INVALID_ARGUMENT;
     Loader L;
     L.h = h;
-    const bool ok = load(L, path, scene_index);
+    L.srgb_color_textures = (options->flags & AWSM_GLTF_SRGB_COLOR_TEXTURES) != 0u;
+    const bool ok = load(L, path, options->scene_index);
     if (info_out) *info_out = L.info;
     if (!ok) {
         if (err_out && err_cap) { snprintf(err_out, err_cap, "%s", L.err.c_str()); }

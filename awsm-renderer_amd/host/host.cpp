@@ -33,6 +33,7 @@
 #include "buffers.hpp"
 #include "glam.hpp"
 #include "ktx2.hpp"
+#include "../csrc/tex_pool.hpp"      // the sRGB table and the integer premultiply, shared with the device library
 
 using namespace awsm_host;
 
@@ -72,6 +73,18 @@ struct Backend {
     int (*env_cube_fill_colors)(AwsmHipCtx*, AwsmCube, uint32_t, const float*) = nullptr;
     int (*env_cube_fill_sky_gradient)(AwsmHipCtx*, AwsmCube, uint32_t, const float*, const float*) = nullptr;
     int (*env_cube_filter)(AwsmHipCtx*, AwsmCube, AwsmCube, const AwsmEnvFilter*) = nullptr;      // optional (awsm_host_env_bake_ibl)
+    // optional: the texture pool at run time (awsm_host_texture_insert_ex / _update; finalize of a resident array)
+    int (*texture_array_create)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) = nullptr;
+    int (*texture_array_resize_layers)(AwsmHipCtx*, uint32_t, uint32_t) = nullptr;
+    int (*texture_array_write_layers)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t, const void*, size_t, const AwsmTexWrite*) = nullptr;
+    int (*texture_array_generate_mips_layers)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t) = nullptr;
+    int (*texture_array_info)(AwsmHipCtx*, uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*) = nullptr;
+    // the name of the first of them the library lacks, or null
+    const char* texture_pool_missing() const {
+        return !texture_array_create ? "awsm_hip_texture_array_create" : !texture_array_resize_layers ? "awsm_hip_texture_array_resize_layers"
+             : !texture_array_write_layers ? "awsm_hip_texture_array_write_layers" : !texture_array_generate_mips_layers ? "awsm_hip_texture_array_generate_mips_layers"
+             : !texture_array_info ? "awsm_hip_texture_array_info" : nullptr;
+    }
 };
 
 struct Transform { Vec3 t; Quat r; Vec3 s; };
@@ -149,7 +162,15 @@ struct AwsmHost {
     DynamicUniformBuffer normals_buf{32, 36};
 
     // ---- textures.rs ----
-    struct PoolArray { uint32_t w, h; std::vector<uint8_t> texels; uint32_t layers = 0; bool dirty = true; std::vector<uint32_t> kinds; };   // kinds: MipmapTextureKind per layer
+    struct PoolArray {
+        uint32_t w, h; std::vector<uint8_t> texels; uint32_t layers = 0; bool dirty = true; std::vector<uint32_t> kinds;   // kinds: MipmapTextureKind per layer
+        // Run-time pool.  flags: AWSM_TEX_* per layer, still to be applied to the layer's bytes in `texels` — by the device when the layer
+        // is written there, by the host when the mirror is asked for, whichever comes first; 0 once the bytes are the pool's content.
+        std::vector<uint32_t> flags, desc_flags;      // desc_flags: what the layer was inserted with (awsm_host_texture_update applies it again)
+        uint32_t dev_layers = 0;                      // layers the device's array has room for (0: not on the device)
+        uint32_t sent_layers = 0;                     // layers [0, sent_layers) are there
+        std::vector<uint32_t> resend;                 // layers below sent_layers whose pixels were replaced
+    };
     std::vector<PoolArray> pool;
     std::vector<std::pair<uint32_t, uint32_t>> tex_entries;   // texture id -> (array, layer)
     std::vector<AwsmSampler> samplers;
@@ -488,6 +509,59 @@ void collect_draws(AwsmHost* h, std::vector<AwsmDraw>& out_opaque, std::vector<A
     }
 }
 
+// One pool array whose host side changed (finalize_gpu_textures).  An array that is not on the device and whose layers need no conversion goes up
+// whole, as it always did.  Otherwise the device does the work: the array grows there by doubling, and only the new or replaced
+// images cross the bus and get their mip chains made.
+int finalize_pool_array(AwsmHost* h, uint32_t i, uint32_t levels) {
+    AwsmHost::PoolArray& a = h->pool[i];
+    int rc;
+    bool flagged = false;
+    for (uint32_t f : a.flags) flagged = flagged || f != 0u;
+    const bool run_time = !h->be.texture_pool_missing();
+    if ((a.dev_layers == 0 && !flagged) || !run_time) {
+        if (flagged || !a.resend.empty()) return fail(h, AWSM_ERR_UNSUPPORTED, "the backend library has no %s", h->be.texture_pool_missing());      // refused at insert / update already
+        if ((rc = h->be.texture_array_upload(h->ctx, i, a.w, a.h, a.layers, levels, AWSM_TEX_RGBA8_UNORM, a.texels.data()))) return dev_fail(h, rc, "texture_array_upload");
+        if ((rc = h->be.texture_array_generate_mips(h->ctx, i, a.kinds.data()))) return dev_fail(h, rc, "texture_array_generate_mips");
+        a.dev_layers = a.sent_layers = a.layers;
+        return AWSM_OK;
+    }
+    if (a.dev_layers == 0) {
+        if ((rc = h->be.texture_array_create(h->ctx, i, a.w, a.h, a.layers, levels))) return dev_fail(h, rc, "texture_array_create");
+        a.dev_layers = a.layers;
+    } else if (a.layers > a.dev_layers) {
+        // doubling; the lean gradient route wants fewer than 4096 layers, so the step stops at 4095 until the images themselves pass it
+        uint64_t want = std::max<uint64_t>((uint64_t)a.dev_layers * 2u, a.layers);
+        if (want > 4095u) want = std::max<uint64_t>(a.layers, std::min<uint64_t>(4095u, want));
+        if ((rc = h->be.texture_array_resize_layers(h->ctx, i, (uint32_t)want))) return dev_fail(h, rc, "texture_array_resize_layers");
+        a.dev_layers = (uint32_t)want;
+    }
+    const size_t bytes = (size_t)a.w * a.h * 4;
+    auto send = [&](uint32_t first, uint32_t n) -> int {      // layers with one kind and one set of flags
+        AwsmTexWrite w{};
+        w.struct_size = sizeof w; w.format = 0u; w.flags = a.flags[first]; w.mipmap_kind = a.kinds[first];
+        w.bytes_per_row = a.w * 4u; w.rows_per_image = a.h; w.offset = 0;
+        int r = h->be.texture_array_write_layers(h->ctx, i, first, n, a.texels.data() + (size_t)first * bytes, (size_t)n * bytes, &w);
+        if (r) return dev_fail(h, r, "texture_array_write_layers");
+        h->upload_bytes += (uint64_t)n * bytes;
+        return AWSM_OK;
+    };
+    std::sort(a.resend.begin(), a.resend.end());
+    for (uint32_t l : a.resend) {
+        if ((rc = send(l, 1u))) return rc;
+        if ((rc = h->be.texture_array_generate_mips_layers(h->ctx, i, l, 1u))) return dev_fail(h, rc, "texture_array_generate_mips_layers");
+    }
+    a.resend.clear();
+    for (uint32_t l = a.sent_layers; l < a.layers;) {
+        uint32_t n = 1;
+        while (l + n < a.layers && a.flags[l + n] == a.flags[l] && a.kinds[l + n] == a.kinds[l]) n++;
+        if ((rc = send(l, n))) return rc;
+        l += n;
+    }
+    if (a.layers > a.sent_layers && (rc = h->be.texture_array_generate_mips_layers(h->ctx, i, a.sent_layers, a.layers - a.sent_layers))) return dev_fail(h, rc, "texture_array_generate_mips_layers");
+    a.sent_layers = a.layers;
+    return AWSM_OK;
+}
+
 template <typename T>
 bool load_sym(AwsmHost* h, T& fn, const char* name) {
     fn = reinterpret_cast<T>(dlsym(h->be.dl, name));
@@ -524,6 +598,11 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.env_cube_fill_colors = reinterpret_cast<decltype(b.env_cube_fill_colors)>(dlsym(b.dl, "awsm_hip_env_cube_fill_colors"));
     b.env_cube_fill_sky_gradient = reinterpret_cast<decltype(b.env_cube_fill_sky_gradient)>(dlsym(b.dl, "awsm_hip_env_cube_fill_sky_gradient"));
     b.env_cube_filter = reinterpret_cast<decltype(b.env_cube_filter)>(dlsym(b.dl, "awsm_hip_env_cube_filter"));
+    b.texture_array_create = reinterpret_cast<decltype(b.texture_array_create)>(dlsym(b.dl, "awsm_hip_texture_array_create"));      // optional (the texture pool at run time)
+    b.texture_array_resize_layers = reinterpret_cast<decltype(b.texture_array_resize_layers)>(dlsym(b.dl, "awsm_hip_texture_array_resize_layers"));
+    b.texture_array_write_layers = reinterpret_cast<decltype(b.texture_array_write_layers)>(dlsym(b.dl, "awsm_hip_texture_array_write_layers"));
+    b.texture_array_generate_mips_layers = reinterpret_cast<decltype(b.texture_array_generate_mips_layers)>(dlsym(b.dl, "awsm_hip_texture_array_generate_mips_layers"));
+    b.texture_array_info = reinterpret_cast<decltype(b.texture_array_info)>(dlsym(b.dl, "awsm_hip_texture_array_info"));
     if (b.abi_version() != AWSM_HIP_ABI_VERSION) { dlclose(b.dl); return AWSM_ERR_INVALID_ARGUMENT; }
     AwsmConfig cfg{};
     cfg.struct_size = sizeof cfg; cfg.abi_version = AWSM_HIP_ABI_VERSION; cfg.device = device; cfg.flags = cfg_flags; cfg.stream = stream;
@@ -622,15 +701,44 @@ int awsm_host_texture_insert_kind(AwsmHost* h, const uint8_t* rgba8, uint32_t w,
     for (; ai < h->pool.size(); ai++) if (h->pool[ai].w == w && h->pool[ai].h == ht) break;
     if (ai == h->pool.size()) {
         if (h->pool.size() >= 64) return fail(h, AWSM_ERR_UNSUPPORTED, "more than 64 pool arrays");
-        h->pool.push_back({w, ht, {}, 0, true, {}});
+        AwsmHost::PoolArray fresh; fresh.w = w; fresh.h = ht;
+        h->pool.push_back(std::move(fresh));
     }
     AwsmHost::PoolArray& a = h->pool[ai];
     a.texels.insert(a.texels.end(), rgba8, rgba8 + (size_t)w * ht * 4);
     a.kinds.push_back(mipmap_kind);
+    a.flags.push_back(0u); a.desc_flags.push_back(0u);
     a.dirty = true;
     h->tex_entries.push_back({ai, a.layers});
     a.layers++;
     return (int)h->tex_entries.size() - 1;
+}
+
+int awsm_host_texture_insert_ex(AwsmHost* h, const uint8_t* rgba8, uint32_t w, uint32_t ht, const AwsmHostTextureDesc* desc) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(AwsmHostTextureDesc)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "texture_insert_ex: a desc with struct_size %zu is missing", sizeof(AwsmHostTextureDesc));
+    const uint32_t flags = (desc->premultiply_alpha ? (uint32_t)AWSM_TEX_PREMULTIPLY_ALPHA : 0u) | (desc->srgb_to_linear ? (uint32_t)AWSM_TEX_SRGB_TO_LINEAR : 0u);
+    if (flags && h->be.texture_pool_missing())
+        return fail(h, AWSM_ERR_UNSUPPORTED, "texture_insert_ex: srgb_to_linear / premultiply_alpha need %s, which the backend library lacks", h->be.texture_pool_missing());
+    const int id = awsm_host_texture_insert_kind(h, rgba8, w, ht, desc->mipmap_kind);
+    if (id < 0) return id;
+    AwsmHost::PoolArray& a = h->pool[h->tex_entries[(size_t)id].first];
+    a.flags.back() = flags; a.desc_flags.back() = flags;
+    return id;
+}
+
+int awsm_host_texture_update(AwsmHost* h, int texture_id, const uint8_t* rgba8) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!rgba8 || texture_id < 0 || (size_t)texture_id >= h->tex_entries.size()) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "texture_update: no pixels, or no texture %d", texture_id);
+    if (h->be.texture_pool_missing()) return fail(h, AWSM_ERR_UNSUPPORTED, "texture_update: the backend library has no %s", h->be.texture_pool_missing());
+    const auto [ai, li] = h->tex_entries[(size_t)texture_id];
+    AwsmHost::PoolArray& a = h->pool[ai];
+    const size_t bytes = (size_t)a.w * a.h * 4;
+    memcpy(a.texels.data() + (size_t)li * bytes, rgba8, bytes);
+    a.flags[li] = a.desc_flags[li];
+    if (li < a.sent_layers && std::find(a.resend.begin(), a.resend.end(), li) == a.resend.end()) a.resend.push_back(li);
+    a.dirty = true;
+    return AWSM_OK;
 }
 
 int awsm_host_sampler_insert(AwsmHost* h, const AwsmSampler* s) {
@@ -1181,8 +1289,7 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
         // TexturePoolArray::new: mipmap = true for every array -> full chain (texture_pool.rs:166-176,187-192,317-319)
         uint32_t levels = 1;
         for (uint32_t m = std::max(a.w, a.h); m > 1u; m >>= 1) levels++;
-        if ((rc = h->be.texture_array_upload(h->ctx, i, a.w, a.h, a.layers, levels, AWSM_TEX_RGBA8_UNORM, a.texels.data()))) return dev_fail(h, rc, "texture_array_upload");
-        if ((rc = h->be.texture_array_generate_mips(h->ctx, i, a.kinds.data()))) return dev_fail(h, rc, "texture_array_generate_mips");
+        if ((rc = finalize_pool_array(h, i, levels))) return rc;
         a.dirty = false;
     }
     // ---- collect_renderables -> geometry pass -> opaque pass (render.rs:144-221) ----
@@ -1295,6 +1402,24 @@ int awsm_host_draw_list(AwsmHost* h, AwsmDraw* out, uint32_t cap, uint32_t* n) {
 uint32_t awsm_host_texture_array_count(AwsmHost* h) { return (uint32_t)h->pool.size(); }
 int awsm_host_texture_array_info(AwsmHost* h, uint32_t i, uint32_t* w, uint32_t* ht, uint32_t* layers, const uint8_t** texels) {
     if (i >= h->pool.size()) return AWSM_ERR_OUT_OF_RANGE;
+    {   // layers whose conversion is still owed get it now, by the device's table and integer rule (tex_pool.hpp)
+        AwsmHost::PoolArray& a = h->pool[i];
+        uint8_t table[256];
+        awsm::tex_srgb_table(table);
+        const size_t texels = (size_t)a.w * a.h;
+        for (uint32_t l = 0; l < a.layers; l++) {
+            const uint32_t f = a.flags[l];
+            if (!f) continue;
+            uint8_t* p = a.texels.data() + (size_t)l * texels * 4;
+            for (size_t t = 0; t < texels; t++, p += 4) {
+                uint32_t v; memcpy(&v, p, 4);
+                if (f & awsm::kTexPremultiplyAlpha) v = awsm::tex_premultiply(v);
+                memcpy(p, &v, 4);
+                if (f & awsm::kTexSrgbToLinear) { p[0] = table[p[0]]; p[1] = table[p[1]]; p[2] = table[p[2]]; }
+            }
+            a.flags[l] = 0u;
+        }
+    }
     *w = h->pool[i].w; *ht = h->pool[i].h; *layers = h->pool[i].layers; *texels = h->pool[i].texels.data();
     return AWSM_OK;
 }

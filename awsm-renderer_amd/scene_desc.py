@@ -100,7 +100,7 @@ class SkinDesc:
 class SceneDesc:
     nodes: List[NodeDesc]
     materials: List[MaterialDesc]
-    textures: List[np.ndarray] = field(default_factory=list)   # (h,w,4) u8, already linear-converted where sRGB
+    textures: List[np.ndarray] = field(default_factory=list)   # (h,w,4) u8, taken as stored (linear) unless inserted as sRGB: Renderer(srgb_textures=...), Host.texture_insert(srgb=True)
     samplers: List[dict] = field(default_factory=list)         # AwsmSampler fields
     skins: List[SkinDesc] = field(default_factory=list)
     lights: List[dict] = field(default_factory=list)           # {kind, color, intensity, direction/position/...}

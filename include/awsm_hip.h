@@ -492,6 +492,41 @@ typedef struct AwsmEnvFilter {
 } AwsmEnvFilter;
 int awsm_hip_env_cube_filter(AwsmHipCtx* ctx, AwsmCube src, AwsmCube dst, const AwsmEnvFilter* filter);
 
+/* ---- the texture pool at run time (renderer-core/src/texture/texture_pool.rs:233-303, texture/convert_srgb.rs, texture/mipmap.rs).
+ * Storage is what awsm_hip_texture_array_upload makes — RGBA8 UNORM, [level][layer][y][x] — and these entries fill and change it in place.
+ *   create               a zero-filled array of `layers` images and `mips` levels (0 = 1); may reallocate and synchronise, as _upload does.
+ *   resize_layers        more layers: every level of every existing layer is kept (moved on the device to its new offset), new layers read zero;
+ *                        reallocates and synchronises as _upload does.  Fewer layers than the array has: AWSM_ERR_INVALID_ARGUMENT.
+ *   write_layers         `n_layers` images of the array's extent into level 0 of layers [first_layer, first_layer + n_layers), read from
+ *                        data[offset + layer * rows_per_image * bytes_per_row + row * bytes_per_row ...] (any offset; rows_per_image is read only
+ *                        when n_layers > 1).  A texel is premultiplied (AWSM_TEX_PREMULTIPLY_ALPHA: c' = (2 c a + 255) / 510 on the encoded bytes)
+ *                        and then decoded (AWSM_TEX_SRGB_TO_LINEAR: the 256-entry table of DESIGN.md §14); alpha is kept.  mipmap_kind is recorded
+ *                        for those layers (layers never written this way have kind 0).  WebGPU's writeTexture rules are checked in 64 bits before
+ *                        anything is read: bytes_per_row covers a row, rows_per_image covers an image, the last byte read lies inside data_len.
+ *                        A refused write changes nothing.
+ *   generate_mips_layers levels 1.. of the named layers only, each from the stored level above, with the layers' recorded kinds: the bytes
+ *                        awsm_hip_texture_array_generate_mips gives.
+ * write_layers and generate_mips_layers neither reallocate nor synchronise the stream: a source of up to 4 MiB goes through the pinned staging
+ * ring, a larger one is copied from the caller's memory and the call waits for that copy alone.  Everything is enqueued behind the opaque passes in
+ * flight (AWSM_CFG_OVERLAP_FRAMES: a frame already submitted keeps the old texels).  AWSM_ERR_NOT_READY: the array was never created or uploaded;
+ * AWSM_ERR_OUT_OF_RANGE: layers past the array; AWSM_ERR_UNSUPPORTED: an unknown format or flag bit. ---- */
+enum { AWSM_TEX_PREMULTIPLY_ALPHA = 1u, AWSM_TEX_SRGB_TO_LINEAR = 2u };
+typedef struct AwsmTexWrite {
+    uint32_t struct_size;      /* sizeof(AwsmTexWrite) */
+    uint32_t format;           /* 0 = RGBA8 */
+    uint32_t flags;            /* AWSM_TEX_* */
+    uint32_t mipmap_kind;      /* MipmapTextureKind of the layers written */
+    uint32_t bytes_per_row;
+    uint32_t rows_per_image;
+    uint64_t offset;
+} AwsmTexWrite;
+int awsm_hip_texture_array_create(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t width, uint32_t height, uint32_t layers, uint32_t mips);
+int awsm_hip_texture_array_resize_layers(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t layers);
+int awsm_hip_texture_array_write_layers(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t first_layer, uint32_t n_layers, const void* data, size_t data_len,
+                                        const AwsmTexWrite* write);
+int awsm_hip_texture_array_generate_mips_layers(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t first_layer, uint32_t n_layers);
+int awsm_hip_texture_array_info(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t* width, uint32_t* height, uint32_t* layers, uint32_t* mips);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,19 @@ int awsm_host_transform_world(AwsmHost* h, AwsmKey key, float out_mat4[16]);
 int awsm_host_texture_insert(AwsmHost* h, const uint8_t* rgba8, uint32_t width, uint32_t height);   /* returns texture id >= 0; mip kind albedo */
 /* with the MipmapTextureKind the image's role implies (0 albedo, 1 normal, 2 metallic-roughness, 3 occlusion, 4 emissive, 5.. box) */
 int awsm_host_texture_insert_kind(AwsmHost* h, const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t mipmap_kind);
+/* TexturePool::add_image with its TextureColorInfo (texture_pool.rs:233-303): srgb_to_linear decodes the colour channels on the
+ * device as the image enters the pool (base colour, emissive, specular colour and sheen colour images: gltf/populate/material.rs:140,255,348,567),
+ * premultiply_alpha multiplies them by alpha first.  Needs a backend with awsm_hip_texture_array_write_layers: without it a flagged insert is
+ * AWSM_ERR_UNSUPPORTED.  An image inserted after the array went to the device costs its own bytes and its own mip chain, not the array's. */
+typedef struct AwsmHostTextureDesc {
+    uint32_t struct_size;      /* sizeof(AwsmHostTextureDesc) */
+    uint32_t mipmap_kind;
+    uint32_t srgb_to_linear;   /* 0 / 1 */
+    uint32_t premultiply_alpha;
+} AwsmHostTextureDesc;
+int awsm_host_texture_insert_ex(AwsmHost* h, const uint8_t* rgba8, uint32_t width, uint32_t height, const AwsmHostTextureDesc* desc);   /* texture id */
+/* new pixels for an existing texture: same extent, same desc.  A frame already submitted (AWSM_CFG_OVERLAP_FRAMES) keeps the old ones. */
+int awsm_host_texture_update(AwsmHost* h, int texture_id, const uint8_t* rgba8);
 int awsm_host_sampler_insert(AwsmHost* h, const AwsmSampler* sampler);                                /* returns sampler id >= 0 */
 AwsmKey awsm_host_texture_transform_insert(AwsmHost* h, const float offset[2], const float origin[2], float rotation, const float scale[2]);
 
@@ -238,6 +251,16 @@ typedef struct AwsmGltfInfo {
     uint32_t nodes, meshes, materials, images, samplers, skins, lights, triangles, generated_tangents, instanced_meshes, reserved[2];
 } AwsmGltfInfo;
 int awsm_host_load_gltf(AwsmHost* h, const char* path, int scene_index, AwsmGltfInfo* info_out, char* err_out, size_t err_cap);
+/* The same with options.  AWSM_GLTF_SRGB_COLOR_TEXTURES: base colour, emissive, specular colour and sheen colour images are decoded from sRGB as
+ * they enter the pool (material.rs:140,255,348,567); pool entries are then keyed by (texture index, colour info) as create_material_cache_key does
+ * (material.rs:812-857), so an image used as colour and as data enters twice.  Without the flag: awsm_host_load_gltf. */
+enum { AWSM_GLTF_SRGB_COLOR_TEXTURES = 1u };
+typedef struct AwsmGltfOptions {
+    uint32_t struct_size;      /* sizeof(AwsmGltfOptions) */
+    int32_t scene_index;       /* < 0: the document's default scene */
+    uint32_t flags;            /* AWSM_GLTF_* */
+} AwsmGltfOptions;
+int awsm_host_load_gltf_ex(AwsmHost* h, const char* path, const AwsmGltfOptions* options, AwsmGltfInfo* info_out, char* err_out, size_t err_cap);
 /* the image decoders the reader uses (PNG: all colour types / bit depths, non-interlaced; JPEG: baseline / extended sequential Huffman,
  * 8-bit, grayscale or YCbCr) on their own: rgba_out = NULL queries the size; needs width * height * 4 bytes. */
 int awsm_host_decode_image(const uint8_t* data, size_t len, uint8_t* rgba_out, size_t cap, uint32_t* width, uint32_t* height, char* err_out, size_t err_cap);
@@ -248,6 +271,8 @@ int awsm_host_draw_list(AwsmHost* h, AwsmDraw* out, uint32_t cap, uint32_t* n); 
 /* the hud meshes (back to front) as the HUD geometry pass and the HUD transparent pass receive them: n entries in each array */
 int awsm_host_hud_draw_lists(AwsmHost* h, AwsmDraw* geometry_out, AwsmDraw* transparent_out, uint32_t cap, uint32_t* n);
 uint32_t awsm_host_texture_array_count(AwsmHost* h);
+/* the pool's content: layers inserted with srgb_to_linear / premultiply_alpha are converted here, on the host, by the device's table and
+ * integer rule, when this is first asked (tests and the oracle ask; rendering never does) */
 int awsm_host_texture_array_info(AwsmHost* h, uint32_t array_idx, uint32_t* width, uint32_t* height, uint32_t* layers, const uint8_t** texels);
 uint64_t awsm_host_upload_bytes_last_frame(AwsmHost* h);
 
