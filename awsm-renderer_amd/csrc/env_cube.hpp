@@ -1,4 +1,4 @@
-// env_cube.hpp — launch arguments shared by awsm_hip.cpp and kernels_env.hip (environment cubes at run time).
+// env_cube.hpp — launch arguments shared by awsm_resources.cpp and kernels_env.hip (environment cubes at run time).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

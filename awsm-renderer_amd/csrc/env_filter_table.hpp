@@ -1,4 +1,4 @@
-// env_filter_table.hpp — the sample tables of awsm_hip_env_cube_filter.  Host-side, no HIP: awsm_hip.cpp builds a level's table
+// env_filter_table.hpp — the sample tables of awsm_hip_env_cube_filter.  Host-side, no HIP: awsm_resources.cpp builds a level's table
 // here and uploads it; header-only so that tests/test_env_filter_cpu.py can compile it with g++ into a program of its own and compare every entry,
 // bit for bit, with the Python restatement (tests/ibl_filter_reference.py).  A table depends on (kind, level, levels, samples, source side) only,
 // never on the texel; it is made in f64 — the operations below, in this order — and each number is rounded to f32 once.

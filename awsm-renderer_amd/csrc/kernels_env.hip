@@ -10,6 +10,7 @@
 #include "frame_params.hpp"
 #include "device_math.hpp"
 #include "env_cube.hpp"
+#include "launch.hpp"
 
 namespace awsm {
 

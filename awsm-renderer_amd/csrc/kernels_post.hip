@@ -25,6 +25,7 @@
 #include <cstdint>
 #include "frame_params.hpp"
 #include "raster_setup.hpp"
+#include "launch.hpp"
 
 namespace awsm {
 namespace post {
@@ -288,8 +289,8 @@ __global__ __launch_bounds__(256) void k_post_bloom(PostArgs a) {
 using awsm::PostArgs;
 
 // flags: 1 SMAA, 2 bloom, 4 DoF (AWSM_POST_*); msaa: 1 or 4.  bloom_a / bloom_b: the two f16 ping-pong images of the bloom chain.
-extern "C" void awsm_launch_post(const void* args_v, uint32_t flags, uint32_t msaa, void* bloom_a, void* bloom_b, hipStream_t s) {
-    PostArgs a = *reinterpret_cast<const PostArgs*>(args_v);
+extern "C" void awsm_launch_post(const PostArgs* args, uint32_t flags, uint32_t msaa, void* bloom_a, void* bloom_b, hipStream_t s) {
+    PostArgs a = *args;
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16), block(256);
     const bool smaa = flags & 1u, bloom = flags & 2u, dof = flags & 4u;
     if (dof) {

@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "frame_params.hpp"
 #include "raster_setup.hpp"
+#include "launch.hpp"
 
 #ifndef AWSM_LEAN_WAVES
 #define AWSM_LEAN_WAVES 6
@@ -3256,7 +3257,6 @@ extern "C" void awsm_launch_resolve_draws(const awsm::DevScene* sc, const awsm::
 #define AWSM_LAUNCH_SG(g, K, S, grid, block, ...) do { if ((g) == 2) hipLaunchKernelGGL((K<S, 2>), grid, block, 0, s, __VA_ARGS__); else if ((g) == 1) hipLaunchKernelGGL((K<S, 1>), grid, block, 0, s, __VA_ARGS__); \
                                                        else hipLaunchKernelGGL((K<S, 0>), grid, block, 0, s, __VA_ARGS__); } while (0)
 static inline int mip_mode(const awsm::FrameDev* f) { return f->mipmap ? (f->aniso ? 2 : 1) : 0; }
-extern "C" int awsm_shade_is_lean(const awsm::FrameDev* f);
 extern "C" void awsm_launch_shade(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s) {
     const uint32_t bx_n = (f->width + 15u) >> 4, by_n = f->band_n > 1u ? 2u * f->tiles_y : ((f->sy1 - f->sy0) + 15u) >> 4;
     const uint32_t nb = 8u * ((by_n + 7u) / 8u) * bx_n;   // every XCD gets ceil(by_n / 8) rows of ids; surplus ids exit

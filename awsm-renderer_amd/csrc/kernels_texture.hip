@@ -1,12 +1,14 @@
-// kernels_texture.hip — the 2D texture pool at run time (include/awsm_hip.h: awsm_hip_texture_array_write_layers / _generate_mips_layers;
-// DESIGN.md §14).  The reference's counterparts are TexturePool's external-image copy with premultiplied_alpha and its sRGB -> linear pass
+// kernels_texture.hip — the 2D texture pool: level 0 at run time (include/awsm_hip.h: awsm_hip_texture_array_write_layers) and the
+// RGBA8 mip chains, a level per launch over a whole array (awsm_hip_texture_array_generate_mips) or five levels per launch over a range of layers
+// (_generate_mips_layers).  The reference's counterparts are TexturePool's external-image copy with premultiplied_alpha and its sRGB -> linear pass
 // (renderer-core/src/texture/texture_pool.rs:233-303, texture/convert_srgb.rs:52-76) and the mip compute pass (texture/mipmap.rs:95-330).
-// k_tex_mips restates k_gen_mip_level (kernels_geometry.hip) operation by operation — that kernel is the yardstick for its bytes — and, like it,
-// must not be contracted into fmas (-ffp-contract=off).
+// k_gen_mip_level and k_tex_mips share one 2x2 filter, tex_mip_filter, and one unorm8 store, tex_to_unorm8: STRICT f32, never contracted into fmas
+// (-ffp-contract=off), so that the RGBA8 results are bit-identical everywhere.
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
 #include "tex_pool.hpp"
+#include "launch.hpp"
 
 namespace awsm {
 
@@ -31,8 +33,10 @@ __global__ __launch_bounds__(256) void k_tex_write(TexWriteArgs a) {
     a.dst[idx] = w;
 }
 
-// ---------------- mip chain: five levels per launch, a range of layers ----------------
-AWSM_DI uint32_t tex_to_unorm8(float v) {      // k_gen_mip_level's to_unorm8
+// ---------------- mip chains ----------------
+// generate_mipmaps (renderer-core/src/texture/mipmap.rs:140-250): 2x2 texel loads, filter by MipmapTextureKind, store as
+// unorm8 = floor(clamp(v,0,1)*255 + 0.5)
+AWSM_DI uint32_t tex_to_unorm8(float v) {
     if (!(v > 0.0f)) return 0u;          // also NaN
     if (v > 1.0f) v = 1.0f;
     return (uint32_t)floorf(v * 255.0f + 0.5f);
@@ -63,6 +67,27 @@ AWSM_DI uint32_t tex_mip_filter(const uint32_t (&t)[4], uint32_t kind) {
     }
     return tex_to_unorm8(o0) | (tex_to_unorm8(o1) << 8) | (tex_to_unorm8(o2) << 16) | (tex_to_unorm8(o3) << 24);
 }
+
+// One level of a whole array: one thread per destination texel and layer, the loads clamped to 2 x the destination extent (and to the real source
+// extent).  On whole arrays a launch per level is faster than k_tex_mips below.
+__global__ __launch_bounds__(256) void k_gen_mip_level(uint32_t* __restrict__ chain, uint32_t src_off, uint32_t dst_off, uint32_t sw, uint32_t sh,
+                                                       uint32_t dw, uint32_t dh, uint32_t layers, const uint32_t* __restrict__ kinds) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= dw * dh * layers) return;
+    const uint32_t x = i % dw, y = (i / dw) % dh, layer = i / (dw * dh);
+    const uint32_t kind = kinds[layer];
+    const uint32_t* src = chain + src_off + (size_t)layer * sw * sh;
+    uint32_t t[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t sx = min(min(x * 2u + (uint32_t)(k & 1), dw * 2u - 1u), sw - 1u);
+        uint32_t sy = min(min(y * 2u + (uint32_t)(k >> 1), dh * 2u - 1u), sh - 1u);
+        t[k] = src[(size_t)sy * sw + sx];
+    }
+    chain[dst_off + ((size_t)layer * dh + y) * dw + x] = tex_mip_filter(t, kind);
+}
+
+// ---------------- five levels per launch, a range of layers ----------------
 // the 2x2 sources of local texel (lx, ly) in a tile stored `stride` words per row.  k_gen_mip_level reads min(min(2x + k, 2 dw - 1), sw - 1): for a
 // source extent of two or more that is 2x + k itself (2 dw <= sw), for an extent of one it is 0 — xinc / yinc say which.
 AWSM_DI uint32_t tex_filter_at(const uint32_t* tile, uint32_t stride, uint32_t lx, uint32_t ly, uint32_t xinc, uint32_t yinc, uint32_t kind) {
@@ -140,6 +165,11 @@ __global__ __launch_bounds__(256) void k_tex_mips(TexMipArgs a) {
 extern "C" void awsm_launch_tex_write(const awsm::TexWriteArgs* a, hipStream_t s) {
     const uint32_t total = a->width * a->height * a->n_layers;
     if (total) hipLaunchKernelGGL(awsm::k_tex_write, dim3((total + 255u) / 256u), dim3(256), 0, s, *a);
+}
+extern "C" void awsm_launch_gen_mip_level(uint8_t* chain, uint32_t src_off, uint32_t dst_off, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, uint32_t layers,
+                                          const uint32_t* kinds, hipStream_t s) {
+    const uint32_t n = dw * dh * layers;
+    if (n) hipLaunchKernelGGL(awsm::k_gen_mip_level, dim3((n + 255u) / 256u), dim3(256), 0, s, (uint32_t*)chain, src_off, dst_off, sw, sh, dw, dh, layers, kinds);
 }
 extern "C" void awsm_launch_tex_mips(const awsm::TexMipArgs* a, hipStream_t s) {
     const uint32_t dw = a->sw > 1u ? a->sw >> 1 : 1u, dh = a->sh > 1u ? a->sh >> 1 : 1u;

@@ -1,4 +1,4 @@
-// tex_pool.hpp — the 2D texture pool at run time: launch arguments shared by awsm_hip.cpp and kernels_texture.hip, and the parts
+// tex_pool.hpp — the 2D texture pool at run time: launch arguments shared by awsm_resources.cpp and kernels_texture.hip, and the parts
 // of the contract that are plain C++ — the sRGB table, the integer premultiply and the validation of a write — so that the host library and the
 // CPU tests use the very same code.  No HIP header is needed to include this file.
 #pragma once
@@ -17,12 +17,14 @@ namespace awsm {
 
 constexpr uint32_t kTexPremultiplyAlpha = 1u, kTexSrgbToLinear = 2u;      // AWSM_TEX_PREMULTIPLY_ALPHA, AWSM_TEX_SRGB_TO_LINEAR
 
+// the sRGB decode in f64: this table's and the environment cubes' 8-bit -> f16 table's (awsm_resources.cpp: env_tables)
+inline double srgb_to_linear(double c) { return c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4); }
+
 // sRGB-encoded q / 255 -> linear, stored as unorm8 = floor(clamp(lin, 0, 1) * 255 + 0.5): 256 bytes, evaluated in f64.  No entry lies within 1e-3
 // of a rounding tie, so an f32 evaluation of the same expression (the reference's shader) gives the same bytes (tests/test_texture_pool_cpu.py).
 inline void tex_srgb_table(uint8_t out[256]) {
     for (int q = 0; q < 256; q++) {
-        const double c = (double)q / 255.0;
-        double lin = c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4);
+        double lin = srgb_to_linear((double)q / 255.0);
         lin = lin < 0.0 ? 0.0 : (lin > 1.0 ? 1.0 : lin);
         out[q] = (uint8_t)floor(lin * 255.0 + 0.5);
     }

@@ -118,6 +118,49 @@ def test_write_layers_refusals_change_nothing(dev):
     assert not dev.texture_array_read_level(1, 0)[1].any()
 
 
+def test_array_shape_refusals_change_nothing():
+    """A texture array or a cube of a shape the library does not hold is refused with the documented code by every entry that takes a shape
+    (_upload, _create, _resize_layers; env_cube_upload, env_cube_create), and what the context held stays as it was.  The raw entries are called
+    where the Python wrapper derives the value from an array."""
+    dev = HipDevice(parity_tap=True)
+    lib, ctx = dev.lib, dev.ctx
+    w, h = 4, 2
+    dev.texture_array_create(5, w, h, 2, 3)
+    base = random_texels(np.random.default_rng(17), (2, h, w))
+    dev.texture_array_write_layers(5, 0, base)
+    texels = np.zeros(64, dtype=np.uint8)      # never read: every call below is refused before a copy
+    ptr = texels.ctypes.data_as(hip_backend.C.c_void_p)
+
+    def unchanged():
+        assert dev.texture_array_info(5) == (w, h, 2, 3)
+        assert (dev.texture_array_read_level(5, 0) == base).all()
+
+    for (uw, uh, layers, mips), code in [((0, h, 2, 3), INVALID), ((w, h, 65537, 3), UNSUPPORTED), ((w, h, 2, 4), INVALID)]:
+        assert lib.awsm_hip_texture_array_upload(ctx, 5, uw, uh, layers, mips, 0, ptr) == code, ("upload", uw, uh, layers, mips)
+        unchanged()
+    for (cw, ch, layers, mips), code in [((w, 0, 2, 3), INVALID), ((w, h, 2, 4), INVALID), ((w, h, 65537, 3), UNSUPPORTED),
+                                         ((256, 256, 65536, 1), UNSUPPORTED)]:      # the last: 2^32 texels, refused before any allocation
+        assert lib.awsm_hip_texture_array_create(ctx, 5, cw, ch, layers, mips) == code, ("create", cw, ch, layers, mips)
+        unchanged()
+    assert lib.awsm_hip_texture_array_resize_layers(ctx, 5, 65537) == UNSUPPORTED
+    unchanged()
+    dev.texture_array_create(6, 256, 256, 1, 1)
+    assert lib.awsm_hip_texture_array_resize_layers(ctx, 6, 65536) == UNSUPPORTED      # 2^32 texels
+    assert dev.texture_array_info(6) == (256, 256, 1, 1)
+    unchanged()
+
+    rng = np.random.default_rng(18)
+    levels = [rng.random((6, n, n, 4)).astype(np.float16) for n in (8, 4, 2, 1)]
+    dev.env_cube_upload(0, levels)
+    for size, mips in [(0, 1), (8193, 1), (8, 5)]:      # 8^2 has four levels
+        assert lib.awsm_hip_env_cube_upload(ctx, 0, size, mips, ptr) == INVALID, ("env_cube_upload", size, mips)
+        assert lib.awsm_hip_env_cube_create(ctx, 0, size, mips) == INVALID, ("env_cube_create", size, mips)
+        assert dev.env_cube_info(0) == (8, 4)
+        assert (dev.env_cube_read_level(0, 0).view(np.uint16) == levels[0].view(np.uint16)).all()
+    unchanged()
+    dev.close()
+
+
 # ------------------------------------------------------------------------------------------------ 2. generate_mips_layers
 
 KINDS = [0, 1, 2, 3, 5]

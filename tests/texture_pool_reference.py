@@ -80,8 +80,9 @@ def to_unorm8(v):
 
 
 def mip_level(src, kinds):
-    """One level below (layers, h, w, 4) uint8, k_gen_mip_level's arithmetic in f32: coordinates min(min(2x + k, 2 dw - 1), sw - 1), q / 255 by
-    division, sums in k order, * 0.25, kind 1 renormalised, kind 2 root mean square of channel 1, to_unorm8 with NaN -> 0."""
+    """One level below (layers, h, w, 4) uint8, the arithmetic of kernels_texture.hip's tex_mip_filter (which k_gen_mip_level and k_tex_mips share)
+    in f32: coordinates min(min(2x + k, 2 dw - 1), sw - 1), q / 255 by division, sums in k order, * 0.25, kind 1 renormalised, kind 2 root mean
+    square of channel 1, tex_to_unorm8 with NaN -> 0."""
     f = np.float32
     layers, sh, sw, _ = src.shape
     dw, dh = max(sw >> 1, 1), max(sh >> 1, 1)
