@@ -15,6 +15,7 @@ from awsm_renderer_amd import host as H
 from awsm_renderer_amd.scene_desc import MaterialDesc, NodeDesc, PrimitiveDesc, SceneDesc, TextureRef
 from oracle import scene_model as sm
 from tests import helpers
+from tests import vertex_stage_cases
 
 MOCK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mock", "libmock_backend.so")
 
@@ -57,13 +58,17 @@ SCENES = {
     "zoo": lambda: scenes.material_zoo_scene(96, 64, tex_size=16),
     "transparent": lambda: scenes.transparent_scene(96, 64, tex_size=16),
     "instanced": lambda: scenes.instanced_scene(96, 64),
+    # JOINTS_1.. / WEIGHTS_1.., morph TANGENT, negative scales (tests/vertex_stage_cases.py)
+    "morph_then_skin": vertex_stage_cases.morph_then_skin,
+    "instanced_morphed": vertex_stage_cases.instanced_morphed,
+    "mirrored": vertex_stage_cases.mirrored,
 }
 
 
 @pytest.mark.parametrize("name", sorted(SCENES))
 @pytest.mark.parametrize("container", ["glb", "gltf", "gltf_data_uri"])
 def test_round_trip_equals_direct_population(name, container, tmp_path):
-    if container != "glb" and name not in ("helmet", "skinned_morph"):
+    if container != "glb" and name not in ("helmet", "skinned_morph", "morph_then_skin", "instanced_morphed", "mirrored"):
         pytest.skip("one container variant per scene is enough beyond glb")
     scene = SCENES[name]()
     path = str(tmp_path / (name + (".glb" if container == "glb" else ".gltf")))

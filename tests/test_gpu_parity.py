@@ -1358,13 +1358,15 @@ def test_transparent_pass_edge_cases(oracle_lut):
 # ------------------------------------------------------------------------------------------------ glTF ingest
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["helmet", "skinned_morph", "transparent"])
+@pytest.mark.parametrize("name", ["helmet", "skinned_morph", "transparent", "morph_then_skin"])
 def test_frames_rendered_from_a_glb_file(name, oracle_lut, tmp_path):
     """File -> native glTF reader -> host layer -> HIP kernels, against the oracle's frame of the scene the file was written from."""
     from awsm_renderer_amd import gltf_export
+    from tests import vertex_stage_cases
     sc = {"helmet": lambda: scenes.helmet_scene(320, 180, segments=48, rings=36, tex_size=64),
           "skinned_morph": lambda: scenes.skinned_morph_scene(320, 200, around=16, along=24, tex_size=16),
-          "transparent": lambda: scenes.transparent_scene(320, 180, tex_size=32)}[name]()
+          "transparent": lambda: scenes.transparent_scene(320, 180, tex_size=32),
+          "morph_then_skin": vertex_stage_cases.morph_then_skin}[name]()      # JOINTS_0..2, morph TANGENT deltas
     path = str(tmp_path / (name + ".glb"))
     gltf_export.write_glb(sc, path)
     model = helpers.build_model(sc)

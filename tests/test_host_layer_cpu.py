@@ -12,6 +12,7 @@ from awsm_renderer_amd import host as H
 from awsm_renderer_amd import scenes
 from oracle import scene_model as sm
 from tests import helpers
+from tests import vertex_stage_cases
 
 MOCK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mock")
 MOCK = os.path.join(MOCK_DIR, "libmock_backend.so")
@@ -54,6 +55,10 @@ SCENES = {
     "skinned_morph": lambda: scenes.skinned_morph_scene(64, 64, around=8, along=12, tex_size=16),
     "atrium": lambda: scenes.atrium_scene(96, 64, detail=0.125, tex_scale=1 / 64),
     "instanced": lambda: scenes.instanced_scene(96, 64),
+    # multi-set skin packing, tangent morph deltas, mirrored and instanced morphed meshes (tests/vertex_stage_cases.py)
+    "morph_then_skin": vertex_stage_cases.morph_then_skin,
+    "instanced_morphed": vertex_stage_cases.instanced_morphed,
+    "mirrored": vertex_stage_cases.mirrored,
 }
 
 
@@ -68,7 +73,7 @@ def test_mirrors_and_draw_list_match_the_model(name, mock):
         if which in (sm.BUF_LIGHTS, sm.BUF_LIGHTS_INFO):
             continue
         assert r.host.mirror(which) == bytes(data), f"mirror {which} differs"
-        if which == sm.BUF_INSTANCES and name != "instanced":
+        if which == sm.BUF_INSTANCES and name not in ("instanced", "instanced_morphed", "mirrored"):
             assert device_bytes(mock, ctx, which) is None      # written only once instancing is used (instances.rs:203-242: transform_gpu_dirty)
         elif which != sm.BUF_VIS_GEOM_INDEX:     # identity indices are never uploaded (redundant for a SW rasteriser)
             assert device_bytes(mock, ctx, which) == bytes(data), f"device copy of {which} differs from its mirror"
