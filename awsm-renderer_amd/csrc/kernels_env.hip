@@ -4,12 +4,13 @@
 // Lambert irradiance level.  The reference's counterparts are gpu.write_texture (renderer-core/src/cubemap.rs:180-228) and the mip
 // compute pass (renderer-core/src/texture/mipmap.rs:143-232, filter_simple for MipmapTextureKind::Albedo).  The arithmetic is DESIGN.md §12:
 // every conversion rounds to f16 once, to nearest even; nothing here may be contracted into an fma (-ffp-contract=off).
-// The apron of the changed levels is rebuilt afterwards by k_cube_border (kernels_shade.hip), which owns the seam rule.
+// The apron of the changed levels is rebuilt afterwards by k_cube_border (kernels_shade.hip) by the seam rule of cube_seam.hpp.
 #include <hip/hip_runtime.h>
 
 #include "frame_params.hpp"
 #include "device_math.hpp"
 #include "env_cube.hpp"
+#include "cube_seam.hpp"
 #include "launch.hpp"
 
 namespace awsm {
@@ -137,23 +138,9 @@ __global__ __launch_bounds__(256) void k_env_mips(EnvMipArgs a) {
 }
 
 // ---------------- filtering a source cube into the split-sum inputs (awsm_hip_env_cube_filter) ----------------
-// textureSampleLevel on the source by sample_cube's contract (kernels_shade.hip, restated: that file's code objects stay as they are): the major
+// textureSampleLevel on the source by sample_cube's contract (kernels_shade.hip), with its seam rule (cube_seam.hpp; the face ladder is restated, see there): the major
 // axis picks the face, bilinear on the level's N x N faces, a tap off the face comes from the face across that edge, the level is clamped to the
 // chain and its two nearest levels are blended.  Divisions and square roots are IEEE here; nothing is clamped, so a non-finite texel propagates.
-__device__ const uint8_t kEnvCubeEdge[6][4] = {{44, 13, 58, 43}, {45, 12, 10, 27}, {1, 16, 21, 4}, {49, 32, 36, 53}, {41, 8, 34, 3}, {40, 9, 18, 51}};
-AWSM_DI uint2 env_texel_seam(const CubeDev& c, uint32_t level_base, int N, uint32_t face, int i, int j) {      // cube_texel_raw
-    if (i < 0 || i >= N) j = min(max(j, 0), N - 1);     // corner taps keep their row
-    if (i < 0 || i >= N || j < 0 || j >= N) {
-        const uint32_t e = i < 0 ? 0u : (i >= N ? 1u : (j < 0 ? 2u : 3u));
-        const uint32_t t = kEnvCubeEdge[face][e];
-        int k = e < 2u ? j : i;
-        if (t & 16u) k = N - 1 - k;
-        const int far = (t & 32u) ? N - 1 : 0;
-        face = t & 7u;
-        if (t & 8u) { i = far; j = k; } else { i = k; j = far; }
-    }
-    return c.texels[level_base + ((size_t)face * (size_t)N + (size_t)j) * (size_t)N + (size_t)i];
-}
 AWSM_DI f3 env_lerp3(f3 a, f3 b, float t) { const float s = 1.0f - t; return {a.x * s + b.x * t, a.y * s + b.y * t, a.z * s + b.z * t}; }
 AWSM_DI f3 env_rgb(uint2 h) { return {f16_bits_to_f32((unsigned short)(h.x & 0xFFFFu)), f16_bits_to_f32((unsigned short)(h.x >> 16)), f16_bits_to_f32((unsigned short)(h.y & 0xFFFFu))}; }
 // one level; sn, tn = 0.5 (sc / ma) + 0.5 on `face`
@@ -172,8 +159,8 @@ AWSM_DI f3 env_cube_level(const CubeDev& c, uint32_t level, uint32_t face, float
         t00 = r0[0]; t10 = r0[1]; t01 = r0[P]; t11 = r0[P + 1u];
     } else {
         const uint32_t base = c.level_off[level];
-        t00 = env_texel_seam(c, base, N, face, i0, j0); t10 = env_texel_seam(c, base, N, face, i0 + 1, j0);
-        t01 = env_texel_seam(c, base, N, face, i0, j0 + 1); t11 = env_texel_seam(c, base, N, face, i0 + 1, j0 + 1);
+        t00 = cube_texel_raw(c, base, N, face, i0, j0); t10 = cube_texel_raw(c, base, N, face, i0 + 1, j0);
+        t01 = cube_texel_raw(c, base, N, face, i0, j0 + 1); t11 = cube_texel_raw(c, base, N, face, i0 + 1, j0 + 1);
     }
     return env_lerp3(env_lerp3(env_rgb(t00), env_rgb(t10), fx), env_lerp3(env_rgb(t01), env_rgb(t11), fx), fy);
 }

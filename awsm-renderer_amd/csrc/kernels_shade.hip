@@ -10,8 +10,9 @@
 //       materialised; the interpolants of the visible triangle are recomputed here and rounded to the
 //       reference's RG16F / RGBA16F storage formats before use, crates/renderer/src/render_textures.rs:49-54)
 //
-// In this file, in order: the STRICT G-buffer reconstruction and MSAA edge predicates; the samplers (2D arrays: level 0 / gradient mips / anisotropic
-// probes; cubes; the BRDF LUT); the material and lighting code of the general route (shade_material, shade_surface) with the transparent pass's three
+// Before this file: shade_gbuffer.hpp (the STRICT G-buffer reconstruction and MSAA edge predicates), shade_samplers.hpp (fm::, the samplers of 2D arrays:
+// level 0 / gradient mips / anisotropic probes; the BRDF terms and the BRDF LUT) and cube_seam.hpp (the cube's seam table and rule, shared with
+// kernels_env.hip).  In this file, in order: the cube sampler; the material and lighting code of the general route (shade_material, shade_surface) with the transparent pass's three
 // kernels (k_forward_cover / shade / blend); k_resolve_draws; the general opaque kernels (k_shade, k_shade_todo); the lean route (k_shade_lean: level-1
 // records staged through LDS, scalar draw records, lean::fetch*, the aproned cube sampler); the MSAA kernels (k_shade_msaa, k_msaa_detect,
 // k_shade_msaa_resolve); k_brdf_lut, k_cube_border and the small service kernels; the launch wrappers.  Kernels that sample are instantiated per mip mode
@@ -21,8 +22,9 @@
 // RGBA16F write; everything else (vertices, metas, materials, texels) is reused across neighbouring pixels
 // and served by L1 / the XCD's L2 — workgroups are dealt to XCDs in contiguous screen runs for that.
 #include <type_traits>
-#include "frame_params.hpp"
-#include "raster_setup.hpp"
+#include "shade_gbuffer.hpp"
+#include "shade_samplers.hpp"
+#include "cube_seam.hpp"
 #include "launch.hpp"
 
 #ifndef AWSM_LEAN_WAVES
@@ -31,602 +33,11 @@
 
 namespace awsm {
 
-// ================================================================================================
-// STRICT section (arithmetic contract, -ffp-contract=off, IEEE div/sqrt): what fs_main wrote for this pixel
-// (fragment.wgsl:23-54), rounded to the G-buffer storage formats.  Bit-identical to the CPU oracle (tests only).
-// ================================================================================================
-struct GBufferTexel {
-    f4 packed_nt;    // RGBA16F normal_tangent, already rounded to f16
-    float bx, by;    // RG16F barycentric, already rounded to f16
-    f4 bary_derivs;  // RGBA16F barycentric_derivatives (db0/dx, db0/dy, db1/dx, db1/dy), rounded to f16; MipmapMode::Gradient only
-};
-// The interpolants are evaluated at the PIXEL CENTRE (@interpolate(perspective, center)); with MSAA the centre may lie
-// outside the triangle and the values extrapolate — every sample the triangle covers in the pixel gets the same texel.
-// A key in the visibility buffer means the triangle's setup record is valid; its edge coefficients are the bits the
-// raster kernel used.
-template <bool DERIVS>
-AWSM_DI GBufferTexel reconstruct_core(const TriSetup& t, float4 n0, float4 n1, float4 n2, float4 t0, float4 t1, float4 t2, int cx, int cy) {
-    GBufferTexel g;
-    g.bary_derivs = {0.0f, 0.0f, 0.0f, 0.0f};
-    const double Xc = sample_coord((cx << 8) + 128), Yc = sample_coord((cy << 8) + 128);
-    const EdgeVals ev = tri_edges_d(t, Xc, Yc);
-    // screen-space edge weights -> perspective-correct barycentrics: one IEEE reciprocal, six products
-    const float e0 = (float)ev.E[0] * t.iw[0], e1 = (float)ev.E[1] * t.iw[1], e2 = (float)ev.E[2] * t.iw[2];
-    const float inv_esum = 1.0f / ((e0 + e1) + e2);
-    const float b0 = e0 * inv_esum, b1 = e1 * inv_esum, b2 = e2 * inv_esum;
-    const f3 Ni = {(b0 * n0.x + b1 * n1.x) + b2 * n2.x, (b0 * n0.y + b1 * n1.y) + b2 * n2.y, (b0 * n0.z + b1 * n1.z) + b2 * n2.z};
-    const f4 Ti = {(b0 * t0.x + b1 * t1.x) + b2 * t2.x, (b0 * t0.y + b1 * t1.y) + b2 * t2.y,
-                   (b0 * t0.z + b1 * t1.z) + b2 * t2.z, (b0 * t0.w + b1 * t1.w) + b2 * t2.w};
-    const f4 p = pack_normal_tangent(normalize(Ni), normalize(mk3(Ti.x, Ti.y, Ti.z)), Ti.w);
-    g.packed_nt = {round_f16(p.x), round_f16(p.y), round_f16(p.z), round_f16(p.w)};
-    g.bx = round_f16(b0);
-    g.by = round_f16(b1);
-    if (DERIVS) {
-        // fragment.wgsl:46-51 dpdx/dpdy of the barycentrics.  Contract ("fine" derivatives of a 2x2 quad): the difference
-        // between the two pixels of the quad row / column this pixel sits in, both evaluated for THIS triangle (helper
-        // invocations extrapolate), right minus left and bottom minus top; then RGBA16F.
-        const EdgeVals eh = tri_edges_d(t, sample_coord(((cx ^ 1) << 8) + 128), Yc), evv = tri_edges_d(t, Xc, sample_coord(((cy ^ 1) << 8) + 128));
-        const float h0 = (float)eh.E[0] * t.iw[0], h1 = (float)eh.E[1] * t.iw[1], h2 = (float)eh.E[2] * t.iw[2];
-        const float w0 = (float)evv.E[0] * t.iw[0], w1 = (float)evv.E[1] * t.iw[1], w2 = (float)evv.E[2] * t.iw[2];
-        const float ish = 1.0f / ((h0 + h1) + h2), isv = 1.0f / ((w0 + w1) + w2);
-        const float hb0 = h0 * ish, hb1 = h1 * ish, vb0 = w0 * isv, vb1 = w1 * isv;
-        const float ddx0 = (cx & 1) ? b0 - hb0 : hb0 - b0, ddx1 = (cx & 1) ? b1 - hb1 : hb1 - b1;
-        const float ddy0 = (cy & 1) ? b0 - vb0 : vb0 - b0, ddy1 = (cy & 1) ? b1 - vb1 : vb1 - b1;
-        g.bary_derivs = {round_f16(ddx0), round_f16(ddy0), round_f16(ddx1), round_f16(ddy1)};
-    }
-    return g;
-}
-template <bool DERIVS>
-AWSM_DI GBufferTexel reconstruct_gbuffer(const FrameDev& f, uint32_t rank, int cx, int cy) {
-    TriSetup t;
-    tri_rec_load(f.tri_rec + rank, t);
-    const float4 n0 = f.nrm[(size_t)rank * 3], n1 = f.nrm[(size_t)rank * 3 + 1], n2 = f.nrm[(size_t)rank * 3 + 2];
-    const float4 t0 = f.tan[(size_t)rank * 3], t1 = f.tan[(size_t)rank * 3 + 1], t2 = f.tan[(size_t)rank * 3 + 2];
-    return reconstruct_core<DERIVS>(t, n0, n1, n2, t0, t1, t2, cx, cy);
-}
-
-// The decoded normal of the pixel's G-buffer texel alone — decode_octahedral(packed_nt.xy) — for the MSAA edge detector: the same operations on the
-// same values as reconstruct_core + pack_normal_tangent's octahedral half, without the tangent (its interpolation, normalisation, basis and atan2: a
-// third of the reconstruction) and without the tangents' 48 bytes per lane.  Bit-identical to unpack_normal_tangent(g.packed_nt).N by construction.
-AWSM_DI f2 strict_oct_of(const FrameDev& f, uint32_t rank, int cx, int cy) {
-    TriSetup t;
-    tri_rec_load(f.tri_rec + rank, t);
-    const float4 n0 = f.nrm[(size_t)rank * 3], n1 = f.nrm[(size_t)rank * 3 + 1], n2 = f.nrm[(size_t)rank * 3 + 2];
-    const double Xc = sample_coord((cx << 8) + 128), Yc = sample_coord((cy << 8) + 128);
-    const EdgeVals ev = tri_edges_d(t, Xc, Yc);
-    const float e0 = (float)ev.E[0] * t.iw[0], e1 = (float)ev.E[1] * t.iw[1], e2 = (float)ev.E[2] * t.iw[2];
-    const float inv_esum = 1.0f / ((e0 + e1) + e2);
-    const float b0 = e0 * inv_esum, b1 = e1 * inv_esum, b2 = e2 * inv_esum;
-    const f3 Ni = {(b0 * n0.x + b1 * n1.x) + b2 * n2.x, (b0 * n0.y + b1 * n1.y) + b2 * n2.y, (b0 * n0.z + b1 * n1.z) + b2 * n2.z};
-    const f2 oct = encode_octahedral(normalize(Ni));
-    return mk2(round_f16(oct.x), round_f16(oct.y));
-}
-AWSM_DI f3 strict_normal_of(const FrameDev& f, uint32_t rank, int cx, int cy) { return decode_octahedral(strict_oct_of(f, rank, cx, cy)); }
-// An octahedral pair as two f16 in a word (its values ARE f16 values: exact both ways)
-AWSM_DI uint32_t oct_word(f2 oct) { return (uint32_t)f16_bits(oct.x) | ((uint32_t)f16_bits(oct.y) << 16); }
-AWSM_DI f2 oct_of_word(uint32_t w) { return mk2(__half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu))), __half2float(__ushort_as_half((unsigned short)(w >> 16)))); }
-
-// Is pixel row `py` one this shard shades (row strip: [sy0, sy1); bands: the 32-row tile rows r, r + n, ...)?
-AWSM_DI bool row_owned(const FrameDev& f, int py) {
-    if (py < (int)f.sy0 || py >= (int)f.sy1) return false;
-    return f.band_n <= 1u || (((uint32_t)py >> kTileShift) % f.band_n) == f.band_r;
-}
-
-// ---- MSAA edge predicates (helpers/msaa.wgsl), STRICT: a decision that flips between implementations would swap a
-// pixel between one-sample and four-sample shading, so every value feeding a threshold follows the arithmetic contract ----
-constexpr float kEdgeNormalThreshold = 0.95f, kEdgeDepthThreshold = 0.02f, kEdgeMsaaDepthThreshold = 0.02f;
-AWSM_DI float view_space_depth(const m4& inv_proj, float depth, float px, float py, float W, float H) {   // msaa.wgsl:185-199
-    // A projection whose view-space z and w depend on the depth alone (every perspective_rh / orthographic_rh: glam's matrices have exact zeros there) makes
-    // the x and y terms of those two rows exact zeros, and ((0 x + 0 y) + c2 d) + c3 IS c2 d + c3 bit for bit: the NDC divisions and two thirds of the
-    // product drop out (the detector calls this up to nine times per pixel).  Wave-uniform test; anything else takes the full product.
-    if (inv_proj.c[0].z == 0.0f && inv_proj.c[1].z == 0.0f && inv_proj.c[0].w == 0.0f && inv_proj.c[1].w == 0.0f)
-        return (inv_proj.c[2].z * depth + inv_proj.c[3].z) / (inv_proj.c[2].w * depth + inv_proj.c[3].w);
-    const f4 view_pos = mul(inv_proj, mk4((px / W) * 2.0f - 1.0f, 1.0f - (py / H) * 2.0f, depth, 1.0f));
-    return view_pos.z / view_pos.w;
-}
-AWSM_DI float key_depth(unsigned long long k) { return k == ~0ull ? 1.0f : __uint_as_float((uint32_t)(k >> 32)); }   // depth clear = 1.0
-AWSM_DI uint32_t key_rank(unsigned long long k) { return 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull); }
-AWSM_DI bool edge_mask_depth_msaa(const m4& inv_proj, const unsigned long long k4[4], float pcx, float pcy, float W, float H) {   // msaa.wgsl:116-146
-    uint32_t count = 0; float dmin = 1e9f, dmax = -1e9f;
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        if (k4[s] == ~0ull) continue;
-        count++;
-        const float vd = view_space_depth(inv_proj, key_depth(k4[s]), pcx, pcy, W, H);
-        dmin = fminf(dmin, vd); dmax = fmaxf(dmax, vd);
-    }
-    if (count < 2u) return false;
-    return fabsf(dmax - dmin) > (kEdgeMsaaDepthThreshold * fabsf((dmax + dmin) * 0.5f));
-}
-
-// The two depth predicates with the division behind a filter: a projection whose view depth is (a d + b) / (c d + e) (view_space_depth's first form) is
-// evaluated with the hardware reciprocal — numerator and denominator as the strict form computes them, so the quotient is within 2 ulps of the IEEE one —
-// and the comparison is accepted when it clears the threshold by more than 4e-6 of the larger depth (ten times that error); anything closer, and any
-// other projection, takes the strict form.  Same decisions, a fifth of the instructions (an IEEE division is ten, and the detector makes up to nine).
-AWSM_DI bool depth_only_projection(const m4& inv_proj) { return inv_proj.c[0].z == 0.0f && inv_proj.c[1].z == 0.0f && inv_proj.c[0].w == 0.0f && inv_proj.c[1].w == 0.0f; }
-AWSM_DI float view_depth_approx(const m4& inv_proj, float depth) { return (inv_proj.c[2].z * depth + inv_proj.c[3].z) * __builtin_amdgcn_rcpf(inv_proj.c[2].w * depth + inv_proj.c[3].w); }
-AWSM_DI bool edge_mask_depth_msaa_filtered(const m4& inv_proj, const unsigned long long k4[4], float pcx, float pcy, float W, float H) {
-    if (depth_only_projection(inv_proj)) {      // wave-uniform
-        uint32_t count = 0; float dmin = 1e9f, dmax = -1e9f;
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            if (k4[s] == ~0ull) continue;
-            count++;
-            const float vd = view_depth_approx(inv_proj, key_depth(k4[s]));
-            dmin = fminf(dmin, vd); dmax = fmaxf(dmax, vd);
-        }
-        if (count < 2u) return false;
-        const float lhs = fabsf(dmax - dmin), rhs = kEdgeMsaaDepthThreshold * fabsf((dmax + dmin) * 0.5f), margin = 4e-6f * fmaxf(fabsf(dmax), fabsf(dmin));
-        if (lhs > rhs + margin) return true;
-        if (lhs < rhs - margin) return false;     // (a NaN falls through to the strict form)
-    }
-    return edge_mask_depth_msaa(inv_proj, k4, pcx, pcy, W, H);
-}
-
-// standard.wgsl:17-33 operation by operation (IEEE divisions, no contraction: this function sits in the STRICT part of the file): the world position exactly
-// as the oracle forms it.  Used by the experiment AWSM_STRICT_POSITION only (tests/diagnostics/abs_bar_survey.py: which pixels over the absolute colour bar
-// come from the position's last bits) — the shipped kernels compose pixel -> view on the host (FrameDev.pix2view).
-AWSM_DI f3 strict_world_position(const m4& inv_proj, const m4& inv_view, int cx, int cy, float W, float H, float depth) {
-    const float uvx = ((float)cx + 0.5f) / W, uvy = ((float)cy + 0.5f) / H;
-    const f4 view_h = mul(inv_proj, mk4(uvx * 2.0f - 1.0f, 1.0f - uvy * 2.0f, depth, 1.0f));
-    const float vw = fmaxf(view_h.w, 1e-8f);
-    const f4 wp = mul(inv_view, mk4(view_h.x / vw, view_h.y / vw, view_h.z / vw, 1.0f));
-    return {wp.x, wp.y, wp.z};
-}
-
-// ================================================================================================
-// RELAXED section: everything downstream of the quantised G-buffer values only has to stay within 1e-4 of the
-// oracle (BASELINE.json north_star), so it may contract to FMA and use the hardware reciprocal / rsqrt / exp2 /
-// log2 / sin / cos units (each ~1 ulp).  Helpers are re-defined here under contract(fast); the strict ones in
-// device_math.hpp keep their own flags even when inlined.
-// ================================================================================================
+// The STRICT G-buffer reconstruction and the MSAA edge predicates: shade_gbuffer.hpp.  RELAXED from here to the pragma above k_brdf_lut — its rules, fm::,
+// the 2D-array samplers, the attribute context, the BRDF terms and the BRDF-LUT sampler: shade_samplers.hpp.
 #pragma clang fp contract(fast)
-namespace fm {
-AWSM_DI float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-AWSM_DI float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
-AWSM_DI float fdiv(float a, float b) { return a * rcp(b); }
-AWSM_DI float fdot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-AWSM_DI f3 fnormalize(f3 a) { return a * rsq(fdot(a, a)); }
-AWSM_DI f3 fsafe_normalize(f3 n) { const float l = fdot(n, n); return l > 0.0f ? n * rsq(l) : mk3(0.0f, 0.0f, 1.0f); }
-AWSM_DI float pow5(float x) { const float x2 = x * x; return x2 * x2 * x; }
-AWSM_DI float powp(float x, float y) { return x > 0.0f ? __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)) : (x == 0.0f ? (y == 0.0f ? 1.0f : 0.0f) : __builtin_nanf("")); }
-AWSM_DI f4 fmul(const m4& m, f4 v) {
-    return {m.c[0].x * v.x + m.c[1].x * v.y + m.c[2].x * v.z + m.c[3].x * v.w, m.c[0].y * v.x + m.c[1].y * v.y + m.c[2].y * v.z + m.c[3].y * v.w,
-            m.c[0].z * v.x + m.c[1].z * v.y + m.c[2].z * v.z + m.c[3].z * v.w, m.c[0].w * v.x + m.c[1].w * v.y + m.c[2].w * v.z + m.c[3].w * v.w};
-}
-AWSM_DI f3 fdecode_octahedral(f2 e) {         // math.wgsl:55-67
-    const float fx = e.x * 2.0f - 1.0f, fy = e.y * 2.0f - 1.0f;
-    f3 n = {fx, fy, (1.0f - fabsf(fx)) - fabsf(fy)};
-    const float t = clampf(-n.z, 0.0f, 1.0f);
-    n.x += (n.x >= 0.0f) ? -t : t;
-    n.y += (n.y >= 0.0f) ? -t : t;
-    return fnormalize(n);
-}
-AWSM_DI TBN funpack_normal_tangent(f4 rgba) {  // math.wgsl:104-116
-    TBN r;
-    r.N = fdecode_octahedral({rgba.x, rgba.y});
-    const float theta = rgba.z * kTau - kPi;
-    const float s = (rgba.w >= 0.5f) ? 1.0f : -1.0f;
-    f3 tt, tb;
-    if (r.N.z < -0.98f) {
-        // canonical_tb (math.wgsl:73-84) divides by 1 + N.z: towards N = (0, 0, -1) a one-ulp difference in the decoded normal moves the basis
-        // by 6e-8 / (1 + N.z) — percent of a radian in the last degrees — so there the normal and the basis are computed with the oracle's
-        // operations (IEEE division and square root, no contraction; decode_octahedral / canonical_tb of the STRICT section).  Found by
-        // rendering from random viewpoints (tests/diagnostics/viewpoint_survey.py): surfaces facing -z were off by up to 6e-2 in single pixels.
-        r.N = decode_octahedral({rgba.x, rgba.y});
-        const TB cb = canonical_tb(r.N);
-        tt = cb.t; tb = cb.b;
-    } else {
-        const float a = rcp(1.0f + r.N.z), bb = (-r.N.x * r.N.y) * a;
-        tt = {1.0f - (r.N.x * r.N.x) * a, bb, -r.N.x};
-        tb = {bb, 1.0f - (r.N.y * r.N.y) * a, -r.N.y};
-    }
-    const float c = __ocml_native_cos_f32(theta), sn = __ocml_native_sin_f32(theta);
-    r.T = fnormalize(tt * c + tb * sn);
-    r.B = fnormalize(cross(r.N, r.T)) * s;
-    return r;
-}
 
-}  // namespace fm
-
-// ---------------- textures.wgsl ----------------
-struct TexInfo {
-    bool exists;
-    uint32_t array_index, layer_index, uv_set_index, sampler_index, uv_transform_index;
-};
-AWSM_DI TexInfo tex_load(const uint32_t* __restrict__ m, uint32_t i) {      // textures.wgsl:75-114
-    TexInfo t;
-    const uint32_t array_and_layer = m[i + 1], uv_and_sampler = m[i + 2], extra = m[i + 3], transform_offset = m[i + 4];
-    t.array_index = array_and_layer & 0xFFFu; t.layer_index = array_and_layer >> 12;
-    t.uv_set_index = uv_and_sampler & 0xFFu; t.sampler_index = uv_and_sampler >> 8;
-    t.exists = (extra & 1u) != 0u;
-    t.uv_transform_index = transform_offset / 32u;
-    return t;
-}
-
-// exact integer wrap without an integer divide: power-of-two sizes use masks, other sizes a float quotient + fix-up
-AWSM_DI int mod_floor(int i, int n) {
-    if ((n & (n - 1)) == 0) return i & (n - 1);
-    int r = i - (int)floorf((float)i * fm::rcp((float)n)) * n;
-    if (r < 0) r += n;
-    if (r >= n) r -= n;
-    return r;
-}
-AWSM_DI int wrap_index(int i, int n, uint32_t mode) {
-    if (mode == 1u) return mod_floor(i, n);
-    if (mode == 2u) { const int m = mod_floor(i, 2 * n); return m < n ? m : 2 * n - 1 - m; }
-    return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-}
-AWSM_DI f4 texel_rgba8(const uint8_t* __restrict__ p) {
-    const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-    const float k = 1.0f / 255.0f;
-    return {(float)(u & 255u) * k, (float)((u >> 8) & 255u) * k, (float)((u >> 16) & 255u) * k, (float)(u >> 24) * k};
-}
-AWSM_DI float safe_floor(float x, float& frac) {
-    const float fl = floorf(x);
-    if (!(fl >= -1073741824.0f && fl <= 1073741824.0f)) { frac = 0.0f; return 0.0f; }
-    frac = x - fl;
-    return fl;
-}
-AWSM_DI f4 lerp4(f4 a, f4 b, float t) { const float s = 1.0f - t; return {a.x * s + b.x * t, a.y * s + b.y * t, a.z * s + b.z * t, a.w * s + b.w * t}; }
-// textureSampleLevel(tex, sampler, uv, layer, level) on one level of one layer: DESIGN.md §"Texture sampling".  General
-// form: any size, any address mode, nearest or linear.  Out of line (one copy for all call sites); the hot path below
-// handles the common sampler inline and only falls back here when some lane of the wavefront needs it.
-__device__ __attribute__((noinline)) f4 sample_level_generic(const uint8_t* base, uint32_t width, uint32_t height, uint32_t mode_u, uint32_t mode_v,
-                                                             uint32_t linear, float u, float v) {
-    const int W = (int)width, H = (int)height;
-    float fx, fy;
-    if (linear == 0u) {
-        const int i = wrap_index((int)safe_floor(u * (float)W, fx), W, mode_u);
-        const int j = wrap_index((int)safe_floor(v * (float)H, fy), H, mode_v);
-        return texel_rgba8(base + ((size_t)j * W + i) * 4u);
-    }
-    const float x0f = safe_floor(u * (float)W - 0.5f, fx);
-    const float y0f = safe_floor(v * (float)H - 0.5f, fy);
-    const int i0 = wrap_index((int)x0f, W, mode_u), i1 = wrap_index((int)x0f + 1, W, mode_u);
-    const int j0 = wrap_index((int)y0f, H, mode_v), j1 = wrap_index((int)y0f + 1, H, mode_v);
-    const uint8_t* r0 = base + (size_t)j0 * W * 4u;
-    const uint8_t* r1 = base + (size_t)j1 * W * 4u;
-    const f4 c00 = texel_rgba8(r0 + i0 * 4), c10 = texel_rgba8(r0 + i1 * 4), c01 = texel_rgba8(r1 + i0 * 4), c11 = texel_rgba8(r1 + i1 * 4);
-    return lerp4(lerp4(c00, c10, fx), lerp4(c01, c11, fx), fy);
-}
-// The common sampler (linear, repeat/repeat, power-of-two extent) inline: wrap is a mask, no mode selects, no quotients,
-// the two taps of a row in one 8-byte load.
-AWSM_DI f4 sample_level_fast(const uint32_t* base, uint32_t W, uint32_t H, float u, float v) {
-    float fx, fy;
-    const float x0f = safe_floor(u * (float)W - 0.5f, fx);
-    const float y0f = safe_floor(v * (float)H - 0.5f, fy);
-    const uint32_t xi = (uint32_t)(int)x0f, yi = (uint32_t)(int)y0f;
-    const uint32_t i0 = xi & (W - 1u), i1 = (xi + 1u) & (W - 1u);
-    const uint32_t r0 = (yi & (H - 1u)) * W, r1 = ((yi + 1u) & (H - 1u)) * W;
-    uint32_t t00, t10, t01, t11;
-    if (i1 == i0 + 1u) {   // neighbours in memory unless the footprint wraps
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2), aligned(4)));
-        const u32x2 p0 = *reinterpret_cast<const u32x2*>(base + r0 + i0), p1 = *reinterpret_cast<const u32x2*>(base + r1 + i0);
-        t00 = p0.x; t10 = p0.y; t01 = p1.x; t11 = p1.y;
-    } else {
-        t00 = base[r0 + i0]; t10 = base[r0 + i1]; t01 = base[r1 + i0]; t11 = base[r1 + i1];
-    }
-    // bilinear on the raw 0..255 values, one scale by 1/255 at the end
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
-    const float k = 1.0f / 255.0f;
-    f4 r;
-    r.x = ((float)(t00 & 255u) * w00 + (float)(t10 & 255u) * w10 + (float)(t01 & 255u) * w01 + (float)(t11 & 255u) * w11) * k;
-    r.y = ((float)((t00 >> 8) & 255u) * w00 + (float)((t10 >> 8) & 255u) * w10 + (float)((t01 >> 8) & 255u) * w01 + (float)((t11 >> 8) & 255u) * w11) * k;
-    r.z = ((float)((t00 >> 16) & 255u) * w00 + (float)((t10 >> 16) & 255u) * w10 + (float)((t01 >> 16) & 255u) * w01 + (float)((t11 >> 16) & 255u) * w11) * k;
-    r.w = ((float)(t00 >> 24) * w00 + (float)(t10 >> 24) * w10 + (float)(t01 >> 24) * w01 + (float)(t11 >> 24) * w11) * k;
-    return r;
-}
-
-// textureSampleGrad's footprint.  WebGPU leaves level selection and anisotropy to the implementation; the contract here:
-//   * max_anisotropy 1 (or a context without AWSM_CFG_ANISOTROPIC — the default, the rule the reference itself documents as "mimics the hardware mip
-//     selection", helpers/mipmap.wgsl:419-439): rho = max(|ddx * size|, |ddy * size|), lod = log2(max(rho, 1e-6));
-//   * max_anisotropy A > 1 (gltf samplers ask for 16, gltf/populate/material.rs:892-902): N = clamp(rho_max / rho_min, 1, A) — a real number — the
-//     level is chosen for rho_max / N, and the footprint is covered by probes along the major axis at t_j = j / N, j = -m..m, m = ceil((N - 1) / 2),
-//     each weighted by the part of [-1/2, 1/2] its cell [t_j - 1/2N, t_j + 1/2N] covers (a box filter of the footprint's length sampled at the chosen
-//     level's spacing), normalised.  Continuous in N — a probe enters with weight zero — so two implementations that disagree in the last bit of a
-//     gradient agree in the colour; N = 1 is the isotropic rule bit for bit.
-struct GradFootprint { float lod, n, major_u, major_v; int m; };
-AWSM_DI GradFootprint grad_footprint(float dxu, float dxv, float dyu, float dyv, float W, float H, uint32_t max_aniso) {
-    const float ax = dxu * W, ay = dxv * H, bx = dyu * W, by = dyv * H;
-    const float rx2 = ax * ax + ay * ay, ry2 = bx * bx + by * by;
-    const float r2max = fmaxf(rx2, ry2);
-    GradFootprint fp;
-    fp.lod = 0.5f * __builtin_amdgcn_logf(fmaxf(r2max, 1e-12f));      // log2(max(rho, 1e-6))
-    fp.n = 1.0f; fp.major_u = 0.0f; fp.major_v = 0.0f; fp.m = 0;
-    if (max_aniso > 1u && r2max > 0.0f) {
-        const float r2min = fminf(rx2, ry2), A = (float)min(max_aniso, 16u);
-        float nf = r2min * (A * A) <= r2max ? A : __builtin_sqrtf(r2max / r2min);
-        nf = fminf(fmaxf(nf, 1.0f), A);
-        if (nf > 1.0f) {
-            fp.n = nf;
-            fp.lod = fp.lod - __builtin_amdgcn_logf(nf);
-            fp.m = (int)ceilf((nf - 1.0f) * 0.5f);
-            const bool xmajor = rx2 >= ry2;
-            fp.major_u = xmajor ? dxu : dyu; fp.major_v = xmajor ? dxv : dyv;
-        }
-    }
-    return fp;
-}
-
-// grad_footprint's probes: 2 m + 1 trilinear samples along the major axis, weighted and normalised.  levels_modes: lo | hi << 8 | address mode u << 16 |
-// v << 18 | linear << 20.  Out of line, per lane: only pixels with an anisotropic footprint on an AWSM_CFG_ANISOTROPIC context come here.
-__device__ __attribute__((noinline)) f4 sample_probes(const uint32_t* texels, const uint32_t* level_off, uint32_t W, uint32_t H, uint32_t layer, uint32_t levels_modes, float f,
-                                                      float u, float v, float major_u, float major_v, float nf, int m) {
-    const uint32_t lo = levels_modes & 255u, hi = (levels_modes >> 8) & 255u, mode_u = (levels_modes >> 16) & 3u, mode_v = (levels_modes >> 18) & 3u, linear = (levels_modes >> 20) & 1u;
-    const float inv_n = 1.0f / nf;
-    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    float wsum = 0.0f;
-    const int n = f > 0.0f ? 2 : 1;
-    for (int j = -m; j <= m; j++) {
-        const float t = (float)j * inv_n, wp = saturate((0.5f - fabsf(t)) * nf + 0.5f);
-        const float pu = u + major_u * t, pv = v + major_v * t;
-        for (int k = 0; k < n; k++) {
-            const uint32_t level = k ? hi : lo;
-            const float w = (k ? f : 1.0f - f) * wp;
-            const uint32_t Wl = max(W >> level, 1u), Hl = max(H >> level, 1u);
-            const uint32_t* base = texels + level_off[level] + (size_t)layer * Wl * Hl;
-            const f4 c = sample_level_generic(reinterpret_cast<const uint8_t*>(base), Wl, Hl, mode_u, mode_v, linear, pu, pv);
-            acc = {acc.x + c.x * w, acc.y + c.y * w, acc.z + c.z * w, acc.w + c.w * w};
-        }
-        wsum += wp;
-    }
-    const float iw = 1.0f / wsum;
-    return {acc.x * iw, acc.y * iw, acc.z * iw, acc.w * iw};
-}
-
-// ---------------- per-pixel attribute context ----------------
-struct Attr {
-    const DevScene* sc;
-    const float* ad;          // attribute_data (f32 view)
-    uint32_t v0, v1, v2;      // vertex_start of the three corners (floats)
-    uint32_t uv_sets_index;
-    f3 bary;
-    f2 uv0;                   // interpolated TEXCOORD_0, computed once per pixel when a core texture uses it
-    bool has_uv0;
-    f4 bary_derivs;           // MipmapMode::Gradient: the RGBA16F barycentric_derivatives texel (db0/dx, db0/dy, db1/dx, db1/dy)
-    f2 duv0_dx, duv0_dy;      // ... and d(TEXCOORD_0)/d(screen), alongside uv0
-};
-// texture_uvs.wgsl:64-84 (+ helpers/mipmap.wgsl:113-205 get_uv_derivatives when GRAD: chain rule over the vertex UVs)
-template <int GRAD>
-AWSM_DI f2 attr_uv(const Attr& a, uint32_t set, f2& ddx, f2& ddy) {
-    const uint32_t o = a.uv_sets_index + set * 2u;
-    const float x0 = a.ad[a.v0 + o], y0 = a.ad[a.v0 + o + 1], x1 = a.ad[a.v1 + o], y1 = a.ad[a.v1 + o + 1];
-    const float x2 = a.ad[a.v2 + o], y2 = a.ad[a.v2 + o + 1];
-    if (GRAD) {
-        const float dAlphaDx = a.bary_derivs.x, dAlphaDy = a.bary_derivs.y, dBetaDx = a.bary_derivs.z, dBetaDy = a.bary_derivs.w;
-        const float dGammaDx = -dAlphaDx - dBetaDx, dGammaDy = -dAlphaDy - dBetaDy;
-        ddx = {x0 * dAlphaDx + x1 * dBetaDx + x2 * dGammaDx, y0 * dAlphaDx + y1 * dBetaDx + y2 * dGammaDx};
-        ddy = {x0 * dAlphaDy + x1 * dBetaDy + x2 * dGammaDy, y0 * dAlphaDy + y1 * dBetaDy + y2 * dGammaDy};
-        const bool tiny = (fabsf(dAlphaDx) + fabsf(dAlphaDy) + fabsf(dBetaDx) + fabsf(dBetaDy)) < 1e-20f;
-        const bool ok = (ddx.x == ddx.x) && (ddx.y == ddx.y) && (ddy.x == ddy.x) && (ddy.y == ddy.y);   // NaN guard
-        if (tiny || !ok) { ddx = {0.0f, 0.0f}; ddy = {0.0f, 0.0f}; }
-    }
-    return {interp3_strict(a.bary.x, a.bary.y, a.bary.z, x0, x1, x2), interp3_strict(a.bary.x, a.bary.y, a.bary.z, y0, y1, y2)};
-}
-// texture_uvs.wgsl:64-187 + textures.wgsl:131-150.  GRAD = MipmapMode::Gradient: textureSampleGrad by the contract the
-// reference documents as "mimics the hardware mip selection" (helpers/mipmap.wgsl:419-439): rho = max(|ddx*size|, |ddy*size|),
-// lod = log2(max(rho, 1e-6)) clamped to the chain; magnification -> mag filter on level 0; otherwise min filter on
-// floor(lod) and floor(lod)+1 blended by the fraction (mipmap filter linear) or round(lod) (nearest).  Isotropic.
-template <int GRAD>
-AWSM_DI f4 sample_tex(const Attr& a, const TexInfo& t) {
-    f2 uv = a.uv0, ddx = a.duv0_dx, ddy = a.duv0_dy;
-    if (!(a.has_uv0 && t.uv_set_index == 0u)) uv = attr_uv<GRAD>(a, t.uv_set_index, ddx, ddy);
-    const float* tt = reinterpret_cast<const float*>(a.sc->buf[AWSM_BUF_TEXTURE_TRANSFORMS] + (size_t)t.uv_transform_index * 32u);
-    const float u = affine2_strict(tt[0], tt[1], tt[4], uv.x, uv.y), v = affine2_strict(tt[2], tt[3], tt[5], uv.x, uv.y);
-    if (t.array_index >= a.sc->n_tex || t.sampler_index >= a.sc->n_samplers) return {0.0f, 0.0f, 0.0f, 0.0f};
-    const TexArrayDev& arr = a.sc->tex[t.array_index];
-    const AwsmSampler& smp = a.sc->samplers[t.sampler_index];
-    const uint32_t W = arr.width, H = arr.height, layers = arr.layers;
-    const uint8_t* texels = arr.texels;
-    if (texels == nullptr || W == 0u || H == 0u || layers == 0u) return {0.0f, 0.0f, 0.0f, 0.0f};
-    const uint32_t layer = min(t.layer_index, layers - 1u);
-    const bool common = smp.address_mode_u == 1u && smp.address_mode_v == 1u && (W & (W - 1u)) == 0u && (H & (H - 1u)) == 0u;
-    if (!GRAD) {
-        // Hot path taken when ALL lanes of the wavefront qualify (one scalar branch)
-        const bool fast = common && smp.mag_filter != 0u;
-        if (__builtin_amdgcn_ballot_w64(!fast) != 0ull)
-            return sample_level_generic(texels + (size_t)layer * W * H * 4u, W, H, smp.address_mode_u, smp.address_mode_v, smp.mag_filter, u, v);
-        return sample_level_fast(reinterpret_cast<const uint32_t*>(texels) + (size_t)layer * W * H, W, H, u, v);
-    }
-    // ---- level selection ----
-    const float dxu = tt[0] * ddx.x + tt[1] * ddx.y, dxv = tt[2] * ddx.x + tt[3] * ddx.y;     // texture_uvs.wgsl:27-35
-    const float dyu = tt[0] * ddy.x + tt[1] * ddy.y, dyv = tt[2] * ddy.x + tt[3] * ddy.y;
-    GradFootprint fp = grad_footprint(dxu, dxv, dyu, dyv, (float)W, (float)H, (GRAD == 2 && smp.mag_filter != 0u && smp.min_filter != 0u && smp.mipmap_filter != 0u) ? smp.max_anisotropy : 1u);
-    const uint32_t levels = max(arr.mips, 1u);
-    uint32_t lo = 0u, hi = 0u, linear = smp.mag_filter;
-    float f = 0.0f;
-    if (fp.lod > 0.0f && levels > 1u) {
-        const float lod = fminf(fp.lod, (float)(levels - 1u));
-        linear = smp.min_filter;
-        if (smp.mipmap_filter == 0u) { lo = hi = (uint32_t)floorf(lod + 0.5f); }
-        else { const float fl = floorf(lod); lo = (uint32_t)fl; hi = min(lo + 1u, levels - 1u); f = (hi != lo) ? lod - fl : 0.0f; }
-    }
-    const bool fast = common && linear != 0u;
-    const bool all_fast = __builtin_amdgcn_ballot_w64(!fast) == 0ull;
-    if (GRAD == 2 && fp.m > 0)      // anisotropic footprint on a context that honours max_anisotropy (the kernels' <2> instantiations): the probes, out of line
-        return sample_probes(reinterpret_cast<const uint32_t*>(texels), arr.level_off, W, H, layer, lo | (hi << 8) | (smp.address_mode_u << 16) | (smp.address_mode_v << 18) | (linear << 20), f, u, v, fp.major_u, fp.major_v, fp.n, fp.m);
-    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int n = f > 0.0f ? 2 : 1;
-    for (int k = 0; k < n; k++) {            // not unrolled: one copy of the samplers per call site
-        const uint32_t level = k ? hi : lo;
-        const float w = k ? f : 1.0f - f;
-        const uint32_t Wl = max(W >> level, 1u), Hl = max(H >> level, 1u);
-        const uint32_t* base = reinterpret_cast<const uint32_t*>(texels) + arr.level_off[level] + (size_t)layer * Wl * Hl;
-        const f4 c = all_fast ? sample_level_fast(base, Wl, Hl, u, v)
-                              : sample_level_generic(reinterpret_cast<const uint8_t*>(base), Wl, Hl, smp.address_mode_u, smp.address_mode_v, linear, u, v);
-        acc = {acc.x + c.x * w, acc.y + c.y * w, acc.z + c.z * w, acc.w + c.w * w};
-    }
-    return acc;
-}
-// A core texture through its per-draw slot.  MipmapMode::None: the fast path needs nothing but the slot; any other sampler / size falls
-// back to the general route through the material words.  MipmapMode::Gradient: level selection as sample_tex<true>, with the array's
-// layout and the sampler's modes taken from the slot.
-template <int GRAD>
-AWSM_DI f4 sample_slot(const Attr& a, const TexSlotDev* __restrict__ slot, const uint32_t* __restrict__ M, uint32_t word) {
-    const uint4* q = reinterpret_cast<const uint4*>(slot);
-    const uint4 q0 = q[0], q1 = q[1], q2 = q[2];        // base lo/hi, width, height | flags, tt0, tt1, tt2 | tt3, tt4, tt5, layer_levels
-    const uint32_t flags = q1.x;
-    const uint32_t uv_set = flags >> 24;
-    const float t0 = __uint_as_float(q1.y), t1 = __uint_as_float(q1.z), t2 = __uint_as_float(q1.w), t3 = __uint_as_float(q2.x), t4 = __uint_as_float(q2.y), t5 = __uint_as_float(q2.z);
-    if (!GRAD) {
-        if (__builtin_amdgcn_ballot_w64((flags & 6u) != 2u) != 0ull) {       // some lane is not on the fast path
-            if (flags & 4u) return {0.0f, 0.0f, 0.0f, 0.0f};
-            return sample_tex<false>(a, tex_load(M, word));
-        }
-        f2 uv = a.uv0, ddx, ddy;
-        if (!(a.has_uv0 && uv_set == 0u)) uv = attr_uv<false>(a, uv_set, ddx, ddy);
-        const float u = affine2_strict(t0, t1, t4, uv.x, uv.y), v = affine2_strict(t2, t3, t5, uv.x, uv.y);
-        const uint32_t* base = reinterpret_cast<const uint32_t*>(((unsigned long long)q0.y << 32) | q0.x);
-        return sample_level_fast(base, q0.z, q0.w, u, v);
-    }
-    if (flags & 4u) return {0.0f, 0.0f, 0.0f, 0.0f};
-    f2 uv = a.uv0, ddx = a.duv0_dx, ddy = a.duv0_dy;
-    if (!(a.has_uv0 && uv_set == 0u)) uv = attr_uv<GRAD>(a, uv_set, ddx, ddy);
-    const float u = affine2_strict(t0, t1, t4, uv.x, uv.y), v = affine2_strict(t2, t3, t5, uv.x, uv.y);
-    const uint4 q3 = q[3];                              // level_off pointer, array base
-    const uint32_t* level_off = reinterpret_cast<const uint32_t*>(((unsigned long long)q3.y << 32) | q3.x);
-    const uint32_t* texels = reinterpret_cast<const uint32_t*>(((unsigned long long)q3.w << 32) | q3.z);
-    const uint32_t W = q0.z, H = q0.w, layer = q2.w & 0xFFFFu, levels = q2.w >> 24;
-    const uint32_t mode_u = (flags >> 13) & 3u, mode_v = (flags >> 21) & 3u;
-    // ---- level selection (texture_uvs.wgsl:27-35 + the LOD contract, grad_footprint) ----
-    const float dxu = t0 * ddx.x + t1 * ddx.y, dxv = t2 * ddx.x + t3 * ddx.y;
-    const float dyu = t0 * ddy.x + t1 * ddy.y, dyv = t2 * ddy.x + t3 * ddy.y;
-    GradFootprint fp = grad_footprint(dxu, dxv, dyu, dyv, (float)W, (float)H, GRAD == 2 ? max((q2.w >> 16) & 31u, 1u) : 1u);
-    uint32_t lo = 0u, hi = 0u, linear = (flags >> 4) & 1u;
-    float f = 0.0f;
-    if (fp.lod > 0.0f && levels > 1u) {
-        const float lod = fminf(fp.lod, (float)(levels - 1u));
-        linear = (flags >> 5) & 1u;
-        if (!(flags & 64u)) { lo = hi = (uint32_t)floorf(lod + 0.5f); }
-        else { const float fl = floorf(lod); lo = (uint32_t)fl; hi = min(lo + 1u, levels - 1u); f = (hi != lo) ? lod - fl : 0.0f; }
-    }
-    const bool fast = (flags & 8u) != 0u && linear != 0u;
-    const bool all_fast = __builtin_amdgcn_ballot_w64(!fast) == 0ull;
-    if (GRAD == 2 && fp.m > 0) return sample_probes(texels, level_off, W, H, layer, lo | (hi << 8) | (mode_u << 16) | (mode_v << 18) | (linear << 20), f, u, v, fp.major_u, fp.major_v, fp.n, fp.m);
-    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int n = f > 0.0f ? 2 : 1;
-    for (int k = 0; k < n; k++) {            // not unrolled: one copy of the samplers per call site
-        const uint32_t level = k ? hi : lo;
-        const float w = k ? f : 1.0f - f;
-        const uint32_t Wl = max(W >> level, 1u), Hl = max(H >> level, 1u);
-        const uint32_t* base = texels + level_off[level] + (size_t)layer * Wl * Hl;
-        const f4 c = all_fast ? sample_level_fast(base, Wl, Hl, u, v)
-                              : sample_level_generic(reinterpret_cast<const uint8_t*>(base), Wl, Hl, mode_u, mode_v, linear, u, v);
-        acc = {acc.x + c.x * w, acc.y + c.y * w, acc.z + c.z * w, acc.w + c.w * w};
-    }
-    return acc;
-}
-
-AWSM_DI f4 vertex_color(const Attr& a, uint32_t set_index) {               // vertex_color_attrib.wgsl:1-21
-    const uint32_t o = set_index * 4u;
-    float r[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) r[j] = a.bary.x * a.ad[a.v0 + o + j] + a.bary.y * a.ad[a.v1 + o + j] + a.bary.z * a.ad[a.v2 + o + j];
-    return {r[0], r[1], r[2], r[3]};
-}
-
-AWSM_DI float mf(const uint32_t* __restrict__ m, uint32_t i) { return __uint_as_float(m[i]); }
-AWSM_DI uint32_t abs_index(uint32_t base, uint32_t rel) { return rel != 0u ? base + rel : 0u; }
-
-// pbr_material_color.wgsl:4-32
-struct PbrColor {
-    f3 base; f2 mr; f3 normal; float occlusion; f3 emissive;
-    float specular; f3 specular_color; float ior; float transmission;
-    float volume_thickness, volume_attenuation_distance; f3 volume_attenuation_color;
-    float clearcoat, clearcoat_roughness; f3 clearcoat_normal;
-    f3 sheen_color; float sheen_roughness;
-};
-
-template <int GRAD>
-AWSM_DI f3 normal_map(const Attr& a, const TexInfo& t, float scale, const TBN& tbn) {   // material_color_calc.wgsl:301-322
-    if (!t.exists) return tbn.N;
-    const f4 s = sample_tex<GRAD>(a, t);
-    const float tx = (s.x * 2.0f - 1.0f) * scale, ty = (s.y * 2.0f - 1.0f) * scale, tz = s.z * 2.0f - 1.0f;
-    return fm::fnormalize(tbn.T * tx + tbn.B * ty + tbn.N * tz);
-}
-
-// ---------------- brdf.wgsl ----------------
-AWSM_DI float ior_to_f0(float ior) { const float v = ior < 1.0f ? 1.5f : ior; const float r = fm::fdiv(v - 1.0f, v + 1.0f); return r * r; }
-AWSM_DI f3 volume_attenuation(float distance, f3 color, float att_distance) {           // brdf.wgsl:55-74
-    if (distance <= 0.0f) return splat3(1.0f);
-    if (att_distance <= 0.0f || att_distance > 1e10f) return splat3(1.0f);
-    if (color.x >= 0.999f && color.y >= 0.999f && color.z >= 0.999f) return splat3(1.0f);
-    const float e = fm::fdiv(distance, att_distance);
-    return {fm::powp(color.x, e), fm::powp(color.y, e), fm::powp(color.z, e)};
-}
-AWSM_DI bool should_apply_volume_attenuation(float thickness, float att_distance, f3 c) {
-    return thickness > 0.0f && att_distance < 1e10f && (c.x < 1.0f || c.y < 1.0f || c.z < 1.0f);
-}
-AWSM_DI f3 fresnel_schlick_f90(float cos_theta, f3 F0, float f90) {                      // brdf.wgsl:111-115
-    const float p = fm::pow5(1.0f - saturate(cos_theta));
-    return {F0.x + (f90 - F0.x) * p, F0.y + (f90 - F0.y) * p, F0.z + (f90 - F0.z) * p};
-}
-AWSM_DI float fresnel_schlick_scalar(float cos_theta, float F0) { return F0 + (1.0f - F0) * fm::pow5(1.0f - saturate(cos_theta)); }
-AWSM_DI float distribution_ggx(float n_dot_h, float alpha) {                             // brdf.wgsl:118-124
-    const float a = fmaxf(alpha, 0.001f);
-    const float a2 = a * a;
-    const float ndh = saturate(n_dot_h);
-    const float d = (ndh * ndh) * (a2 - 1.0f) + 1.0f;
-    return fm::fdiv(a2, (kPi * d) * d + kEps);
-}
-AWSM_DI float geometry_schlick_ggx(float n_dot_x, float alpha) {                         // brdf.wgsl:127-132
-    const float a = fmaxf(alpha, 0.001f);
-    const float k = ((a + 1.0f) * (a + 1.0f)) * 0.125f;
-    const float ndx = saturate(n_dot_x);
-    return fm::fdiv(ndx, ndx * (1.0f - k) + k);
-}
-constexpr float kClearcoatF0 = 0.04f;
-AWSM_DI float clearcoat_fresnel(float clearcoat, float v_dot_h) { return clearcoat <= 0.0f ? 0.0f : clearcoat * fresnel_schlick_scalar(v_dot_h, kClearcoatF0); }
-AWSM_DI float sheen_albedo_scaling(f3 sheen_color, float sheen_roughness, float n_dot_v) {   // brdf.wgsl:245-262
-    const float sheen_max = fmaxf(fmaxf(sheen_color.x, sheen_color.y), sheen_color.z);
-    if (sheen_max <= 0.0f) return 1.0f;
-    const float alpha = sheen_roughness * sheen_roughness;
-    return 1.0f - sheen_max * (alpha * (0.18f + 0.06f * (1.0f - n_dot_v)));
-}
-// brdf.wgsl:293-302 — linear, clamp-to-edge, RG of the RGBA16F LUT
-AWSM_DI f2 sample_brdf_lut(const DevScene* sc, float n_dot_v, float roughness) {
-    const float u = saturate(n_dot_v), v = saturate(roughness);
-    const int W = (int)sc->lut_w, H = (int)sc->lut_h;
-    float fx, fy;
-    const float x0f = safe_floor(u * (float)W - 0.5f, fx);
-    const float y0f = safe_floor(v * (float)H - 0.5f, fy);
-    const int i0 = wrap_index((int)x0f, W, 0u), i1 = wrap_index((int)x0f + 1, W, 0u);
-    const int j0 = wrap_index((int)y0f, H, 0u), j1 = wrap_index((int)y0f + 1, H, 0u);
-    const uint32_t* L = reinterpret_cast<const uint32_t*>(sc->lut_rg16f);   // one u32 = (r16, g16)
-    const uint32_t t00 = L[(size_t)j0 * W + i0], t10 = L[(size_t)j0 * W + i1], t01 = L[(size_t)j1 * W + i0], t11 = L[(size_t)j1 * W + i1];
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    const float r_top = f16_bits_to_f32((unsigned short)(t00 & 0xFFFFu)) * gx + f16_bits_to_f32((unsigned short)(t10 & 0xFFFFu)) * fx;
-    const float r_bot = f16_bits_to_f32((unsigned short)(t01 & 0xFFFFu)) * gx + f16_bits_to_f32((unsigned short)(t11 & 0xFFFFu)) * fx;
-    const float g_top = f16_bits_to_f32((unsigned short)(t00 >> 16)) * gx + f16_bits_to_f32((unsigned short)(t10 >> 16)) * fx;
-    const float g_bot = f16_bits_to_f32((unsigned short)(t01 >> 16)) * gx + f16_bits_to_f32((unsigned short)(t11 >> 16)) * fx;
-    return {r_top * gy + r_bot * fy, g_top * gy + g_bot * fy};
-}
-
-
-// ---------------- cubemaps: textureSampleLevel(texture_cube<f32>, linear / linear / linear sampler, direction, level) ----------------
-// (skybox.wgsl:37, brdf.wgsl:268-290).  Contract where WebGPU defers to the hardware: the major axis picks the face (z if |z| >= |x|,|y|,
-// else y if |y| >= |x|, else x — the Vulkan / D3D table, as are sc, tc below); bilinear on the level's N x N faces with texel
-// centres at (i + 0.5) / N; a tap that falls off the face comes from the face across that edge (seamless, kCubeEdge; a corner tap,
-// off in both directions, keeps its row); the level is clamped to the chain and the two nearest levels are blended by its fraction.
-// Continuous in the direction everywhere but at the eight corners, which is what lets a relaxed-arithmetic direction stay in tolerance.
-// kCubeEdge[face][edge: 0 left (i = -1), 1 right (i = N), 2 up (j = -1), 3 down (j = N)] = face' | swap << 3 | flip << 4 | far << 5:
-// the running coordinate k (j for left / right, i for up / down), reversed if flip, becomes j' (swap) or i'; the other one is N - 1 (far) or 0.
-__device__ const uint8_t kCubeEdge[6][4] = {{44, 13, 58, 43}, {45, 12, 10, 27}, {1, 16, 21, 4}, {49, 32, 36, 53}, {41, 8, 34, 3}, {40, 9, 18, 51}};
-AWSM_DI uint2 cube_texel_raw(const CubeDev& c, uint32_t level_base, int N, uint32_t face, int i, int j) {
-    if (i < 0 || i >= N) j = min(max(j, 0), N - 1);     // corner taps keep their row
-    if (i < 0 || i >= N || j < 0 || j >= N) {
-        const uint32_t e = i < 0 ? 0u : (i >= N ? 1u : (j < 0 ? 2u : 3u));
-        const uint32_t t = kCubeEdge[face][e];
-        int k = e < 2u ? j : i;
-        if (t & 16u) k = N - 1 - k;
-        const int far = (t & 32u) ? N - 1 : 0;
-        face = t & 7u;
-        if (t & 8u) { i = far; j = k; } else { i = k; j = far; }
-    }
-    return c.texels[level_base + ((size_t)face * (size_t)N + (size_t)j) * (size_t)N + (size_t)i];
-}
+// ---------------- cubemaps: the contract, the seam table kCubeEdge and the seam rule cube_texel_raw are in cube_seam.hpp (shared with kernels_env.hip) ----------------
 AWSM_DI f4 half4(uint2 h) { return {f16_bits_to_f32((unsigned short)(h.x & 0xFFFFu)), f16_bits_to_f32((unsigned short)(h.x >> 16)), f16_bits_to_f32((unsigned short)(h.y & 0xFFFFu)), f16_bits_to_f32((unsigned short)(h.y >> 16))}; }
 AWSM_DI f4 cube_texel(const CubeDev& c, uint32_t level_base, int N, uint32_t face, int i, int j) { return half4(cube_texel_raw(c, level_base, N, face, i, j)); }
 // CubeDev.bordered: one thread per texel of the aproned chain
@@ -3249,57 +2660,57 @@ extern "C" void awsm_launch_resolve_draws(const awsm::DevScene* sc, const awsm::
     if (f->n_draws) hipLaunchKernelGGL(awsm::k_resolve_draws, dim3((8u * f->n_draws + 255u) / 256u), dim3(256), 0, s, sc, *f);
 }
 // A kernel's instantiation by mip mode: 0 MipmapMode::None, 1 MipmapMode::Gradient, 2 Gradient on a context that honours max_anisotropy
-// (AWSM_CFG_ANISOTROPIC; separate instantiations: the probes cost the isotropic sampler registers it would pay for on every frame)
-#define AWSM_LAUNCH_G(g, K, grid, block, ...) do { if ((g) == 2) hipLaunchKernelGGL((K<2>), grid, block, 0, s, __VA_ARGS__); else if ((g) == 1) hipLaunchKernelGGL((K<1>), grid, block, 0, s, __VA_ARGS__); \
-                                                   else hipLaunchKernelGGL((K<0>), grid, block, 0, s, __VA_ARGS__); } while (0)
-#define AWSM_LAUNCH_G2(g, K, B, grid, block, ...) do { if ((g) == 2) hipLaunchKernelGGL((K<2, B>), grid, block, 0, s, __VA_ARGS__); else if ((g) == 1) hipLaunchKernelGGL((K<1, B>), grid, block, 0, s, __VA_ARGS__); \
-                                                       else hipLaunchKernelGGL((K<0, B>), grid, block, 0, s, __VA_ARGS__); } while (0)
-#define AWSM_LAUNCH_SG(g, K, S, grid, block, ...) do { if ((g) == 2) hipLaunchKernelGGL((K<S, 2>), grid, block, 0, s, __VA_ARGS__); else if ((g) == 1) hipLaunchKernelGGL((K<S, 1>), grid, block, 0, s, __VA_ARGS__); \
-                                                       else hipLaunchKernelGGL((K<S, 0>), grid, block, 0, s, __VA_ARGS__); } while (0)
-static inline int mip_mode(const awsm::FrameDev* f) { return f->mipmap ? (f->aniso ? 2 : 1) : 0; }
-extern "C" void awsm_launch_shade(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s) {
+// (AWSM_CFG_ANISOTROPIC; separate instantiations, as the reference keeps separate pipelines: the probes cost the isotropic sampler registers it
+// would pay for on every frame).  `launch` is called once, with std::integral_constant<int, mode>.
+template <typename Launch>
+static inline void by_mip_mode(const awsm::FrameDev* f, Launch&& launch) {
+    if (!f->mipmap) launch(std::integral_constant<int, 0>{});
+    else if (f->aniso) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 1>{});
+}
+// The pass's grid of 16x16 blocks as the kernels number it (shade_block, k_shade_lean): every XCD gets ceil(by_n / 8) block rows of ids and surplus
+// ids exit.  blocks: ids on the block pitch bx_n (0: nothing to shade); strip_blocks: on the lean kernel's power-of-two pitch.
+struct ShadeGrid { uint32_t blocks, strip_blocks; };
+static ShadeGrid shade_grid(const awsm::FrameDev* f) {
     const uint32_t bx_n = (f->width + 15u) >> 4, by_n = f->band_n > 1u ? 2u * f->tiles_y : ((f->sy1 - f->sy0) + 15u) >> 4;
-    const uint32_t nb = 8u * ((by_n + 7u) / 8u) * bx_n;   // every XCD gets ceil(by_n / 8) rows of ids; surplus ids exit
-    if (!nb) return;
-    const int g = mip_mode(f);      // MipmapMode::None / Gradient / Gradient + anisotropy: separate instantiations, as the reference keeps separate pipelines
-    const bool msaa = f->msaa == 4u;
-    if (awsm_shade_is_lean(f)) {
-        // the lean kernel over the screen (a wavefront per strip id on a power-of-two block pitch: the padding exits), then the general code for the
-        // wavefronts it declined (awsm_launch_shade_todo; k_deform_transform / k_resolve_draws reset the list)
-        uint32_t pitch = 1; while (pitch < bx_n) pitch <<= 1;
-        const uint32_t nb_ids = 8u * ((by_n + 7u) / 8u) * pitch;
-        if (msaa) {
-            if (g == 2) hipLaunchKernelGGL((awsm::k_shade_lean<false, 2, true>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-            else if (g == 1) hipLaunchKernelGGL((awsm::k_shade_lean<false, 1, true>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-            else hipLaunchKernelGGL((awsm::k_shade_lean<false, 0, true>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-        } else if (g == 2) hipLaunchKernelGGL((awsm::k_shade_lean<false, 2, false>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-        else if (g == 1) hipLaunchKernelGGL((awsm::k_shade_lean<false, 1, false>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-        else if (f->lean_grid && f->lean_next) hipLaunchKernelGGL((awsm::k_shade_lean<true, 0, false>), dim3(min(f->lean_grid, nb_ids)), dim3(256), 0, s, sc, *f);
-        else hipLaunchKernelGGL((awsm::k_shade_lean<false, 0, false>), dim3(nb_ids), dim3(256), 0, s, sc, *f);
-        return;
-    }
-    if (msaa) {
-        AWSM_LAUNCH_G(g, awsm::k_shade_msaa, dim3(nb), dim3(256), sc, *f);
-        AWSM_LAUNCH_G(g, awsm::k_shade_msaa_resolve, dim3(nb), dim3(64), sc, *f);
-    } else AWSM_LAUNCH_G(g, awsm::k_shade, dim3(nb), dim3(256), sc, *f);
+    uint32_t pitch = 1; while (pitch < bx_n) pitch <<= 1;
+    const uint32_t rows = 8u * ((by_n + 7u) / 8u);
+    return {rows * bx_n, rows * pitch};
+}
+extern "C" void awsm_launch_shade(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s) {
+    const ShadeGrid g = shade_grid(f);
+    if (!g.blocks) return;
+    const bool msaa = f->msaa == 4u, lean = awsm_shade_is_lean(f) != 0;
+    by_mip_mode(f, [&](auto mode) {
+        constexpr int G = decltype(mode)::value;
+        if (lean) {
+            // the lean kernel over the screen (a wavefront per strip id on a power-of-two block pitch: the padding exits), then the general code for the
+            // wavefronts it declined (awsm_launch_shade_todo; k_deform_transform / k_resolve_draws reset the list)
+            if (msaa) hipLaunchKernelGGL((awsm::k_shade_lean<false, G, true>), dim3(g.strip_blocks), dim3(256), 0, s, sc, *f);
+            else if (G == 0 && f->lean_grid && f->lean_next) hipLaunchKernelGGL((awsm::k_shade_lean<true, 0, false>), dim3(min(f->lean_grid, g.strip_blocks)), dim3(256), 0, s, sc, *f);
+            else hipLaunchKernelGGL((awsm::k_shade_lean<false, G, false>), dim3(g.strip_blocks), dim3(256), 0, s, sc, *f);
+        } else if (msaa) {
+            hipLaunchKernelGGL((awsm::k_shade_msaa<G>), dim3(g.blocks), dim3(256), 0, s, sc, *f);
+            hipLaunchKernelGGL((awsm::k_shade_msaa_resolve<G>), dim3(g.blocks), dim3(64), 0, s, sc, *f);
+        } else hipLaunchKernelGGL((awsm::k_shade<G>), dim3(g.blocks), dim3(256), 0, s, sc, *f);
+    });
+}
+// does this frame take the lean route?
+extern "C" int awsm_shade_is_lean(const awsm::FrameDev* f) {
+    return shade_grid(f).blocks && (f->msaa != 4u || (f->msaa_edge_bits && f->msaa_cells)) && f->draw_lean && f->tri_shade && f->shade_todo && f->has_opaque && f->n_draws;
 }
 // second half of the lean route; returns 0 when the frame did not take it
-extern "C" int awsm_shade_is_lean(const awsm::FrameDev* f) {
-    const uint32_t bx_n = (f->width + 15u) >> 4, by_n = f->band_n > 1u ? 2u * f->tiles_y : ((f->sy1 - f->sy0) + 15u) >> 4;
-    return (bx_n * by_n) && (f->msaa != 4u || (f->msaa_edge_bits && f->msaa_cells)) && f->draw_lean && f->tri_shade && f->shade_todo && f->has_opaque && f->n_draws;
-}
 extern "C" int awsm_launch_shade_todo(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s) {
     if (!awsm_shade_is_lean(f)) return 0;
-    const int g = mip_mode(f);
-    if (f->msaa == 4u) {      // ... and the edge pixels' remaining samples, once every sample-0 colour is in place
-        const uint32_t bx_n = (f->width + 15u) >> 4, by_n = f->band_n > 1u ? 2u * f->tiles_y : ((f->sy1 - f->sy0) + 15u) >> 4;
-        const uint32_t nb = 8u * ((by_n + 7u) / 8u) * bx_n;
-        AWSM_LAUNCH_G2(g, awsm::k_shade_todo, true, dim3(awsm::kTodoBlocks), dim3(256), sc, *f);
-        hipLaunchKernelGGL(awsm::k_msaa_detect, dim3(nb), dim3(64), 0, s, *f);
-        AWSM_LAUNCH_G(g, awsm::k_shade_msaa_resolve, dim3(nb), dim3(64), sc, *f);
-        return 1;
-    }
-    AWSM_LAUNCH_G2(g, awsm::k_shade_todo, false, dim3(awsm::kTodoBlocks), dim3(256), sc, *f);
+    const uint32_t blocks = shade_grid(f).blocks;
+    by_mip_mode(f, [&](auto mode) {
+        constexpr int G = decltype(mode)::value;
+        if (f->msaa == 4u) {      // ... and the edge pixels' remaining samples, once every sample-0 colour is in place
+            hipLaunchKernelGGL((awsm::k_shade_todo<G, true>), dim3(awsm::kTodoBlocks), dim3(256), 0, s, sc, *f);
+            hipLaunchKernelGGL(awsm::k_msaa_detect, dim3(blocks), dim3(64), 0, s, *f);
+            hipLaunchKernelGGL((awsm::k_shade_msaa_resolve<G>), dim3(blocks), dim3(64), 0, s, sc, *f);
+        } else hipLaunchKernelGGL((awsm::k_shade_todo<G, false>), dim3(awsm::kTodoBlocks), dim3(256), 0, s, sc, *f);
+    });
     return 1;
 }
 // f: the transparent pass's frame (its own draws / vertices / bins; vis = the geometry pass's keys; opaque_rgba16f = the opaque image;
@@ -3308,11 +2719,13 @@ extern "C" void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameD
     const uint32_t n_tiles = f->tiles_x * f->tiles_y;
     if (!n_tiles) return;
     const bool ms = f->msaa == 4u;
-    const int g = mip_mode(f);
     const uint32_t nb_shade = (f->frag_cap + 255u) / 256u, nb_blend = (f->width * f->height + 255u) / 256u;
-    if (ms) AWSM_LAUNCH_SG(g, awsm::k_forward_cover, 4, dim3(n_tiles * awsm::kFwdSubs), dim3(awsm::kFwdThreads), sc, *f);
-    else AWSM_LAUNCH_SG(g, awsm::k_forward_cover, 1, dim3(n_tiles * awsm::kFwdSubs), dim3(awsm::kFwdThreads), sc, *f);
-    if (nb_shade) AWSM_LAUNCH_G(g, awsm::k_forward_shade, dim3(nb_shade), dim3(256), sc, *f);
+    by_mip_mode(f, [&](auto mode) {
+        constexpr int G = decltype(mode)::value;
+        if (ms) hipLaunchKernelGGL((awsm::k_forward_cover<4, G>), dim3(n_tiles * awsm::kFwdSubs), dim3(awsm::kFwdThreads), 0, s, sc, *f);
+        else hipLaunchKernelGGL((awsm::k_forward_cover<1, G>), dim3(n_tiles * awsm::kFwdSubs), dim3(awsm::kFwdThreads), 0, s, sc, *f);
+        if (nb_shade) hipLaunchKernelGGL((awsm::k_forward_shade<G>), dim3(nb_shade), dim3(256), 0, s, sc, *f);
+    });
     if (ms) hipLaunchKernelGGL(awsm::k_forward_blend<4>, dim3(nb_blend), dim3(256), 0, s, *f); else hipLaunchKernelGGL(awsm::k_forward_blend<1>, dim3(nb_blend), dim3(256), 0, s, *f);
 }
 extern "C" void awsm_launch_msaa_halo_export(const awsm::FrameDev* f, unsigned long long* dst, uint32_t bands_out, hipStream_t s) {

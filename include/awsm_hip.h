@@ -91,7 +91,7 @@ typedef struct AwsmConfig {
                                          measurements and for tests that compare the two routes; results must agree within the shading tolerance. */
 #define AWSM_CFG_ANISOTROPIC 16u /* MipmapMode::Gradient honours AwsmSampler.max_anisotropy (gltf samplers ask for 16,
                                   * gltf/populate/material.rs:892-902): up to 17 weighted trilinear probes along the footprint's major axis,
-                                  * the level chosen for rho_max / N (the contract: DESIGN.md §2, grad_footprint in kernels_shade.hip).  Off by
+                                  * the level chosen for rho_max / N (the contract: DESIGN.md §2, grad_footprint in shade_samplers.hpp).  Off by
                                   * default: textureSampleGrad's anisotropy is implementation-defined in WebGPU, and the default here is the
                                   * isotropic rule the reference itself documents (helpers/mipmap.wgsl:419-439).  Draws whose core textures
                                   * ask for anisotropy leave the lean opaque route under this flag. */

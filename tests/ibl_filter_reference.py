@@ -10,7 +10,7 @@ import numpy as np
 
 GGX, LAMBERT = 0, 1
 
-# the face across each edge of each face: sample_cube's seam rule (kernels_shade.hip kCubeEdge) — face' | swap << 3 | flip << 4 | far << 5 for the
+# the face across each edge of each face: sample_cube's seam rule (cube_seam.hpp kCubeEdge) — face' | swap << 3 | flip << 4 | far << 5 for the
 # edges left (i = -1), right (i = N), up (j = -1), down (j = N)
 CUBE_EDGE = np.array([[44, 13, 58, 43], [45, 12, 10, 27], [1, 16, 21, 4], [49, 32, 36, 53], [41, 8, 34, 3], [40, 9, 18, 51]], dtype=np.int64)
 

@@ -1,4 +1,4 @@
-"""The anisotropic half of the textureSampleGrad contract (AWSM_CFG_ANISOTROPIC; oracle_shade.c: sample_array_grad, kernels_shade.hip: grad_footprint):
+"""The anisotropic half of the textureSampleGrad contract (AWSM_CFG_ANISOTROPIC; oracle_shade.c: sample_array_grad, shade_samplers.hpp: grad_footprint):
 properties of the oracle's restatement.  WebGPU leaves anisotropy to the implementation (the reference asks for max_anisotropy 16 on its glTF samplers,
 gltf/populate/material.rs:892-902, and samples with textureSampleGrad, texture_uvs.wgsl:122), so there is no golden vector to pin it with — what is
 checked is that the rule reduces to the isotropic one, is continuous where the probe count changes, conserves energy, and does what anisotropic

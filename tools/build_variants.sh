@@ -8,9 +8,8 @@ set -e
 cd "$(dirname "$0")/../awsm-renderer_amd/csrc"
 OUT=../../build/variants
 mkdir -p $OUT
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wall -Wno-unused-function"
+FLAGS="$(make -s print-CXXFLAGS)"; OBJ="$(make -s print-OBJ)"      # the Makefile's own flags and object list
 make -s ../libawsm_hip.so >/dev/null
-OBJ="awsm_hip.o awsm_resources.o kernels_geometry.o kernels_shade.o kernels_post.o kernels_env.o kernels_texture.o"      # csrc/Makefile: OBJ
 while [ $# -ge 2 ]; do
   NAME=$1; DEFS=$2; shift 2
   if [[ $NAME == g_* ]]; then SRC="kernels_geometry.hip"; elif [[ $NAME == h_* ]]; then SRC="awsm_hip.cpp awsm_resources.cpp"; else SRC="kernels_shade.hip"; fi
