@@ -898,6 +898,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->tex) fr(b);
     for (auto& b : c->tex_kinds) fr(b);
     for (auto& b : c->merged_vis) fr(b);
+    fr(c->pose_records);
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
@@ -966,6 +967,88 @@ int awsm_hip_buffer_write(AwsmHipCtx* c, AwsmBuf which, size_t dst_off, const vo
     // large (resize-time) uploads: the runtime stages pageable memory itself; wait so `src` is not retained
     HIPCHK(c, hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AWSM_OK;
+}
+
+// ---- skin matrices composed on the device (include/awsm_hip.h; kernels_pose.hip) ----
+int awsm_hip_skin_pose_records_write(AwsmHipCtx* c, uint32_t first, uint32_t n, const AwsmSkinPoseRecord* records) {
+    if (!c || (!records && n)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "skin_pose_records_write: bad argument");
+    static_assert(sizeof(AwsmSkinPoseRecord) == 72, "k_skin_pose reads 72-byte records");
+    std::vector<AwsmSkinPoseRecord>& host = c->pose_records_host;
+    if (first > host.size() || n > 0x03000000u - first) return fail(c, AWSM_ERR_OUT_OF_RANGE, "skin_pose_records_write: [%u,+%u) with %zu records resident", first, n, host.size());
+    if (n == 0) return AWSM_OK;
+    for (uint32_t i = 0; i < n; i++)
+        if ((records[i].transform_offset & 3u) || (records[i].matrix_offset & 3u)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "skin_pose_records_write: record %u has an offset that is not a multiple of 4", first + i);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c, false); if (rcb) return rcb; }
+    // the records as they will be: the context's copy, against which lists are checked, takes them only once the device has them
+    std::vector<AwsmSkinPoseRecord> next(host.begin(), host.end());
+    if (next.size() < (size_t)first + n) next.resize((size_t)first + n);
+    memcpy(next.data() + first, records, (size_t)n * sizeof(AwsmSkinPoseRecord));
+    size_t lo = first, count = n;
+    if (c->pose_records.size < next.size() * sizeof(AwsmSkinPoseRecord)) {      // grow by doubling; dev_realloc keeps nothing, so everything goes up again
+        const size_t cap = std::max<size_t>(std::max<size_t>(c->pose_records.size / sizeof(AwsmSkinPoseRecord) * 2, next.size()), 64);
+        int rc = dev_realloc(c, c->pose_records, cap * sizeof(AwsmSkinPoseRecord), false);
+        if (rc) { host.clear(); return rc; }      // nothing is resident any more
+        lo = 0; count = next.size();
+    }
+    constexpr size_t kChunk = 8192;      // records per staged copy (576 KiB)
+    for (size_t at = lo; at < lo + count; at += kChunk) {
+        const size_t m = std::min(kChunk, lo + count - at);
+        int rc = upload_small(c, (uint8_t*)c->pose_records.ptr + at * sizeof(AwsmSkinPoseRecord), next.data() + at, m * sizeof(AwsmSkinPoseRecord));
+        if (rc) { host.clear(); return rc; }      // part of the array may be neither the old nor the new records: no list passes until it is written again from 0
+    }
+    host.swap(next);
+    return AWSM_OK;
+}
+
+int awsm_hip_skin_pose(AwsmHipCtx* c, const uint32_t* ids, uint32_t n) {
+    if (!c || (!ids && n)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "skin_pose: bad argument");
+    if (n == 0) return AWSM_OK;
+    const DevBuf& tb = c->bufs[AWSM_BUF_TRANSFORMS];
+    const DevBuf& mb = c->bufs[AWSM_BUF_SKIN_MATRICES];
+    if (!tb.ptr || !mb.ptr) return fail(c, AWSM_ERR_NOT_READY, "skin_pose: the transforms or the skin matrices buffer was never created");
+    const std::vector<AwsmSkinPoseRecord>& host = c->pose_records_host;
+    // everything is checked before anything is enqueued: a refused list writes nothing
+    std::vector<uint32_t> offs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (ids[i] >= host.size()) return fail(c, AWSM_ERR_OUT_OF_RANGE, "skin_pose: record id %u (list entry %u) with %zu records resident", ids[i], i, host.size());
+        const AwsmSkinPoseRecord& r = host[ids[i]];
+        if (tb.size < 64 || r.transform_offset > tb.size - 64) return fail(c, AWSM_ERR_OUT_OF_RANGE, "skin_pose: record %u reads [%u,+64) of a transforms buffer of %zu bytes", ids[i], r.transform_offset, tb.size);
+        if (mb.size < 64 || r.matrix_offset > mb.size - 64) return fail(c, AWSM_ERR_OUT_OF_RANGE, "skin_pose: record %u writes [%u,+64) of a skin matrices buffer of %zu bytes", ids[i], r.matrix_offset, mb.size);
+        offs[i] = r.matrix_offset;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }      // as awsm_hip_buffer_write(AWSM_BUF_SKIN_MATRICES): behind the opaque passes in flight
+    std::sort(offs.begin(), offs.end());
+    for (size_t i = 0; i < offs.size();) {      // one dirty range per run of adjacent matrices: the geometry cache recomputes the skinned draws they belong to
+        size_t j = i + 1;
+        while (j < offs.size() && offs[j] <= offs[j - 1] + 64u) j++;
+        log_dirty(c, AWSM_BUF_SKIN_MATRICES, offs[i], (size_t)offs[j - 1] + 64);
+        i = j;
+    }
+    constexpr uint32_t kChunk = 65536;      // ids per launch: 256 KiB of the pinned ring
+    for (uint32_t at = 0; at < n; at += kChunk) {
+        const uint32_t m = std::min(kChunk, n - at);
+        uint8_t* st;
+        int rc = stage_alloc(c, (size_t)m * 4, &st);
+        if (rc) return rc;
+        memcpy(st, ids + at, (size_t)m * 4);
+        awsm_launch_skin_pose(c->pose_records.ptr, (const uint32_t*)st, m, tb.ptr, mb.ptr, c->stream);      // pinned memory is device-visible at the same address
+        HIPCHK(c, hipGetLastError());
+    }
+    return AWSM_OK;
+}
+
+int awsm_hip_buffer_read(AwsmHipCtx* c, AwsmBuf which, size_t offset, void* dst, size_t len) {
+    if (!c || (int)which < 0 || which >= AWSM_BUF_COUNT || (!dst && len)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "buffer_read: bad argument");
+    const DevBuf& b = c->bufs[which];
+    if (!b.ptr) return fail(c, AWSM_ERR_NOT_READY, "buffer_read: buffer %d was never created", (int)which);
+    if (offset > b.size || len > b.size - offset) return fail(c, AWSM_ERR_OUT_OF_RANGE, "buffer_read: [%zu,+%zu) outside buffer %d of %zu bytes", offset, len, (int)which, b.size);
+    if (len == 0) return AWSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // every write to a scene buffer is enqueued on the caller's stream
+    HIPCHK(c, hipMemcpy(dst, (const uint8_t*)b.ptr + offset, len, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 

@@ -98,6 +98,10 @@ struct AwsmHipCtx {
     uint32_t tex_srgb[64] = {};
     bool tex_srgb_made = false;
 
+    // awsm_hip_skin_pose: the resident records (72 bytes each; grows by doubling) and the host's copy, against which a list's ids and offsets are checked
+    DevBuf pose_records;
+    std::vector<AwsmSkinPoseRecord> pose_records_host;
+
     // frame targets
     uint32_t width = 0, height = 0;
     uint32_t y0 = 0, y1 = 0;     // shard rows (0,0 = full)

@@ -51,4 +51,6 @@ void awsm_launch_tex_write(const awsm::TexWriteArgs* a, hipStream_t s);
 void awsm_launch_tex_mips(const awsm::TexMipArgs* a, hipStream_t s);
 void awsm_launch_gen_mip_level(uint8_t* chain, uint32_t src_off, uint32_t dst_off, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, uint32_t layers,
                                const uint32_t* kinds, hipStream_t s);
+// kernels_pose.hip
+void awsm_launch_skin_pose(const void* records, const uint32_t* ids_pinned, uint32_t n, const void* transforms, void* skin_matrices, hipStream_t s);
 }

@@ -276,6 +276,31 @@ def scene_to_gltf(scene: SceneDesc, embed_images: bool = True) -> Tuple[dict, by
             doc["images"] = [{"bufferView": b.add_blob(png), "mimeType": "image/png"} for png in pngs]
         else:
             doc["images"] = [{"uri": f"image{i}.png"} for i in range(len(pngs))]
+    # ---- animations (SceneDesc.animations): after everything else, so a scene without any is written exactly as before ----
+    if getattr(scene, "animations", None):
+        interp = {"linear": "LINEAR", "step": "STEP", "cubic": "CUBICSPLINE"}
+        anims = []
+        for a in scene.animations:
+            samplers, channels = [], []
+            for ch in a["channels"]:
+                path, kind = ch["path"], ch.get("interpolation", "linear")
+                times = np.asarray(ch["times"], dtype=F).reshape(-1)
+                values = np.asarray(ch["values"], dtype=F).reshape(len(times), -1)
+                if kind == "cubic":      # per key: in-tangent, value, out-tangent
+                    values = np.stack([np.asarray(ch["in_tangents"], dtype=F).reshape(values.shape), values,
+                                       np.asarray(ch["out_tangents"], dtype=F).reshape(values.shape)], axis=1).reshape(len(times) * 3, -1)
+                gtype = {"translation": "VEC3", "rotation": "VEC4", "scale": "VEC3"}.get(path, "SCALAR")
+                out = values if gtype != "SCALAR" else values.reshape(-1)
+                out_acc = b.add(out, 5126, gtype)
+                in_acc = b.add(times, 5126, "SCALAR")
+                b.accessors[in_acc]["min"], b.accessors[in_acc]["max"] = [_f(times.min())], [_f(times.max())]      # required on a sampler's input
+                samplers.append({"input": in_acc, "output": out_acc, "interpolation": interp[kind]})
+                channels.append({"sampler": len(samplers) - 1, "target": {"node": int(ch["node"]), "path": path}})
+            g = {"channels": channels, "samplers": samplers}
+            if a.get("name"):
+                g["name"] = a["name"]
+            anims.append(g)
+        doc["animations"] = anims
     doc["bufferViews"] = b.views
     doc["accessors"] = b.accessors
     doc["buffers"] = [{"byteLength": len(b.data)}]

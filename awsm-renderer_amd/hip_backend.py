@@ -38,7 +38,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level",
            "awsm_hip_env_cube_filter",
            "awsm_hip_texture_array_create", "awsm_hip_texture_array_resize_layers", "awsm_hip_texture_array_write_layers",
-           "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info"]
+           "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info",
+           "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read"]
 
 
 class AwsmConfig(C.Structure):
@@ -202,6 +203,9 @@ def load_library():
     lib.awsm_hip_env_cube_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.awsm_hip_env_cube_read_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     lib.awsm_hip_env_cube_filter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.awsm_hip_skin_pose_records_write.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.awsm_hip_skin_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.awsm_hip_buffer_read.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
     _lib = lib
     return lib
 
@@ -253,6 +257,22 @@ class HipDevice:
     def buffer_write(self, which: int, offset: int, data):
         arr = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         self._chk(self.lib.awsm_hip_buffer_write(self.ctx, which, offset, arr.ctypes.data_as(C.c_void_p), arr.nbytes), f"buffer_write({BUF_NAMES[which]})")
+
+    def buffer_read(self, which: int, offset: int, nbytes: int) -> bytes:
+        """awsm_hip_buffer_read: a synchronising read-back of a scene buffer (tests, diagnostics)."""
+        out = np.zeros(max(1, nbytes), dtype=np.uint8)
+        self._chk(self.lib.awsm_hip_buffer_read(self.ctx, which, offset, out.ctypes.data_as(C.c_void_p), nbytes), f"buffer_read({BUF_NAMES[which]})")
+        return out[:nbytes].tobytes()
+
+    def skin_pose_records_write(self, first: int, records: np.ndarray):
+        """records: (n, 18) uint32 / float32 words — transform_offset, matrix_offset, inverse_bind[16] (AwsmSkinPoseRecord)."""
+        r = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 18)
+        self._chk(self.lib.awsm_hip_skin_pose_records_write(self.ctx, first, r.shape[0], r.ctypes.data_as(C.c_void_p)), "skin_pose_records_write")
+
+    def skin_pose(self, record_ids):
+        """awsm_hip_skin_pose: AWSM_BUF_SKIN_MATRICES[matrix_offset] = world * inverse_bind for the listed records."""
+        ids = np.ascontiguousarray(record_ids, dtype=np.uint32)
+        self._chk(self.lib.awsm_hip_skin_pose(self.ctx, ids.ctypes.data_as(C.c_void_p), ids.size), "skin_pose")
 
     def upload_mirrors(self, mirrors: Dict[int, bytes]):
         """create + full write of every mirror (what the reference does on the first frame / after a resize)."""

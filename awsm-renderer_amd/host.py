@@ -74,6 +74,22 @@ class HostLight(C.Structure):
                 ("direction", C.c_float * 3), ("inner_angle", C.c_float), ("outer_angle", C.c_float)]
 
 
+class AnimationClip(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("n_keys", C.c_uint32), ("width", C.c_uint32),
+                ("times", C.POINTER(C.c_double)), ("values", F32P), ("in_tangents", F32P), ("out_tangents", F32P), ("duration", C.c_double)]
+
+
+class AnimationState(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("direction", C.c_int32), ("state", C.c_int32), ("loop_style", C.c_int32),
+                ("local_time", C.c_double), ("duration", C.c_double), ("speed", C.c_double)]
+
+
+ANIM_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}
+ANIM_INTERPOLATIONS = {"linear": 0, "step": 1, "cubic": 2}
+ANIM_LOOP_NONE, ANIM_LOOP, ANIM_PING_PONG = -1, 0, 1
+ANIM_FORWARD, ANIM_BACKWARD = 0, 1
+ANIM_PLAYING, ANIM_PAUSED, ANIM_ENDED = 0, 1, 2
+
 _lib = None
 
 
@@ -130,6 +146,16 @@ def load_library():
         "awsm_host_texture_insert_ex": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp]), "awsm_host_texture_update": (C.c_int, [vp, C.c_int, vp]),
         "awsm_host_load_gltf_ex": (C.c_int, [vp, C.c_char_p, vp, vp, C.c_char_p, C.c_size_t]),
         "awsm_host_upload_bytes_last_frame": (u64, [vp]),
+        "awsm_host_transform_get_local": (C.c_int, [vp, u64, F32P, F32P, F32P]), "awsm_host_transform_duplicate": (u64, [vp, u64]),
+        "awsm_host_mesh_update_morph_weights": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_light_update": (C.c_int, [vp, u64, vp]),
+        "awsm_host_animation_insert_transform": (u64, [vp, vp, u64]), "awsm_host_animation_insert_morph": (u64, [vp, vp, u64]),
+        "awsm_host_animation_remove": (C.c_int, [vp, u64]),
+        "awsm_host_animation_set_playback": (C.c_int, [vp, u64, C.c_double, C.c_int, C.c_int, C.c_int]),
+        "awsm_host_animation_seek": (C.c_int, [vp, u64, C.c_double]), "awsm_host_animation_state": (C.c_int, [vp, u64, vp]),
+        "awsm_host_animation_sample": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_update_animations": (C.c_int, [vp, C.c_double]),
+        "awsm_host_skin_matrices_offset": (i64, [vp, u64]),
+        "awsm_host_gltf_animation_keys": (C.c_int, [vp, C.POINTER(u64), C.c_uint32, U32P]),
+        "awsm_host_set_device_skin_posing": (C.c_int, [vp, C.c_int]), "awsm_host_skin_pose_ids_last_frame": (C.c_int, [vp, U32P, C.c_uint32, U32P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -223,6 +249,19 @@ class Host:
         k1, k2, k3 = _f(t), _f(r), _f(s)
         self._chk(self.lib.awsm_host_transform_set_local(self.h, key, k1[1], k2[1], k3[1]), "transform_set_local")
 
+    def transform_get_local(self, key):
+        """Transforms::get_local: (translation, rotation xyzw, scale) as float32 arrays."""
+        t, r, s = np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.awsm_host_transform_get_local(self.h, key, t.ctypes.data_as(F32P), r.ctypes.data_as(F32P), s.ctypes.data_as(F32P)), "transform_get_local")
+        return t, r, s
+
+    def transform_duplicate(self, key) -> int:
+        """Transforms::duplicate: a new node with the same local transform under the same parent."""
+        k = self.lib.awsm_host_transform_duplicate(self.h, key)
+        if not k:
+            self._chk(-1, "transform_duplicate")
+        return k
+
     def transform_parent(self, key) -> int:
         return self.lib.awsm_host_transform_parent(self.h, key)
 
@@ -285,6 +324,10 @@ class Host:
             self._chk(-1, "skin_insert")
         return k
 
+    def skin_matrices_offset(self, key: int) -> int:
+        """Byte offset of the skin's first matrix in AWSM_BUF_SKIN_MATRICES (-1: no such skin)."""
+        return self.lib.awsm_host_skin_matrices_offset(self.h, key)
+
     def hud_draw_lists(self):
         """(HUD geometry pass draws, HUD transparent pass draws): the hud meshes, back to front (render.rs:169-178,301-312)."""
         n = C.c_uint32()
@@ -333,15 +376,29 @@ class Host:
             self._chk(-1, "mesh_insert")
         return k
 
+    def mesh_update_morph_weights(self, key: int, weights):
+        """Morphs::update_morph_weights_with: the mesh's weights (one per target), uploaded with the next frame."""
+        a, ap = _f(weights)
+        self._chk(self.lib.awsm_host_mesh_update_morph_weights(self.h, key, ap, a.size), "mesh_update_morph_weights")
+
     def mesh_remove(self, key: int):
         self._chk(self.lib.awsm_host_mesh_remove(self.h, key), "mesh_remove")
 
     # ---- lights / camera / env ----
-    def light_insert(self, l: dict) -> int:
+    @staticmethod
+    def _light(l: dict) -> HostLight:
         kind = {"directional": 1, "point": 2, "spot": 3}[l["kind"]]
-        hl = HostLight(kind, (C.c_float * 3)(*l["color"]), l["intensity"], (C.c_float * 3)(*l.get("position", (0, 0, 0))), l.get("range", 0.0),
-                       (C.c_float * 3)(*l.get("direction", (0, 0, 0))), l.get("inner_angle", 0.0), l.get("outer_angle", 0.0))
+        return HostLight(kind, (C.c_float * 3)(*l["color"]), l["intensity"], (C.c_float * 3)(*l.get("position", (0, 0, 0))), l.get("range", 0.0),
+                         (C.c_float * 3)(*l.get("direction", (0, 0, 0))), l.get("inner_angle", 0.0), l.get("outer_angle", 0.0))
+
+    def light_insert(self, l: dict) -> int:
+        hl = self._light(l)
         return self.lib.awsm_host_light_insert(self.h, C.byref(hl))
+
+    def light_update(self, key: int, l: dict):
+        """Lights::update: the light's new values, uploaded with the next frame."""
+        hl = self._light(l)
+        self._chk(self.lib.awsm_host_light_update(self.h, key, C.byref(hl)), "light_update")
 
     def light_remove(self, key: int):
         self._chk(self.lib.awsm_host_light_remove(self.h, key), "light_remove")
@@ -509,6 +566,81 @@ class Host:
         self._chk(self.lib.awsm_host_set_render_hooks(self.h, C.cast(self._hooks[0], C.c_void_p) if self._hooks[0] else None, None,
                                                       C.cast(self._hooks[1], C.c_void_p) if self._hooks[1] else None, None), "set_render_hooks")
 
+    # ---- animation (animation/animations.rs) ----
+    def _animation_insert(self, fn, target, path, times, values, interpolation, in_tangents, out_tangents, duration):
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(len(t), -1) if len(t) else np.zeros((0, 0), np.float32)
+        clip = AnimationClip(struct_size=C.sizeof(AnimationClip), path=ANIM_PATHS[path], interpolation=ANIM_INTERPOLATIONS[interpolation],
+                             n_keys=len(t), width=v.shape[1])
+        keep = [t, v]
+        clip.times, clip.values = t.ctypes.data_as(C.POINTER(C.c_double)), v.ctypes.data_as(F32P)
+        for name, arr in (("in_tangents", in_tangents), ("out_tangents", out_tangents)):
+            if arr is not None:
+                a = np.ascontiguousarray(arr, dtype=np.float32).reshape(len(t), -1)
+                keep.append(a)
+                setattr(clip, name, a.ctypes.data_as(F32P))
+        clip.duration = float(t[-1] - t[0]) if duration is None and len(t) else float(duration or 0.0)      # gltf/populate/animation.rs:107,229
+        k = fn(self.h, C.byref(clip), target)
+        if not k:
+            self._chk(-1, "animation_insert")
+        return k
+
+    def animation_insert_transform(self, transform: int, path: str, times, values, interpolation: str = "linear", in_tangents=None, out_tangents=None,
+                                   duration: Optional[float] = None) -> int:
+        """A player (speed 1/1000, Loop, Forward, Playing) for one of a node's translation / rotation / scale; values: (keys, 3 or 4).  duration
+        defaults to last key - first key, as the glTF reader sets it."""
+        return self._animation_insert(self.lib.awsm_host_animation_insert_transform, transform, path, times, values, interpolation, in_tangents, out_tangents, duration)
+
+    def animation_insert_morph(self, mesh: int, times, values, interpolation: str = "linear", in_tangents=None, out_tangents=None,
+                               duration: Optional[float] = None) -> int:
+        """A player for a mesh's morph weights; values: (keys, targets)."""
+        return self._animation_insert(self.lib.awsm_host_animation_insert_morph, mesh, "weights", times, values, interpolation, in_tangents, out_tangents, duration)
+
+    def animation_remove(self, key: int):
+        self._chk(self.lib.awsm_host_animation_remove(self.h, key), "animation_remove")
+
+    def animation_state(self, key: int) -> dict:
+        st = AnimationState(struct_size=C.sizeof(AnimationState))
+        self._chk(self.lib.awsm_host_animation_state(self.h, key, C.byref(st)), "animation_state")
+        return {k: getattr(st, k) for k in ("local_time", "direction", "state", "loop_style", "duration", "speed")}
+
+    def animation_set_playback(self, key: int, speed: Optional[float] = None, loop_style: Optional[int] = None, direction: Optional[int] = None,
+                               state: Optional[int] = None):
+        """The player's speed, loop style (ANIM_LOOP_NONE / ANIM_LOOP / ANIM_PING_PONG), direction and state; None keeps a value."""
+        cur = self.animation_state(key)
+        pick = lambda v, name: cur[name] if v is None else v      # noqa: E731
+        self._chk(self.lib.awsm_host_animation_set_playback(self.h, key, pick(speed, "speed"), pick(loop_style, "loop_style"), pick(direction, "direction"),
+                                                            pick(state, "state")), "animation_set_playback")
+
+    def animation_seek(self, key: int, local_time: float):
+        self._chk(self.lib.awsm_host_animation_seek(self.h, key, local_time), "animation_seek")
+
+    def animation_sample(self, key: int) -> np.ndarray:
+        """The value at the player's local time (nothing applied): 3, 4 or target-count float32."""
+        n = self.lib.awsm_host_animation_sample(self.h, key, None, 0)      # the width
+        if n < 0:
+            self._chk(n, "animation_sample")
+        out = np.zeros(max(1, n), np.float32)
+        n = self.lib.awsm_host_animation_sample(self.h, key, out.ctypes.data_as(F32P), out.size)
+        if n < 0:
+            self._chk(n, "animation_sample")
+        return out[:n].copy()
+
+    def update_animations(self, global_time_delta: float):
+        """AwsmRenderer::update_animations: every player advances by global_time_delta * speed and is applied."""
+        self._chk(self.lib.awsm_host_update_animations(self.h, float(global_time_delta)), "update_animations")
+
+    def set_device_skin_posing(self, on: bool):
+        """Skin matrices composed on the device from the world matrices already there (off by default; the same bytes either way)."""
+        self._chk(self.lib.awsm_host_set_device_skin_posing(self.h, 1 if on else 0), "set_device_skin_posing")
+
+    def skin_pose_ids_last_frame(self) -> List[int]:
+        n = C.c_uint32()
+        self._chk(self.lib.awsm_host_skin_pose_ids_last_frame(self.h, None, 0, C.byref(n)), "skin_pose_ids_last_frame")
+        arr = (C.c_uint32 * max(1, n.value))()
+        self._chk(self.lib.awsm_host_skin_pose_ids_last_frame(self.h, arr, n.value, C.byref(n)), "skin_pose_ids_last_frame")
+        return list(arr[: n.value])
+
     def update_transforms(self):
         self._chk(self.lib.awsm_host_update_transforms(self.h), "update_transforms")
 
@@ -536,8 +668,17 @@ class Host:
             rc = self.lib.awsm_host_load_gltf(self.h, os.fsencode(path), scene_index, info, err, 512)
         if rc != 0:
             raise HostError(f"load_gltf({path}) failed ({rc}): {err.value.decode(errors='replace')}")
-        names = ("nodes", "meshes", "materials", "images", "samplers", "skins", "lights", "triangles", "generated_tangents")
+        names = ("nodes", "meshes", "materials", "images", "samplers", "skins", "lights", "triangles", "generated_tangents", "instanced_meshes",
+                 "animations", "animation_channels_skipped")
         return {k: int(info[i]) for i, k in enumerate(names)}
+
+    def gltf_animation_keys(self) -> List[int]:
+        """The players the last load_gltf made, in insertion order (awsm_host_gltf_animation_keys)."""
+        n = C.c_uint32()
+        self._chk(self.lib.awsm_host_gltf_animation_keys(self.h, None, 0, C.byref(n)), "gltf_animation_keys")
+        arr = (C.c_uint64 * max(1, n.value))()
+        self._chk(self.lib.awsm_host_gltf_animation_keys(self.h, arr, n.value, C.byref(n)), "gltf_animation_keys")
+        return list(arr[: n.value])
 
     def transparent_draw_list(self) -> List[dict]:
         """The world transparent pass's list: back to front; vis_data_off = offset into the transparency geometry buffer."""
@@ -758,6 +899,11 @@ class Renderer:
     def update(self):
         self.host.update_transforms()
         self.host.camera_update(self.scene.view, self.scene.proj, self.scene.camera_position)
+
+    def update_all(self, global_time_delta: float):
+        """update_all (update.rs:8-18): animations -> transforms -> camera."""
+        self.host.update_animations(global_time_delta)
+        self.update()
 
     def render(self, sync: bool = True):
         return self.host.render(sync)

@@ -208,6 +208,22 @@ class DynamicStorageBuffer {
         mark_dirty_range(dirty_, raw_.size(), it->second.first, it->second.second);
         return true;
     }
+    // bytes [at, at + len) of the key's block, with that range alone marked dirty (update_with_unchecked marks the whole block).  false: missing key
+    // or outside the block
+    bool write_range(SlotKey key, size_t at, const uint8_t* bytes, size_t len) {
+        auto it = slots_.find(key);
+        if (it == slots_.end() || at > it->second.second || len > it->second.second - at) return false;
+        memcpy(raw_.data() + it->second.first + at, bytes, len);
+        mark_dirty_range(dirty_, raw_.size(), it->second.first + at, len);
+        return true;
+    }
+    // bytes the device already holds (it computed them itself): into the mirror without a dirty range.  false: missing key or outside the block
+    bool write_untracked(SlotKey key, size_t at, const uint8_t* bytes, size_t len) {
+        auto it = slots_.find(key);
+        if (it == slots_.end() || at > it->second.second || len > it->second.second - at) return false;
+        memcpy(raw_.data() + it->second.first + at, bytes, len);
+        return true;
+    }
     void remove(SlotKey key) {
         auto it = slots_.find(key);
         if (it == slots_.end()) return;

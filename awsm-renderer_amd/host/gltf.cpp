@@ -16,7 +16,9 @@
 //
 // Images: PNG (png.hpp, zlib inflate) and JPEG (jpeg.hpp: baseline, extended sequential and progressive; Huffman, 8 bit).  KTX2 and anything else return
 // AWSM_ERR_UNSUPPORTED with the image index in the message.
-// Not read: cameras (the caller owns the camera), animations, KHR_mesh_quantization beyond the normalised integer attribute
+// Animations (populate.rs:229-268, populate/animation.rs): channels on translation / rotation / scale / weights with float inputs and outputs
+// become players through awsm_host_animation_insert_*; the first sampler per (node, path) in document order wins, over all animations.
+// Not read: cameras (the caller owns the camera), KHR_mesh_quantization beyond the normalised integer attribute
 // types glTF core already allows.
 #include <algorithm>
 #include <cmath>
@@ -36,6 +38,10 @@
 
 using awsm_json::Value;
 
+// host.cpp: where the reader leaves the keys of the players it made (awsm_host_gltf_animation_keys returns them); internal to the library: hidden,
+// so that it is not among the symbols the library exports
+extern "C" __attribute__((visibility("hidden"))) void awsm_host_gltf_set_animation_keys(AwsmHost* h, const AwsmKey* keys, uint32_t n);
+
 namespace {
 
 struct Loader {
@@ -53,8 +59,12 @@ struct Loader {
     std::map<std::vector<int64_t>, int> tex_cache;
     std::map<std::vector<uint32_t>, uint32_t> sampler_ids;   // AwsmSampler fields -> host sampler id
     std::vector<AwsmKey> node_keys;
+    // build_node_animation_sampler_lookup (populate.rs:229-268): per node, the (animation, sampler) of the first channel on each path; -1 = none
+    struct NodeSamplers { int path[4][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}}; };
+    std::map<size_t, NodeSamplers> node_samplers;
     std::map<int, AwsmKey> material_keys;             // glTF material (-1 = default) -> key
     std::map<std::vector<float>, AwsmKey> tex_transform_keys;
+    std::vector<AwsmKey> animation_keys;              // the players made, in the order they were inserted
     AwsmGltfInfo info{};
 
     bool fail(const char* fmt, ...) {
@@ -601,9 +611,83 @@ bool add_transforms(Loader& L, size_t node, AwsmKey parent) {
     return true;
 }
 
+// build_node_animation_sampler_lookup (populate.rs:229-268): first sampler per (node, path) in document order, over all animations.  A path this
+// reader does not know is counted as skipped.
+void build_animation_lookup(Loader& L) {
+    const Value& anims = L.doc["animations"];
+    static const char* kPaths[4] = {"translation", "rotation", "scale", "weights"};
+    for (size_t a = 0; a < anims.size(); a++) {
+        const Value& channels = anims[a]["channels"];
+        for (size_t c = 0; c < channels.size(); c++) {
+            const Value& target = channels[c]["target"];
+            const int64_t node = target["node"].integer(-1);
+            int path = -1;
+            for (int k = 0; k < 4; k++) if (target["path"].string() == kPaths[k]) path = k;
+            if (node < 0 || path < 0) { L.info.animation_channels_skipped++; continue; }
+            Loader::NodeSamplers& ns = L.node_samplers[(size_t)node];
+            if (ns.path[path][0] < 0) { ns.path[path][0] = (int)a; ns.path[path][1] = (int)channels[c]["sampler"].integer(-1); }
+        }
+    }
+}
+
+// gltf_animation_clip_transform / populate_gltf_animation_morph (populate/animation.rs:68-149,223-276): times are f32 in the file and f64 in the
+// clip, duration = last - first, a cubic output is (in-tangent, value, out-tangent) per key.  false: the sampler cannot be used (its input or output
+// is not a float accessor, it has no keys, the output does not hold keys * width values): the channel is skipped and counted.
+struct ClipArrays { std::vector<double> times; std::vector<float> values, in_t, out_t; AwsmHostAnimationClip clip; };
+bool animation_clip(Loader& L, int anim, int sampler, uint32_t path, uint32_t width, ClipArrays& out) {
+    const Value& smp = L.doc["animations"][(size_t)anim]["samplers"][(size_t)sampler];
+    if (anim < 0 || sampler < 0 || !smp.is_object()) return false;
+    const int64_t in_acc = smp["input"].integer(-1), out_acc = smp["output"].integer(-1);
+    const Value& accs = L.doc["accessors"];
+    if (in_acc < 0 || out_acc < 0 || accs[(size_t)in_acc]["componentType"].integer(0) != 5126 || accs[(size_t)out_acc]["componentType"].integer(0) != 5126) return false;
+    const std::string& interp = smp["interpolation"].string();
+    const uint32_t interpolation = interp == "STEP" ? AWSM_ANIM_STEP : (interp == "CUBICSPLINE" ? AWSM_ANIM_CUBICSPLINE : AWSM_ANIM_LINEAR);
+    std::vector<float> t32, raw;
+    size_t n_keys = 0, n_out = 0;
+    const std::string saved = L.err;
+    if (!read_floats(L, (int)in_acc, 1, t32, &n_keys) || !read_floats(L, (int)out_acc, path == AWSM_ANIM_WEIGHTS ? 1 : (int)width, raw, &n_out)) { L.err = saved; return false; }
+    const size_t per_key = (size_t)width * (interpolation == AWSM_ANIM_CUBICSPLINE ? 3u : 1u);
+    if (n_keys == 0 || raw.size() < n_keys * per_key) return false;
+    out.times.assign(t32.begin(), t32.end());
+    if (interpolation == AWSM_ANIM_CUBICSPLINE) {
+        out.values.resize(n_keys * width); out.in_t.resize(n_keys * width); out.out_t.resize(n_keys * width);
+        for (size_t k = 0; k < n_keys; k++) {
+            memcpy(&out.in_t[k * width], &raw[(k * 3 + 0) * width], (size_t)width * 4);
+            memcpy(&out.values[k * width], &raw[(k * 3 + 1) * width], (size_t)width * 4);
+            memcpy(&out.out_t[k * width], &raw[(k * 3 + 2) * width], (size_t)width * 4);
+        }
+    } else out.values.assign(raw.begin(), raw.begin() + n_keys * width);
+    AwsmHostAnimationClip& c = out.clip;
+    memset(&c, 0, sizeof c);
+    c.struct_size = sizeof c; c.path = path; c.interpolation = interpolation; c.n_keys = (uint32_t)n_keys; c.width = width;
+    c.times = out.times.data(); c.values = out.values.data();
+    c.in_tangents = out.in_t.empty() ? nullptr : out.in_t.data(); c.out_tangents = out.out_t.empty() ? nullptr : out.out_t.data();
+    c.duration = (double)(t32.back() - t32.front());      // an f32 difference, then widened (animation.rs:107,229)
+    return true;
+}
+
+// populate_gltf_node_animation (populate/animation.rs:21-66): translation, rotation, scale of a node, then its children
+bool add_node_animations(Loader& L, size_t node) {
+    auto it = L.node_samplers.find(node);
+    if (it != L.node_samplers.end() && L.node_keys[node]) {
+        for (uint32_t path = 0; path < 3; path++) {
+            const int* ref = it->second.path[path];
+            if (ref[0] < 0) continue;
+            ClipArrays ca;
+            if (!animation_clip(L, ref[0], ref[1], path, path == AWSM_ANIM_ROTATION ? 4u : 3u, ca)) { L.info.animation_channels_skipped++; continue; }
+            const AwsmKey k = awsm_host_animation_insert_transform(L.h, &ca.clip, L.node_keys[node]);
+            if (!k) return L.fail("animation %d on node %zu: %s", ref[0], node, awsm_host_last_error(L.h));
+            L.animation_keys.push_back(k);
+            L.info.animations++;
+        }
+    }
+    const Value& ch = L.doc["nodes"][node]["children"];
+    for (size_t i = 0; i < ch.size(); i++) if (!add_node_animations(L, (size_t)ch[i].integer(-1))) return false;
+    return true;
+}
+
 // populate/mesh.rs + gltf/buffers/mesh.rs for one primitive
 bool add_primitive(Loader& L, const Value& node, size_t node_index, const Value& mesh, const Value& prim, AwsmKey transform, bool is_joint_node) {
-    (void)node_index;
     const bool mesh_on_joint_node = is_joint_node;
     const int64_t mode = prim["mode"].integer(4);
     if (mode != 4 && mode != 5 && mode != 6) return L.fail("primitive mode %lld is not supported (triangles, strips and fans only; buffers/index.rs:203-206)", (long long)mode);
@@ -715,6 +799,21 @@ bool add_primitive(Loader& L, const Value& node, size_t node_index, const Value&
     const AwsmKey mesh_key = awsm_host_mesh_insert(L.h, &p, transform, mk, skin_key, 0);
     if (!mesh_key) return L.fail("mesh: %s", awsm_host_last_error(L.h));
     L.info.meshes++; L.info.triangles += p.triangle_count;
+    // a weights channel on the node: one player per primitive that has targets (populate_gltf_animation_morph, populate/animation.rs:68-149)
+    {
+        auto ns = L.node_samplers.find(node_index);
+        if (ns != L.node_samplers.end() && ns->second.path[AWSM_ANIM_WEIGHTS][0] >= 0 && !mts.empty()) {
+            const int* ref = ns->second.path[AWSM_ANIM_WEIGHTS];
+            ClipArrays ca;
+            if (!animation_clip(L, ref[0], ref[1], AWSM_ANIM_WEIGHTS, (uint32_t)mts.size(), ca)) L.info.animation_channels_skipped++;
+            else {
+                const AwsmKey k = awsm_host_animation_insert_morph(L.h, &ca.clip, mesh_key);
+                if (!k) return L.fail("morph animation on node %zu: %s", node_index, awsm_host_last_error(L.h));
+                L.animation_keys.push_back(k);
+                L.info.animations++;
+            }
+        }
+    }
     // EXT_mesh_gpu_instancing on the node (gltf/populate/extensions/instancing.rs:9-160): TRANSLATION / SCALE are float VEC3, ROTATION is a
     // VEC4 of floats or of integers cast as they are (`v as f32`: the reference does not normalise them); the count is that of the first
     // attribute present, missing ones are identity; every mesh that hangs on the node's own transform becomes instanced (a skinned mesh
@@ -865,6 +964,8 @@ bool load(Loader& L, const char* path, int scene_index) {
     std::vector<bool> is_joint(n_nodes, false);
     const Value& skins = L.doc["skins"];
     for (size_t s = 0; s < skins.size(); s++) for (size_t j = 0; j < skins[s]["joints"].size(); j++) { const size_t jn = (size_t)skins[s]["joints"][j].integer(-1); if (jn < n_nodes) is_joint[jn] = true; }
+    build_animation_lookup(L);
+    for (size_t i = 0; i < roots.size(); i++) if (!add_node_animations(L, (size_t)roots[i].integer(-1))) return false;      // populate.rs:197-199: before the meshes
     for (size_t i = 0; i < roots.size(); i++) if (!add_meshes(L, (size_t)roots[i].integer(-1), is_joint)) return false;
     if (awsm_host_update_transforms(L.h)) return L.fail("update_transforms: %s", awsm_host_last_error(L.h));
     return add_lights(L);
@@ -898,6 +999,7 @@ extern "C" int awsm_host_load_gltf_ex(AwsmHost* h, const char* path, const AwsmG
     L.h = h;
     L.srgb_color_textures = (options->flags & AWSM_GLTF_SRGB_COLOR_TEXTURES) != 0u;
     const bool ok = load(L, path, options->scene_index);
+    awsm_host_gltf_set_animation_keys(h, L.animation_keys.data(), (uint32_t)L.animation_keys.size());
     if (info_out) *info_out = L.info;
     if (!ok) {
         if (err_out && err_cap) { snprintf(err_out, err_cap, "%s", L.err.c_str()); }

@@ -13,6 +13,7 @@
 //   renderable.rs:38-150, frustum.rs:42-89, bounds.rs:38-61   cull + sort -> draw list
 //   render.rs:71-97,144-221,370   write_gpu order, geometry pass, opaque pass, submit
 //   buffer/helpers.rs:124-220     write_buffer_with_dirty_ranges
+//   animation/animations.rs:39-141   Animations, update_animations (players and samplers: animation.hpp)
 // The device is reached only through the awsm_hip_* C-ABI, resolved with dlsym from the backend library.
 #include "../../include/awsm_host.h"
 
@@ -30,6 +31,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "animation.hpp"
 #include "buffers.hpp"
 #include "glam.hpp"
 #include "ktx2.hpp"
@@ -79,6 +81,9 @@ struct Backend {
     int (*texture_array_write_layers)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t, const void*, size_t, const AwsmTexWrite*) = nullptr;
     int (*texture_array_generate_mips_layers)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t) = nullptr;
     int (*texture_array_info)(AwsmHipCtx*, uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*) = nullptr;
+    // optional: skin matrices composed on the device (awsm_host_set_device_skin_posing)
+    int (*skin_pose_records_write)(AwsmHipCtx*, uint32_t, uint32_t, const AwsmSkinPoseRecord*) = nullptr;
+    int (*skin_pose)(AwsmHipCtx*, const uint32_t*, uint32_t) = nullptr;
     // the name of the first of them the library lacks, or null
     const char* texture_pool_missing() const {
         return !texture_array_create ? "awsm_hip_texture_array_create" : !texture_array_resize_layers ? "awsm_hip_texture_array_resize_layers"
@@ -212,9 +217,25 @@ struct AwsmHost {
     std::unordered_map<SlotKey, uint32_t> skin_sets;
     DynamicStorageBuffer skin_matrices{16 * 4 * 32}, skin_index_weights{4096 * 2};
     bool skin_matrices_dirty = true, skin_iw_dirty = true;
+    // One record per (skin, joint), in insertion order: what skins.rs:162-194 walks, indexed by the joint's transform key so that a frame costs
+    // O(joints that moved).  With device posing on, a record is also resident on the device under the same id (awsm_hip_skin_pose_records_write).
+    struct PoseRecord { SlotKey skin, joint; uint32_t joint_index; };
+    std::vector<PoseRecord> pose_records;
+    std::unordered_map<SlotKey, std::vector<uint32_t>> joint_records;      // transform key -> record ids
+    bool device_posing = false;
+    uint32_t pose_records_sent = 0;              // records [0, sent) are on the device as they are here
+    std::vector<uint32_t> pose_records_resend;   // ... but for these, whose inverse bind matrix a later skin replaced
+    std::vector<uint32_t> pose_ids;              // records the next render has the device compose (sorted at render)
+    std::vector<uint32_t> pose_ids_last;         // ... and what the last render handed over
+    std::unordered_set<uint32_t> pose_stale;     // records whose matrix in the host mirror is older than the device's
     SlotMap<uint32_t> morphs;             // targets_len
     DynamicStorageBuffer morph_weights{4096}, morph_values{4096};
     bool morph_weights_dirty = true, morph_values_dirty = true;
+
+    // ---- animation/animations.rs:39-44: players; SecondaryMaps iterate in slot order ----
+    SlotMap<anim::Player> players;
+    std::map<uint32_t, std::pair<SlotKey, SlotKey>> anim_transforms, anim_morphs;      // slot index -> (animation key, transform key / mesh key)
+    std::vector<AwsmKey> gltf_animation_keys;      // what the last awsm_host_load_gltf made
 
     // ---- camera.rs ----
     uint8_t camera_raw[512] = {};
@@ -562,6 +583,76 @@ int finalize_pool_array(AwsmHost* h, uint32_t i, uint32_t levels) {
     return AWSM_OK;
 }
 
+// skins.rs:162-194 for one record: world * inverse_bind of the joint, as the mirror holds it
+Mat4 skin_matrix(AwsmHost* h, const AwsmHost::PoseRecord& r) {
+    Mat4 wm = h->world[r.joint];
+    auto ib = h->inverse_bind.find(r.joint);
+    if (ib != h->inverse_bind.end()) wm = mat4_mul(wm, ib->second);
+    return wm;
+}
+
+// Device posing: the matrices the device composed since the mirror was last looked at, composed here too (a cold path: awsm_host_mirror, and in
+// front of a flush that may write the whole mirror).  The bytes are the device's, so nothing is marked dirty.
+void sync_skin_mirror(AwsmHost* h) {
+    for (uint32_t id : h->pose_stale) {
+        const AwsmHost::PoseRecord& r = h->pose_records[id];
+        if (!h->skin_matrices.contains(r.skin) || !h->world.count(r.joint)) continue;
+        const Mat4 wm = skin_matrix(h, r);
+        h->skin_matrices.write_untracked(r.skin, (size_t)r.joint_index * 64, reinterpret_cast<const uint8_t*>(&wm), 64);
+    }
+    h->pose_stale.clear();
+}
+
+// Device posing: everything the device has composed or was still to compose, settled on the host with the inverse bind matrices as they are now —
+// the mirror brought up to date, and the joints not yet handed to the device composed here and marked for upload.  Called before anything changes
+// what a record means (a skin insert replaces the inverse bind matrices of the joints it shares; posing is switched off).
+void settle_pose_on_host(AwsmHost* h) {
+    sync_skin_mirror(h);
+    for (uint32_t id : h->pose_ids) {
+        const AwsmHost::PoseRecord& r = h->pose_records[id];
+        if (!h->skin_matrices.contains(r.skin) || !h->world.count(r.joint)) continue;
+        const Mat4 wm = skin_matrix(h, r);
+        h->skin_matrices.write_range(r.skin, (size_t)r.joint_index * 64, reinterpret_cast<const uint8_t*>(&wm), 64);
+        h->skin_matrices_dirty = true;
+    }
+    h->pose_ids.clear();
+}
+
+AwsmSkinPoseRecord device_record(AwsmHost* h, const AwsmHost::PoseRecord& r) {
+    AwsmSkinPoseRecord d{};
+    const long long to = h->transforms_buf.offset(r.joint), mo = h->skin_matrices.offset(r.skin);      // a removed joint or skin is never listed again
+    d.transform_offset = to < 0 ? 0u : (uint32_t)to;
+    d.matrix_offset = mo < 0 ? 0u : (uint32_t)(mo + (long long)r.joint_index * 64);
+    Mat4 ib = mat4_identity();
+    auto it = h->inverse_bind.find(r.joint);
+    if (it != h->inverse_bind.end()) ib = it->second;
+    memcpy(d.inverse_bind, &ib, 64);
+    return d;
+}
+
+// the records the device does not have yet, or has with an older inverse bind matrix
+int send_pose_records(AwsmHost* h) {
+    int rc;
+    std::sort(h->pose_records_resend.begin(), h->pose_records_resend.end());
+    for (uint32_t id : h->pose_records_resend) {
+        if (id >= h->pose_records_sent) continue;
+        const AwsmSkinPoseRecord d = device_record(h, h->pose_records[id]);
+        if ((rc = h->be.skin_pose_records_write(h->ctx, id, 1u, &d))) return dev_fail(h, rc, "skin_pose_records_write");
+        h->upload_bytes += sizeof d;
+    }
+    h->pose_records_resend.clear();
+    const uint32_t total = (uint32_t)h->pose_records.size();
+    if (h->pose_records_sent < total) {
+        std::vector<AwsmSkinPoseRecord> recs;
+        recs.reserve(total - h->pose_records_sent);
+        for (uint32_t id = h->pose_records_sent; id < total; id++) recs.push_back(device_record(h, h->pose_records[id]));
+        if ((rc = h->be.skin_pose_records_write(h->ctx, h->pose_records_sent, (uint32_t)recs.size(), recs.data()))) return dev_fail(h, rc, "skin_pose_records_write");
+        h->upload_bytes += recs.size() * sizeof(AwsmSkinPoseRecord);
+        h->pose_records_sent = total;
+    }
+    return AWSM_OK;
+}
+
 template <typename T>
 bool load_sym(AwsmHost* h, T& fn, const char* name) {
     fn = reinterpret_cast<T>(dlsym(h->be.dl, name));
@@ -603,6 +694,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.texture_array_write_layers = reinterpret_cast<decltype(b.texture_array_write_layers)>(dlsym(b.dl, "awsm_hip_texture_array_write_layers"));
     b.texture_array_generate_mips_layers = reinterpret_cast<decltype(b.texture_array_generate_mips_layers)>(dlsym(b.dl, "awsm_hip_texture_array_generate_mips_layers"));
     b.texture_array_info = reinterpret_cast<decltype(b.texture_array_info)>(dlsym(b.dl, "awsm_hip_texture_array_info"));
+    b.skin_pose_records_write = reinterpret_cast<decltype(b.skin_pose_records_write)>(dlsym(b.dl, "awsm_hip_skin_pose_records_write"));      // optional (awsm_host_set_device_skin_posing)
+    b.skin_pose = reinterpret_cast<decltype(b.skin_pose)>(dlsym(b.dl, "awsm_hip_skin_pose"));
     if (b.abi_version() != AWSM_HIP_ABI_VERSION) { dlclose(b.dl); return AWSM_ERR_INVALID_ARGUMENT; }
     AwsmConfig cfg{};
     cfg.struct_size = sizeof cfg; cfg.abi_version = AWSM_HIP_ABI_VERSION; cfg.device = device; cfg.flags = cfg_flags; cfg.stream = stream;
@@ -688,6 +781,24 @@ int awsm_host_transform_world(AwsmHost* h, AwsmKey key, float out[16]) {
     if (it == h->world.end()) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[transform] world transform does not exist");
     memcpy(out, &it->second, 64);
     return AWSM_OK;
+}
+
+int awsm_host_transform_get_local(AwsmHost* h, AwsmKey key, float t[3], float r[4], float s[3]) {   // transforms.rs:229-233
+    const Transform* tr = h->locals.get(key);
+    if (!tr) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[transform] local transform does not exist");
+    if (t) { t[0] = tr->t.x; t[1] = tr->t.y; t[2] = tr->t.z; }
+    if (r) { r[0] = tr->r.x; r[1] = tr->r.y; r[2] = tr->r.z; r[3] = tr->r.w; }
+    if (s) { s[0] = tr->s.x; s[1] = tr->s.y; s[2] = tr->s.z; }
+    return AWSM_OK;
+}
+
+AwsmKey awsm_host_transform_duplicate(AwsmHost* h, AwsmKey key) {   // transforms.rs:151-155
+    const Transform* tr = h->locals.get(key);
+    if (!tr) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "[transform] local transform does not exist"); return 0; }
+    const Transform copy = *tr;
+    const float t[3] = {copy.t.x, copy.t.y, copy.t.z}, r[4] = {copy.r.x, copy.r.y, copy.r.z, copy.r.w}, s[3] = {copy.s.x, copy.s.y, copy.s.z};
+    auto pit = h->parents.find(key);      // get_parent(key).ok(): the root has none, and insert(.., None) parents to the root
+    return awsm_host_transform_insert(h, t, r, s, pit == h->parents.end() ? 0 : pit->second);
 }
 
 // ------------------------------------------------------------------------------------------------ textures
@@ -810,6 +921,9 @@ int64_t awsm_host_material_offset(AwsmHost* h, AwsmKey key) { return h->material
 AwsmKey awsm_host_skin_insert(AwsmHost* h, const AwsmKey* joints, uint32_t n_joints, const float* inverse_bind, uint32_t set_count,
                               const uint32_t* const* joints_per_set, const float* const* weights_per_set, uint32_t vertex_count) {
     if (!joints || !n_joints || !set_count || !joints_per_set || !weights_per_set) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "skin_insert: bad argument"); return 0; }
+    // before inverse_bind changes below: what was composed, or is still to be, with the matrices of the earlier skins is theirs (and the insert
+    // may grow the buffer, after which the whole mirror goes up)
+    if (h->device_posing) settle_pose_on_host(h);
     std::vector<uint8_t> fill;
     std::vector<SlotKey> jv(joints, joints + n_joints);
     for (uint32_t j = 0; j < n_joints; j++) {   // skins.rs:84-143
@@ -821,6 +935,12 @@ AwsmKey awsm_host_skin_insert(AwsmHost* h, const AwsmKey* joints, uint32_t n_joi
     }
     SlotKey sk = h->skins.insert(jv);
     h->skin_matrices.update(sk, fill.data(), fill.size());
+    for (uint32_t j = 0; j < n_joints; j++) {
+        std::vector<uint32_t>& ids = h->joint_records[joints[j]];
+        for (uint32_t id : ids) h->pose_records_resend.push_back(id);      // inverse_bind is keyed by the joint: an earlier skin's record now has this one's
+        ids.push_back((uint32_t)h->pose_records.size());
+        h->pose_records.push_back({sk, joints[j], j});
+    }
     h->skin_sets[sk] = set_count;
     // gltf/buffers/skin.rs:22-113: per vertex, per set, 4 x {u32 joint, f32 weight}
     std::vector<uint8_t> iw((size_t)vertex_count * set_count * 32);
@@ -835,6 +955,8 @@ AwsmKey awsm_host_skin_insert(AwsmHost* h, const AwsmKey* joints, uint32_t n_joi
     h->skin_matrices_dirty = h->skin_iw_dirty = true;
     return sk;
 }
+
+int64_t awsm_host_skin_matrices_offset(AwsmHost* h, AwsmKey skin) { return h->skin_matrices.offset(skin); }   // skins.rs:146-152
 
 // ------------------------------------------------------------------------------------------------ meshes
 static AwsmKey mesh_insert_impl(AwsmHost* h, const AwsmHostPrimitive* p, AwsmKey transform, AwsmKey material, AwsmKey skin, uint32_t hidden, bool hud);
@@ -983,6 +1105,18 @@ int awsm_host_mesh_remove(AwsmHost* h, AwsmKey mesh) {
     return AWSM_OK;
 }
 
+int awsm_host_mesh_update_morph_weights(AwsmHost* h, AwsmKey mesh, const float* weights, uint32_t n) {   // morphs.rs:197-217
+    const MeshRec* rec = h->meshes.get(mesh);
+    if (!rec) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[mesh] not found");
+    const uint32_t* targets = rec->morph_key ? h->morphs.get(rec->morph_key) : nullptr;
+    if (!targets) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "mesh_update_morph_weights: the mesh has no morph targets");
+    if (n != *targets || !weights) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "mesh_update_morph_weights: %u weights for %u targets", n, *targets);
+    // the callback sees floats [1, n + 1) of the block (the reference's offset-by-one, kept: DESIGN.md section 3)
+    h->morph_weights.update_with_unchecked(rec->morph_key, [&](size_t, uint8_t* blk, size_t) { memcpy(blk + 4, weights, (size_t)n * 4); });
+    h->morph_weights_dirty = true;
+    return AWSM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ instancing (meshes.rs:176-290, instances.rs)
 static std::vector<uint8_t> instance_bytes(const Transform* list, size_t n) {   // Instances::transforms_to_bytes: to_matrix().to_cols_array() each
     std::vector<uint8_t> out(n * 64);
@@ -1032,6 +1166,14 @@ AwsmKey awsm_host_light_insert(AwsmHost* h, const AwsmHostLight* l) {
 int awsm_host_light_remove(AwsmHost* h, AwsmKey key) {
     if (!h->lights.remove(key)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[light] not found");
     h->punctual_dirty = h->lights_info_dirty = true;
+    return AWSM_OK;
+}
+int awsm_host_light_update(AwsmHost* h, AwsmKey key, const AwsmHostLight* l) {   // lights.rs:218-224
+    AwsmHostLight* cur = h->lights.get(key);
+    if (!cur) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[light] not found");
+    if (!l || l->kind < 1 || l->kind > 3) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "light_update: bad kind");
+    *cur = *l;
+    h->punctual_dirty = true;
     return AWSM_OK;
 }
 int awsm_host_set_ibl_mip_counts(AwsmHost* h, uint32_t prefiltered, uint32_t irradiance) {
@@ -1197,6 +1339,142 @@ int awsm_host_set_shard_bands(AwsmHost* h, uint32_t n, uint32_t r, uint32_t comp
     return AWSM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ animation (animation/animations.rs)
+static bool clip_to_player(AwsmHost* h, const AwsmHostAnimationClip* c, anim::Player& p) {
+    if (!c || c->struct_size < sizeof(AwsmHostAnimationClip)) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert: struct_size %u", c ? c->struct_size : 0u); return false; }
+    if (c->n_keys == 0 || !c->times || !c->values) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert: a clip without keys"); return false; }   // deviation: the reference panics at the first sample
+    if (c->interpolation == AWSM_ANIM_CUBICSPLINE && (!c->in_tangents || !c->out_tangents)) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert: a cubic clip without tangents"); return false; }
+    anim::Sampler& s = p.sampler;
+    s.path = c->path; s.interpolation = c->interpolation; s.width = c->width;
+    const size_t total = (size_t)c->n_keys * c->width;
+    s.times.assign(c->times, c->times + c->n_keys);
+    s.values.assign(c->values, c->values + total);
+    if (c->interpolation == AWSM_ANIM_CUBICSPLINE) { s.in_tangents.assign(c->in_tangents, c->in_tangents + total); s.out_tangents.assign(c->out_tangents, c->out_tangents + total); }
+    if (!s.valid()) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert: path %u, interpolation %u, width %u do not fit", c->path, c->interpolation, c->width); return false; }
+    p.duration = c->duration;
+    return true;
+}
+
+AwsmKey awsm_host_animation_insert_transform(AwsmHost* h, const AwsmHostAnimationClip* clip, AwsmKey transform) {   // animations.rs:60-68
+    anim::Player p;
+    if (!clip_to_player(h, clip, p)) return 0;
+    if (p.sampler.path == anim::kWeights) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert_transform: a weights clip animates a mesh"); return 0; }
+    if (!h->locals.contains(transform) || transform == h->root) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "[transform] local transform does not exist"); return 0; }
+    const SlotKey k = h->players.insert(std::move(p));
+    h->anim_transforms[key_idx(k)] = {k, transform};
+    return k;
+}
+
+AwsmKey awsm_host_animation_insert_morph(AwsmHost* h, const AwsmHostAnimationClip* clip, AwsmKey mesh) {   // animations.rs:71-79
+    anim::Player p;
+    if (!clip_to_player(h, clip, p)) return 0;
+    if (p.sampler.path != anim::kWeights) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert_morph: only a weights clip animates a mesh"); return 0; }
+    const MeshRec* rec = h->meshes.get(mesh);
+    const uint32_t* targets = rec && rec->morph_key ? h->morphs.get(rec->morph_key) : nullptr;
+    if (!targets) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert_morph: the mesh has no morph targets"); return 0; }
+    if (p.sampler.width != *targets) { fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_insert_morph: width %u for %u targets", p.sampler.width, *targets); return 0; }
+    const SlotKey k = h->players.insert(std::move(p));
+    h->anim_morphs[key_idx(k)] = {k, mesh};
+    return k;
+}
+
+int awsm_host_animation_remove(AwsmHost* h, AwsmKey key) {   // animations.rs:53-57
+    if (!h->players.remove(key)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] not found");
+    h->anim_transforms.erase(key_idx(key));
+    h->anim_morphs.erase(key_idx(key));
+    return AWSM_OK;
+}
+
+int awsm_host_animation_set_playback(AwsmHost* h, AwsmKey key, double speed, int loop_style, int direction, int state) {
+    anim::Player* p = h->players.get(key);
+    if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] not found");
+    if (loop_style < -1 || loop_style > 1 || direction < 0 || direction > 1 || state < 0 || state > 2) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_set_playback: loop style %d, direction %d, state %d", loop_style, direction, state);
+    p->speed = speed; p->loop_style = loop_style; p->direction = direction; p->state = state;
+    return AWSM_OK;
+}
+
+int awsm_host_animation_seek(AwsmHost* h, AwsmKey key, double local_time) {
+    anim::Player* p = h->players.get(key);
+    if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] not found");
+    if (!std::isfinite(local_time)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_seek: the time is not finite");
+    p->local_time = local_time;
+    return AWSM_OK;
+}
+
+int awsm_host_animation_state(AwsmHost* h, AwsmKey key, AwsmHostAnimationState* out) {
+    const anim::Player* p = h->players.get(key);
+    if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] not found");
+    if (!out || out->struct_size < sizeof(AwsmHostAnimationState)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "animation_state: struct_size");
+    out->direction = p->direction; out->state = p->state; out->loop_style = p->loop_style;
+    out->local_time = p->local_time; out->duration = p->duration; out->speed = p->speed;
+    return AWSM_OK;
+}
+
+int awsm_host_animation_sample(AwsmHost* h, AwsmKey key, float* out, uint32_t cap) {   // player.rs:105-107
+    const anim::Player* p = h->players.get(key);
+    if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] not found");
+    if (!out) return (int)p->sampler.width;      // the query
+    if (cap < p->sampler.width) return fail(h, AWSM_ERR_OUT_OF_RANGE, "animation_sample: room for %u of %u floats", cap, p->sampler.width);
+    anim::sample(p->sampler, p->local_time, out);
+    return (int)p->sampler.width;
+}
+
+int awsm_host_update_animations(AwsmHost* h, double global_time_delta) {   // animations.rs:84-141
+    for (anim::Player& p : h->players.values()) p.update(global_time_delta);
+    std::vector<float> v;
+    for (const auto& kv : h->anim_transforms) {
+        const anim::Player* p = h->players.get(kv.second.first);
+        if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] missing key");
+        const SlotKey tk = kv.second.second;
+        const Transform* cur = h->locals.get(tk);      // get_local
+        if (!cur) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[transform] local transform does not exist");
+        Transform t = *cur;
+        float q[4];
+        anim::sample(p->sampler, p->local_time, q);
+        if (p->sampler.path == anim::kTranslation) t.t = {q[0], q[1], q[2]};      // TransformAnimation::apply (data.rs:188-199)
+        else if (p->sampler.path == anim::kRotation) t.r = {q[0], q[1], q[2], q[3]};
+        else t.s = {q[0], q[1], q[2]};
+        const float tt[3] = {t.t.x, t.t.y, t.t.z}, rr[4] = {t.r.x, t.r.y, t.r.z, t.r.w}, ss[3] = {t.s.x, t.s.y, t.s.z};
+        int rc = awsm_host_transform_set_local(h, tk, tt, rr, ss);
+        if (rc) return rc;
+    }
+    for (const auto& kv : h->anim_morphs) {
+        const anim::Player* p = h->players.get(kv.second.first);
+        if (!p) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "[animation] missing key");
+        v.resize(p->sampler.width);
+        anim::sample(p->sampler, p->local_time, v.data());
+        int rc = awsm_host_mesh_update_morph_weights(h, kv.second.second, v.data(), (uint32_t)v.size());
+        if (rc) return rc;
+    }
+    return AWSM_OK;
+}
+
+// the glTF reader (gltf.cpp) leaves the keys of the players it made here; hidden: internal to the library
+__attribute__((visibility("hidden"))) void awsm_host_gltf_set_animation_keys(AwsmHost* h, const AwsmKey* keys, uint32_t n) { h->gltf_animation_keys.assign(keys, keys + n); }
+int awsm_host_gltf_animation_keys(AwsmHost* h, AwsmKey* out, uint32_t cap, uint32_t* n) {
+    if (!h || !n) return AWSM_ERR_INVALID_ARGUMENT;
+    *n = (uint32_t)h->gltf_animation_keys.size();
+    if (out) memcpy(out, h->gltf_animation_keys.data(), std::min<size_t>(cap, h->gltf_animation_keys.size()) * sizeof(AwsmKey));
+    return AWSM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ device skin posing
+int awsm_host_set_device_skin_posing(AwsmHost* h, int on) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (on && (!h->be.skin_pose_records_write || !h->be.skin_pose))
+        return fail(h, AWSM_ERR_NOT_READY, "set_device_skin_posing: the backend library has no %s", !h->be.skin_pose_records_write ? "awsm_hip_skin_pose_records_write" : "awsm_hip_skin_pose");
+    if (!on && h->device_posing) settle_pose_on_host(h);      // back to the host: what the device was still to compose is composed here and uploaded
+    h->device_posing = on != 0;
+    return AWSM_OK;
+}
+
+int awsm_host_skin_pose_ids_last_frame(AwsmHost* h, uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!h || !n) return AWSM_ERR_INVALID_ARGUMENT;
+    *n = (uint32_t)h->pose_ids_last.size();
+    if (out) memcpy(out, h->pose_ids_last.data(), std::min<size_t>(cap, h->pose_ids_last.size()) * 4);
+    return AWSM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ frame
 int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes.rs:872-939
     h->transforms_gpu_dirty = h->transforms_gpu_dirty || !h->dirties.empty();
@@ -1213,16 +1491,18 @@ int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes
             if (m) { m->world_aabb = aabb_transformed(m->local_aabb, kv.second); m->has_world_aabb = true; }
         }
     }
-    const auto& skeys = h->skins.keys();   // skins.rs:162-194
-    for (size_t i = 0; i < skeys.size(); i++) {
-        const std::vector<SlotKey>& joints = h->skins.values()[i];
-        for (size_t j = 0; j < joints.size(); j++) {
-            auto dit = dirty.find(joints[j]);
-            if (dit == dirty.end()) continue;
-            Mat4 wm = dit->second;
-            auto ib = h->inverse_bind.find(joints[j]);
-            if (ib != h->inverse_bind.end()) wm = mat4_mul(wm, ib->second);
-            h->skin_matrices.update_with_unchecked(skeys[i], [&](size_t, uint8_t* blk, size_t) { memcpy(blk + j * 64, &wm, 64); });
+    // skins.rs:162-194 walks every joint of every skin and asks whether it is dirty; the index built at skin_insert finds the same (skin, joint)
+    // pairs from the dirty keys, and the bytes written are the same
+    for (auto& kv : dirty) {
+        auto rit = h->joint_records.find(kv.first);
+        if (rit == h->joint_records.end()) continue;
+        for (uint32_t id : rit->second) {
+            const AwsmHost::PoseRecord& r = h->pose_records[id];
+            if (h->device_posing) { h->pose_ids.push_back(id); h->pose_stale.insert(id); continue; }      // composed by the device at the next render
+            const Mat4 wm = skin_matrix(h, r);
+            // the matrix's 64 bytes alone are marked dirty: the reference marks the skin's whole block (update_with_unchecked, skins.rs:182-188) and
+            // uploads it whichever joints moved; the bytes that reach the device are the same
+            h->skin_matrices.write_range(r.skin, (size_t)r.joint_index * 64, reinterpret_cast<const uint8_t*>(&wm), 64);
             h->skin_matrices_dirty = true;
         }
     }
@@ -1263,7 +1543,20 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
         h->lights_info_dirty = false;
     }
     if ((rc = flush_buffer(h, h->instances, AWSM_BUF_INSTANCES, h->instances_dirty))) return rc;   // instances.write_gpu: after lights, before skins (render.rs:73-80)
+    if (h->device_posing && h->skin_matrices_dirty) sync_skin_mirror(h);      // a skin came or went: the flush may write the whole mirror, so it has to be the device's bytes
     if ((rc = flush_buffer(h, h->skin_matrices, AWSM_BUF_SKIN_MATRICES, h->skin_matrices_dirty))) return rc;
+    h->pose_ids_last.clear();
+    if (h->device_posing) {      // AWSM_BUF_TRANSFORMS went up above: the device composes the joints that moved from the world matrices it has
+        if ((rc = send_pose_records(h))) return rc;
+        std::sort(h->pose_ids.begin(), h->pose_ids.end());
+        h->pose_ids.erase(std::unique(h->pose_ids.begin(), h->pose_ids.end()), h->pose_ids.end());
+        if (!h->pose_ids.empty()) {
+            if ((rc = h->be.skin_pose(h->ctx, h->pose_ids.data(), (uint32_t)h->pose_ids.size()))) return dev_fail(h, rc, "skin_pose");
+            h->upload_bytes += (uint64_t)h->pose_ids.size() * 4;
+        }
+        h->pose_ids_last.swap(h->pose_ids);
+        h->pose_ids.clear();
+    }
     if ((rc = flush_buffer(h, h->skin_index_weights, AWSM_BUF_SKIN_INDEX_WEIGHTS, h->skin_iw_dirty))) return rc;
     if ((rc = flush_buffer(h, h->morph_weights, AWSM_BUF_MORPH_WEIGHTS, h->morph_weights_dirty))) return rc;
     if ((rc = flush_buffer(h, h->morph_values, AWSM_BUF_MORPH_VALUES, h->morph_values_dirty))) return rc;
@@ -1354,7 +1647,7 @@ int awsm_host_mirror(AwsmHost* h, AwsmBuf which, const uint8_t** data, size_t* l
         case AWSM_BUF_TRANSFORMS: v = &h->transforms_buf.raw(); break;
         case AWSM_BUF_NORMAL_MATS: v = &h->normals_buf.raw(); break;
         case AWSM_BUF_MATERIALS: v = &h->materials_buf.raw(); break;
-        case AWSM_BUF_SKIN_MATRICES: v = &h->skin_matrices.raw(); break;
+        case AWSM_BUF_SKIN_MATRICES: sync_skin_mirror(h); v = &h->skin_matrices.raw(); break;
         case AWSM_BUF_SKIN_INDEX_WEIGHTS: v = &h->skin_index_weights.raw(); break;
         case AWSM_BUF_MORPH_WEIGHTS: v = &h->morph_weights.raw(); break;
         case AWSM_BUF_MORPH_VALUES: v = &h->morph_values.raw(); break;

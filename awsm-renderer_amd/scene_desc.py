@@ -117,6 +117,10 @@ class SceneDesc:
     prefiltered_mip_count: int = 9   # 256^2 cube with a full chain
     irradiance_mip_count: int = 9
     lut_size: int = 64
+    # glTF animations, carried by gltf_export / the glTF reader (populate() does not read them: players are made with Host.animation_insert_*):
+    # [{"name"?, "channels": [{"node", "path": translation | rotation | scale | weights, "interpolation": linear | step | cubic,
+    #   "times": (keys,), "values": (keys, width), "in_tangents" / "out_tangents": (keys, width) for cubic}]}]
+    animations: List[dict] = field(default_factory=list)
 
 
 

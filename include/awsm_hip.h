@@ -527,6 +527,26 @@ int awsm_hip_texture_array_write_layers(AwsmHipCtx* ctx, uint32_t array_idx, uin
 int awsm_hip_texture_array_generate_mips_layers(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t first_layer, uint32_t n_layers);
 int awsm_hip_texture_array_info(AwsmHipCtx* ctx, uint32_t array_idx, uint32_t* width, uint32_t* height, uint32_t* layers, uint32_t* mips);
 
+/* ---- skin matrices composed on the device (crates/renderer/src/meshes/skins.rs:162-194 does it on the CPU).  A record names one
+ * joint of one skin: where its world matrix lies in AWSM_BUF_TRANSFORMS, where its skin matrix goes in AWSM_BUF_SKIN_MATRICES (both byte offsets,
+ * multiples of 4), and its inverse bind matrix (column-major).  Records live in an array the context owns, which grows by doubling.
+ *   skin_pose_records_write   records [first, first + n); first may be at most the current count (no holes).  In stream order.
+ *   skin_pose                 for each listed record id, AWSM_BUF_SKIN_MATRICES[matrix_offset, +64) = world * inverse_bind, with the products and
+ *                             sums of glam's Mat4::mul_mat4 in its order, unfused: the bits the host computes.  Enqueued on the caller's stream with
+ *                             the ordering of an awsm_hip_buffer_write to AWSM_BUF_SKIN_MATRICES (behind the opaque passes in flight), and logged for
+ *                             the geometry cache like one, a range per run of adjacent matrices.  Neither reallocates nor synchronises.  Every id
+ *                             and every offset of a listed record is checked against the record count and the two buffers' sizes before anything is
+ *                             enqueued: AWSM_ERR_OUT_OF_RANGE, and nothing is written.  An id may be listed twice.
+ *   buffer_read               a synchronising read-back of bytes [offset, offset + len) of a scene buffer (tests, diagnostics). ---- */
+typedef struct AwsmSkinPoseRecord {
+    uint32_t transform_offset;
+    uint32_t matrix_offset;
+    float inverse_bind[16];
+} AwsmSkinPoseRecord;
+int awsm_hip_skin_pose_records_write(AwsmHipCtx* ctx, uint32_t first, uint32_t n, const AwsmSkinPoseRecord* records);
+int awsm_hip_skin_pose(AwsmHipCtx* ctx, const uint32_t* record_ids, uint32_t n);
+int awsm_hip_buffer_read(AwsmHipCtx* ctx, AwsmBuf which, size_t offset, void* dst, size_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,11 @@ int awsm_host_transform_set_parent(AwsmHost* h, AwsmKey child, AwsmKey parent);
 int awsm_host_transform_remove(AwsmHost* h, AwsmKey key);
 AwsmKey awsm_host_transform_parent(AwsmHost* h, AwsmKey child);          /* 0 if none */
 int awsm_host_transform_world(AwsmHost* h, AwsmKey key, float out_mat4[16]);
+/* Transforms::get_local (transforms.rs:229-233): the node's translation, rotation (xyzw) and scale as last set */
+int awsm_host_transform_get_local(AwsmHost* h, AwsmKey key, float translation[3], float rotation_xyzw[4], float scale[3]);
+/* Transforms::duplicate (transforms.rs:151-155): a new node with the same local transform under the same parent (children and meshes are not
+ * copied); returns its key, 0 on failure */
+AwsmKey awsm_host_transform_duplicate(AwsmHost* h, AwsmKey key);
 
 /* ---- Textures (textures.rs; renderer-core texture_pool): decoded RGBA8 images, one array per (w,h) ---- */
 int awsm_host_texture_insert(AwsmHost* h, const uint8_t* rgba8, uint32_t width, uint32_t height);   /* returns texture id >= 0; mip kind albedo */
@@ -118,6 +123,8 @@ int64_t awsm_host_material_offset(AwsmHost* h, AwsmKey key);
 AwsmKey awsm_host_skin_insert(AwsmHost* h, const AwsmKey* joint_transforms, uint32_t n_joints, const float* inverse_bind_mat4s,
                               uint32_t set_count, const uint32_t* const* joints_per_set, const float* const* weights_per_set, uint32_t vertex_count);
 
+int64_t awsm_host_skin_matrices_offset(AwsmHost* h, AwsmKey skin);      /* Skins::joint_matrices_offset (skins.rs:146-152): byte offset of the skin's first matrix in AWSM_BUF_SKIN_MATRICES, -1 if absent */
+
 /* ---- Meshes (meshes.rs:455-674; the gltf/buffers packers run inside) ---- */
 typedef struct AwsmHostMorphTarget { const float* positions; const float* normals; const float* tangents; } AwsmHostMorphTarget;  /* each vertex_count*3 or NULL */
 typedef struct AwsmHostPrimitive {
@@ -139,6 +146,10 @@ AwsmKey awsm_host_mesh_insert(AwsmHost* h, const AwsmHostPrimitive* prim, AwsmKe
  * MaterialMeshMeta, drawn by render() in the two HUD passes (render.rs:169-178,301-312) instead of the world's */
 AwsmKey awsm_host_mesh_insert_hud(AwsmHost* h, const AwsmHostPrimitive* prim, AwsmKey transform, AwsmKey material, AwsmKey skin, uint32_t hidden);
 int awsm_host_mesh_remove(AwsmHost* h, AwsmKey mesh);
+/* Morphs::update_morph_weights_with (meshes/morphs.rs:197-217) with a callback that copies `weights`: floats [1, n + 1) of the mesh's block in
+ * AWSM_BUF_MORPH_WEIGHTS (the reference's offset-by-one), uploaded with the next frame.  n must be the mesh's target count;
+ * a mesh without morph targets and a wrong n are AWSM_ERR_INVALID_ARGUMENT. */
+int awsm_host_mesh_update_morph_weights(AwsmHost* h, AwsmKey mesh, const float* weights, uint32_t n);
 
 /* ---- Lights (lights.rs:160-310) ---- */
 typedef struct AwsmHostLight {
@@ -149,6 +160,7 @@ typedef struct AwsmHostLight {
 } AwsmHostLight;
 AwsmKey awsm_host_light_insert(AwsmHost* h, const AwsmHostLight* l);
 int awsm_host_light_remove(AwsmHost* h, AwsmKey key);
+int awsm_host_light_update(AwsmHost* h, AwsmKey key, const AwsmHostLight* l);      /* Lights::update (lights.rs:218-224): punctual_gpu_dirty, as insert */
 int awsm_host_set_ibl_mip_counts(AwsmHost* h, uint32_t prefiltered, uint32_t irradiance);
 
 /* ---- Camera (camera.rs:17-28,111-227): column-major mat4s ---- */
@@ -228,8 +240,56 @@ int awsm_host_set_shard_bands(AwsmHost* h, uint32_t n, uint32_t r, uint32_t comp
  * off = awsm_hip_set_stage_timers(ctx, 0), the ms_* fields of the stats read 0 and the frame loses its event bubbles */
 int awsm_host_set_render_timings(AwsmHost* h, int enabled);
 
+/* ---- Animation (animation/{player,sampler,interpolate,data,clip,animations}.rs; host/animation.hpp has the rules, DESIGN.md section 15 the
+ * quirks kept and the deviations).  A clip animates one path of one target. ---- */
+enum { AWSM_ANIM_TRANSLATION = 0, AWSM_ANIM_ROTATION = 1, AWSM_ANIM_SCALE = 2, AWSM_ANIM_WEIGHTS = 3 };      /* path: width 3, 4, 3, the mesh's target count */
+enum { AWSM_ANIM_LINEAR = 0, AWSM_ANIM_STEP = 1, AWSM_ANIM_CUBICSPLINE = 2 };                                  /* interpolation */
+enum { AWSM_ANIM_LOOP_NONE = -1, AWSM_ANIM_LOOP = 0, AWSM_ANIM_PING_PONG = 1 };                                /* loop_style (Option<AnimationLoopStyle>) */
+enum { AWSM_ANIM_FORWARD = 0, AWSM_ANIM_BACKWARD = 1 };                                                        /* direction */
+enum { AWSM_ANIM_PLAYING = 0, AWSM_ANIM_PAUSED = 1, AWSM_ANIM_ENDED = 2 };                                     /* state */
+typedef struct AwsmHostAnimationClip {
+    uint32_t struct_size;      /* sizeof(AwsmHostAnimationClip) */
+    uint32_t path, interpolation, n_keys, width;
+    const double* times;       /* n_keys, ascending */
+    const float* values;       /* n_keys * width */
+    const float* in_tangents;  /* n_keys * width, AWSM_ANIM_CUBICSPLINE only */
+    const float* out_tangents;
+    double duration;           /* AnimationClip::duration; the glTF reader passes last key - first key (gltf/populate/animation.rs:107,229) */
+} AwsmHostAnimationClip;
+typedef struct AwsmHostAnimationState {
+    uint32_t struct_size;      /* IN: sizeof(AwsmHostAnimationState) */
+    int32_t direction, state, loop_style;
+    double local_time, duration, speed;
+} AwsmHostAnimationState;
+/* Animations::insert_transform / insert_morph with AnimationPlayer::new(clip) (speed 1/1000, Loop, Forward, Playing, local time 0).  Returns the
+ * AnimationKey, 0 on failure: no keys, a width other than the path's (the mesh's target count for weights), a path the target cannot take, an
+ * unknown target.  The arrays are copied. */
+AwsmKey awsm_host_animation_insert_transform(AwsmHost* h, const AwsmHostAnimationClip* clip, AwsmKey transform);
+AwsmKey awsm_host_animation_insert_morph(AwsmHost* h, const AwsmHostAnimationClip* clip, AwsmKey mesh);
+int awsm_host_animation_remove(AwsmHost* h, AwsmKey key);
+/* the player's public fields (player.rs:8-15): speed, loop_style, play_direction, and its state */
+int awsm_host_animation_set_playback(AwsmHost* h, AwsmKey key, double speed, int loop_style, int direction, int state);
+int awsm_host_animation_seek(AwsmHost* h, AwsmKey key, double local_time);      /* a finite time; nothing is applied until the next update */
+int awsm_host_animation_state(AwsmHost* h, AwsmKey key, AwsmHostAnimationState* out);
+/* AnimationPlayer::sample: the value at the player's local time into out[0, width), nothing applied.  Returns the width, or a negative status
+ * (cap < width: AWSM_ERR_OUT_OF_RANGE).  out = NULL asks for the width alone. */
+int awsm_host_animation_sample(AwsmHost* h, AwsmKey key, float* out, uint32_t cap);
+/* AwsmRenderer::update_animations (animations.rs:84-141): every player advances by global_time_delta * speed; then the transform players, in
+ * key order, overwrite their component of the node's local transform (get_local -> apply -> set_local); then the morph players write their mesh's
+ * weights (awsm_host_mesh_update_morph_weights).  Call it before awsm_host_update_transforms (update.rs:8-18). */
+int awsm_host_update_animations(AwsmHost* h, double global_time_delta);
+
+/* ---- Skin matrices composed on the device.  Off by default.  On: awsm_host_update_transforms no longer multiplies
+ * world * inverse_bind for the joints that moved; it collects their record ids, and awsm_host_render, after it has uploaded AWSM_BUF_TRANSFORMS,
+ * has the device compose them (awsm_hip_skin_pose) from the world matrices that are already there: 4 bytes per joint cross the bus instead of 64.
+ * The result is byte-identical to the host's, and awsm_host_mirror(AWSM_BUF_SKIN_MATRICES) still returns it (composed on the CPU when asked).
+ * AWSM_ERR_NOT_READY, naming the symbol, with a backend library that lacks awsm_hip_skin_pose_records_write or awsm_hip_skin_pose. ---- */
+int awsm_host_set_device_skin_posing(AwsmHost* h, int on);
+/* the record ids the last awsm_host_render handed to awsm_hip_skin_pose (sorted); n = their count */
+int awsm_host_skin_pose_ids_last_frame(AwsmHost* h, uint32_t* out, uint32_t cap, uint32_t* n);
+
 /* ---- frame: update_all (update.rs:8-18) + AwsmRenderer::render (render.rs:53-383, hot path only) ---- */
-int awsm_host_update_transforms(AwsmHost* h);
+int awsm_host_update_transforms(AwsmHost* h);      /* after awsm_host_update_animations, before awsm_host_camera_update */
 /* sync != 0: ends with awsm_hip_frame_end (stats filled if non-NULL); sync == 0: enqueue only */
 int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats);
 /* RenderHooks (crates/renderer/src/render.rs:54-63,181-190: pre_render / after_geometry_pass / ...): callbacks render() makes between
@@ -248,7 +308,11 @@ int awsm_host_mirror(AwsmHost* h, AwsmBuf which, const uint8_t** data, size_t* l
  * given, the reason (AWSM_ERR_UNSUPPORTED for arithmetic-coded / 12-bit / CMYK JPEG and KTX2 images, sparse accessors, point / line primitives, unknown required
  * extensions); objects inserted before the failure stay inserted. ---- */
 typedef struct AwsmGltfInfo {
-    uint32_t nodes, meshes, materials, images, samplers, skins, lights, triangles, generated_tangents, instanced_meshes, reserved[2];
+    uint32_t nodes, meshes, materials, images, samplers, skins, lights, triangles, generated_tangents, instanced_meshes;
+    /* the two words that were reserved (the struct carries no struct_size; its size and the fields before are unchanged): the players made from
+     * animations[].channels, and the channels passed over — a path other than translation / rotation / scale / weights, an input or output that is
+     * not a float accessor, a sampler without keys.  A second channel on a (node, path) is neither: the first one wins (populate.rs:229-268). */
+    uint32_t animations, animation_channels_skipped;
 } AwsmGltfInfo;
 int awsm_host_load_gltf(AwsmHost* h, const char* path, int scene_index, AwsmGltfInfo* info_out, char* err_out, size_t err_cap);
 /* The same with options.  AWSM_GLTF_SRGB_COLOR_TEXTURES: base colour, emissive, specular colour and sheen colour images are decoded from sRGB as
@@ -261,6 +325,9 @@ typedef struct AwsmGltfOptions {
     uint32_t flags;            /* AWSM_GLTF_* */
 } AwsmGltfOptions;
 int awsm_host_load_gltf_ex(AwsmHost* h, const char* path, const AwsmGltfOptions* options, AwsmGltfInfo* info_out, char* err_out, size_t err_cap);
+/* the AnimationKeys of the players the last awsm_host_load_gltf[_ex] on this host made, in insertion order: per node (depth first) translation,
+ * rotation, scale; then, as the meshes are inserted, one per primitive with targets of a node that has a weights channel.  *n = their count. */
+int awsm_host_gltf_animation_keys(AwsmHost* h, AwsmKey* out, uint32_t cap, uint32_t* n);
 /* the image decoders the reader uses (PNG: all colour types / bit depths, non-interlaced; JPEG: baseline / extended sequential Huffman,
  * 8-bit, grayscale or YCbCr) on their own: rgba_out = NULL queries the size; needs width * height * 4 bytes. */
 int awsm_host_decode_image(const uint8_t* data, size_t len, uint8_t* rgba_out, size_t cap, uint32_t* width, uint32_t* height, char* err_out, size_t err_cap);
