@@ -660,6 +660,58 @@ int awsm_hip_env_cube_filter(AwsmHipCtx* c, AwsmCube src, AwsmCube dst, const Aw
     return AWSM_OK;
 }
 
+// DESIGN.md §16.  Level 0 of an existing texel cube from an equirectangular panorama: the source goes to env_stage as a cube write's does (§12), one
+// launch of k_env_from_equirect projects it, and the level's apron is rebuilt.  Everything is checked before anything is enqueued.
+int awsm_hip_env_cube_from_equirect(AwsmHipCtx* c, AwsmCube which, const void* data, size_t data_len, const AwsmEquirect* p) {
+    { int rc = cube_id_ok(c, which, "env_cube_from_equirect"); if (rc) return rc; }
+    if (!data || !p || p->struct_size != sizeof(AwsmEquirect))
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: data, or a panorama description with struct_size %zu, is missing", sizeof(AwsmEquirect));
+    if (p->width == 0 || p->height == 0 || p->width > 32768u || p->height > 32768u)
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: a %ux%u panorama (1..32768 per side)", p->width, p->height);
+    if (p->samples > 8u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: %u samples per side (0 = auto, else 1..8)", p->samples);
+    if (!std::isfinite(p->yaw) || !std::isfinite(p->scale)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: yaw and scale must be finite");
+    if (p->format != (uint32_t)AWSM_PANO_RGBE8 && p->format != (uint32_t)AWSM_PANO_RGBA32F)
+        return fail(c, AWSM_ERR_UNSUPPORTED, "env_cube_from_equirect: unknown AwsmPanoFormat %u", p->format);
+    const uint32_t bpp = p->format == (uint32_t)AWSM_PANO_RGBE8 ? 4u : 16u;
+    const uint64_t tight = (uint64_t)p->width * bpp;
+    const uint64_t bpr = p->bytes_per_row ? (uint64_t)p->bytes_per_row : tight;
+    if (bpr < tight) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: bytes_per_row %u, a row of %u pixels takes %llu bytes", p->bytes_per_row, p->width, (unsigned long long)tight);
+    if (bpr > 0xFFFFFFFFull) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "env_cube_from_equirect: a row of %llu bytes", (unsigned long long)bpr);
+    const uint64_t used = bpr * (p->height - 1u) + tight;      // only the bytes the taps read: up to the end of the last row
+    if ((uint64_t)data_len < used)
+        return fail(c, AWSM_ERR_OUT_OF_RANGE, "env_cube_from_equirect: %zu bytes, a %ux%u panorama with rows of %llu bytes takes %llu", data_len, p->width, p->height,
+                    (unsigned long long)bpr, (unsigned long long)used);
+    const CubeDev cd = c->scene.cube[which];
+    if (!cd.texels) return fail(c, AWSM_ERR_NOT_READY, "env_cube_from_equirect: cube %d is a uniform colour or was never created", (int)which);
+
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }
+    int rc;
+    if (used <= (4u << 20)) {      // through the pinned ring to env_stage, as cube_write: the taps gather from device memory
+        uint8_t* st;
+        if ((rc = dev_reserve(c, c->env_stage, (size_t)used))) return rc;
+        if ((rc = stage_alloc(c, (size_t)used, &st))) return rc;
+        memcpy(st, data, (size_t)used);
+        HIPCHK(c, hipMemcpyAsync(c->env_stage.ptr, st, (size_t)used, hipMemcpyHostToDevice, c->stream));
+    } else {
+        if ((rc = stage_large_source(c, (const uint8_t*)data, (size_t)used))) return rc;
+    }
+    EnvEquirectArgs a{};
+    a.src = (const uint8_t*)c->env_stage.ptr;
+    a.dst = (uint2*)c->cube_tex[which].ptr + cd.level_off[0];
+    a.n = cd.size; a.width = p->width; a.height = p->height; a.format = p->format; a.bytes_per_row = (uint32_t)bpr;
+    // S = clamp(ceil(W / (4 N)), 1, 8): panorama pixels per cube texel along the equator
+    a.samples = p->samples ? p->samples : (uint32_t)std::min<uint64_t>(8u, std::max<uint64_t>(1u, ((uint64_t)p->width + 4ull * cd.size - 1u) / (4ull * cd.size)));
+    const double turns = (double)p->yaw / 6.283185307179586476925;      // reduced here in f64, so that a yaw of any magnitude costs the kernel's f32 nothing
+    a.turn = (float)(turns - std::floor(turns));
+    if (!(a.turn < 1.0f)) a.turn = 0.0f;                                 // a hair below a whole turn rounds to 1.0f
+    a.scale = p->scale == 0.0f ? 1.0f : p->scale;
+    awsm_launch_env_from_equirect(&a, c->stream);
+    cube_reborder(c, which, 0, 1);
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
 int awsm_hip_brdf_lut_generate(AwsmHipCtx* c, uint32_t width, uint32_t height) {
     if (!c || width == 0 || height == 0 || width > 8192 || height > 8192) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "brdf_lut_generate: bad size");
     HIPCHK(c, hipSetDevice(c->device));

@@ -52,4 +52,17 @@ struct EnvFilterLevel0Args {
     float lod;                  // max(0, log2(src.size / n)); unused when n == src.size (the bits are copied)
 };
 
+// k_env_from_equirect (awsm_hip_env_cube_from_equirect): an equirectangular panorama projected into level 0 of a cube
+struct EnvEquirectArgs {
+    const uint8_t* src;         // device staging: row y at src + y * bytes_per_row
+    uint2* dst;                 // level 0 of the plain chain
+    uint32_t n;                 // side of level 0
+    uint32_t width, height;     // of the panorama
+    uint32_t format;            // AwsmPanoFormat
+    uint32_t bytes_per_row;
+    uint32_t samples;           // S, 1..8 (auto resolved on the host)
+    float turn;                 // yaw / 2 pi reduced to [0, 1) on the host in f64
+    float scale;                // 0 resolved to 1 on the host
+};
+
 }  // namespace awsm

@@ -1,7 +1,7 @@
 // kernels_env.hip — environment cubes at run time (include/awsm_hip.h: awsm_hip_env_cube_write_face / _write_all_faces / _generate_mips /
 // _fill_colors / _fill_sky_gradient): source texels of eight formats -> RGBA16F, the 2x2 mip filter through five levels per launch, and the
-// expansion of a per-row colour table; and awsm_hip_env_cube_filter: a source cube filtered into a GGX-prefiltered chain or a
-// Lambert irradiance level.  The reference's counterparts are gpu.write_texture (renderer-core/src/cubemap.rs:180-228) and the mip
+// expansion of a per-row colour table; awsm_hip_env_cube_filter: a source cube filtered into a GGX-prefiltered chain or a
+// Lambert irradiance level; and awsm_hip_env_cube_from_equirect (§16): an equirectangular panorama projected into level 0.  The reference's counterparts are gpu.write_texture (renderer-core/src/cubemap.rs:180-228) and the mip
 // compute pass (renderer-core/src/texture/mipmap.rs:143-232, filter_simple for MipmapTextureKind::Albedo).  The arithmetic is DESIGN.md §12:
 // every conversion rounds to f16 once, to nearest even; nothing here may be contracted into an fma (-ffp-contract=off).
 // The apron of the changed levels is rebuilt afterwards by k_cube_border (kernels_shade.hip) by the seam rule of cube_seam.hpp.
@@ -253,8 +253,76 @@ __global__ __launch_bounds__(256) void k_env_filter_level0(EnvFilterLevel0Args a
     a.dst[idx] = pack_half4(f16_bits(s.x), f16_bits(s.y), f16_bits(s.z), kHalfOne);
 }
 
+// ---------------- level 0 from an equirectangular panorama (awsm_hip_env_cube_from_equirect) ----------------
+// One panorama pixel as RGB in f32.  RGBE8: e == 0 is black, else m * 2^(e - 136) by ldexp — exact (m < 2^8; e - 136 >= -135 stays above f32's last
+// denormal bit).  RGBA32F: the first three floats.  Any byte address: a padded bytes_per_row need not be a multiple of the pixel size.
+AWSM_DI f3 pano_pixel(const EnvEquirectArgs& a, uint32_t col, uint32_t row) {
+    const uint8_t* r = a.src + (uint64_t)row * a.bytes_per_row;
+    if (a.format == AWSM_PANO_RGBE8) {
+        uint32_t w[1]; load_texel<1>(r + (size_t)col * 4u, w);
+        const uint32_t e = w[0] >> 24;
+        if (e == 0u) return {0.0f, 0.0f, 0.0f};
+        const int k = (int)e - 136;
+        return {ldexpf((float)(w[0] & 255u), k), ldexpf((float)((w[0] >> 8) & 255u), k), ldexpf((float)((w[0] >> 16) & 255u), k)};
+    }
+    uint32_t w[3]; load_texel<3>(r + (size_t)col * 16u, w);
+    return {__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2])};
+}
+
+// One thread per level-0 texel, a workgroup = a 16 x 16 tile of one face (grid padded per face): neighbouring lanes look in neighbouring directions and
+// so read neighbouring panorama pixels.  Per texel S x S taps, b outer and a inner; per tap the direction through the sub-sample by §13's face table,
+// u = atan2(d.x, -d.z) / 2 pi + 0.5 + turn reduced to [0, 1], v = acos(d.y) / pi, and §3's bilinear rule at x = u W - 0.5, y = v H - 0.5 with columns
+// wrapped and rows clamped.  The mean times `scale`, NaN -> 0, clamped to f16's finite range, rounded once; alpha 1.0; one 8-byte store.
+__global__ __launch_bounds__(256) void k_env_from_equirect(EnvEquirectArgs a) {
+    const uint32_t i = blockIdx.x * 16u + (threadIdx.x & 15u), j = blockIdx.y * 16u + (threadIdx.x >> 4), face = blockIdx.z;
+    if (i >= a.n || j >= a.n) return;
+    const float fn = (float)a.n, fs = (float)a.samples, fw = (float)a.width, fh = (float)a.height;
+    const int wi = (int)a.width, hi = (int)a.height;
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f;
+    for (uint32_t sb_i = 0; sb_i < a.samples; sb_i++) {
+        const float t = (2.0f * ((float)j + ((float)sb_i + 0.5f) / fs)) / fn - 1.0f;
+        for (uint32_t sa_i = 0; sa_i < a.samples; sa_i++) {
+            const float s = (2.0f * ((float)i + ((float)sa_i + 0.5f) / fs)) / fn - 1.0f;
+            f3 d;
+            switch (face) {
+            case 0: d = {1.0f, -t, -s}; break;
+            case 1: d = {-1.0f, -t, s}; break;
+            case 2: d = {s, 1.0f, t}; break;
+            case 3: d = {s, -1.0f, -t}; break;
+            case 4: d = {s, -t, 1.0f}; break;
+            default: d = {-s, -t, -1.0f}; break;
+            }
+            d = normalize(d);
+            float u = (atan2f(d.x, -d.z) * 0.15915494f + 0.5f) + a.turn;                 // 1 / (2 pi)
+            u = u - floorf(u);                                                            // [0, 1]: 1.0 itself when u was a hair below an integer
+            const float v = acosf(fminf(fmaxf(d.y, -1.0f), 1.0f)) * 0.31830987f;          // 1 / pi
+            const float x = u * fw - 0.5f, y = v * fh - 0.5f;
+            const float flx = floorf(x), fly = floorf(y), fx = x - flx, fy = y - fly;
+            int x0 = (int)flx, x1 = x0 + 1, y0 = (int)fly, y1 = y0 + 1;                   // x0 in [-1, W - 1], y0 in [-1, H - 1]
+            if (x0 < 0) x0 += wi;
+            if (x1 >= wi) x1 -= wi;
+            // the columns are inside [0, W) by the reduction of u and the rows are clamped; the unsigned min keeps every load inside the source whatever u and v were
+            const uint32_t c0 = min((uint32_t)x0, a.width - 1u), c1 = min((uint32_t)x1, a.width - 1u);
+            const uint32_t r0 = (uint32_t)min(max(y0, 0), hi - 1), r1 = (uint32_t)min(max(y1, 0), hi - 1);
+            const f3 p00 = pano_pixel(a, c0, r0), p10 = pano_pixel(a, c1, r0), p01 = pano_pixel(a, c0, r1), p11 = pano_pixel(a, c1, r1);
+            const f3 tap = env_lerp3(env_lerp3(p00, p10, fx), env_lerp3(p01, p11, fx), fy);
+            sr += tap.x; sg += tap.y; sb += tap.z;
+        }
+    }
+    const float k = 1.0f / (fs * fs);
+    float r = (sr * k) * a.scale, g = (sg * k) * a.scale, b = (sb * k) * a.scale;
+    r = r == r ? fminf(fmaxf(r, -65504.0f), 65504.0f) : 0.0f;
+    g = g == g ? fminf(fmaxf(g, -65504.0f), 65504.0f) : 0.0f;
+    b = b == b ? fminf(fmaxf(b, -65504.0f), 65504.0f) : 0.0f;
+    a.dst[((size_t)face * a.n + j) * a.n + i] = pack_half4(f16_bits(r), f16_bits(g), f16_bits(b), kHalfOne);
+}
+
 }  // namespace awsm
 
+extern "C" void awsm_launch_env_from_equirect(const awsm::EnvEquirectArgs* a, hipStream_t s) {
+    const uint32_t tiles = (a->n + 15u) / 16u;
+    if (tiles) hipLaunchKernelGGL(awsm::k_env_from_equirect, dim3(tiles, tiles, 6), dim3(256), 0, s, *a);
+}
 extern "C" void awsm_launch_env_filter(const awsm::EnvFilterArgs* a, uint32_t blocks, hipStream_t s) {
     if (blocks) hipLaunchKernelGGL(awsm::k_env_filter, dim3(blocks), dim3(256), 0, s, *a);
 }

@@ -46,6 +46,7 @@ void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, u
 void awsm_launch_env_mips(const awsm::EnvMipArgs* a, hipStream_t s);
 void awsm_launch_env_filter(const awsm::EnvFilterArgs* a, uint32_t blocks, hipStream_t s);
 void awsm_launch_env_filter_level0(const awsm::EnvFilterLevel0Args* a, hipStream_t s);
+void awsm_launch_env_from_equirect(const awsm::EnvEquirectArgs* a, hipStream_t s);
 // kernels_texture.hip
 void awsm_launch_tex_write(const awsm::TexWriteArgs* a, hipStream_t s);
 void awsm_launch_tex_mips(const awsm::TexMipArgs* a, hipStream_t s);

@@ -36,7 +36,7 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_post_pass", "awsm_hip_read_display", "awsm_hip_read_effects", "awsm_hip_bind_display", "awsm_hip_display_device_ptr",
            "awsm_hip_env_cube_create", "awsm_hip_env_cube_write_face", "awsm_hip_env_cube_write_all_faces", "awsm_hip_env_cube_generate_mips",
            "awsm_hip_env_cube_fill_colors", "awsm_hip_env_cube_fill_sky_gradient", "awsm_hip_env_cube_info", "awsm_hip_env_cube_read_level",
-           "awsm_hip_env_cube_filter",
+           "awsm_hip_env_cube_filter", "awsm_hip_env_cube_from_equirect",
            "awsm_hip_texture_array_create", "awsm_hip_texture_array_resize_layers", "awsm_hip_texture_array_write_layers",
            "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info",
            "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read"]
@@ -65,6 +65,23 @@ class AwsmCubeLayout(C.Structure):
 
 class AwsmEnvFilter(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("size", C.c_uint32), ("mips", C.c_uint32), ("sample_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AwsmEquirect(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("bytes_per_row", C.c_uint32),
+                ("samples", C.c_uint32), ("yaw", C.c_float), ("scale", C.c_float)]
+
+
+AWSM_PANO_RGBE8, AWSM_PANO_RGBA32F = 0, 1
+
+
+def equirect_source(array, yaw=0.0, samples=0, scale=1.0):
+    """(contiguous array, AwsmEquirect) for a panorama: uint8 [H, W, 4] is RGBE, float32 [H, W, 4] is RGBA32F; anything else is a TypeError."""
+    a = np.ascontiguousarray(array)
+    if a.ndim != 3 or a.shape[2] != 4 or a.dtype not in (np.uint8, np.float32):
+        raise TypeError("a panorama is uint8 [H, W, 4] (RGBE) or float32 [H, W, 4], got %s %s" % (a.dtype, a.shape))
+    fmt = AWSM_PANO_RGBE8 if a.dtype == np.uint8 else AWSM_PANO_RGBA32F
+    return a, AwsmEquirect(C.sizeof(AwsmEquirect), a.shape[1], a.shape[0], fmt, 0, samples, yaw, scale)
 
 
 class AwsmTexWrite(C.Structure):
@@ -203,6 +220,7 @@ def load_library():
     lib.awsm_hip_env_cube_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.awsm_hip_env_cube_read_level.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     lib.awsm_hip_env_cube_filter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.awsm_hip_env_cube_from_equirect.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.awsm_hip_skin_pose_records_write.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.awsm_hip_skin_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.awsm_hip_buffer_read.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -431,6 +449,12 @@ class HipDevice:
             mips = 1 if k == 1 else int(size).bit_length()
         f = AwsmEnvFilter(C.sizeof(AwsmEnvFilter), k, size, mips, sample_count, 0)
         self._chk(self.lib.awsm_hip_env_cube_filter(self.ctx, src, dst, C.byref(f)), "env_cube_filter")
+
+    def env_cube_from_equirect(self, which: int, array, yaw: float = 0.0, samples: int = 0, scale: float = 1.0):
+        """An equirectangular panorama (uint8 [H, W, 4] RGBE or float32 [H, W, 4]) projected into level 0 of an existing texel cube (DESIGN.md section
+        16): row 0 is the zenith, the centre column looks along -Z at yaw 0.  samples 0 picks S from the sizes.  env_cube_generate_mips follows."""
+        a, pano = equirect_source(array, yaw, samples, scale)
+        self._chk(self.lib.awsm_hip_env_cube_from_equirect(self.ctx, which, a.ctypes.data_as(C.c_void_p), a.nbytes, C.byref(pano)), "env_cube_from_equirect")
 
     def env_upload(self, skybox=(0, 0, 0, 1), prefiltered=(1, 1, 1), irradiance=(1, 1, 1), lut_rgba16f: Optional[np.ndarray] = None):
         env = AwsmEnv()

@@ -128,6 +128,10 @@ def load_library():
         "awsm_host_ktx2_parse": (C.c_int, [vp, sz, vp, C.c_char_p, sz]),
         "awsm_host_env_cube_load_ktx2": (C.c_int, [vp, C.c_int, C.c_char_p, vp, C.c_char_p, sz]),
         "awsm_host_env_cube_load_ktx2_memory": (C.c_int, [vp, C.c_int, vp, sz, vp, C.c_char_p, sz]),
+        "awsm_host_hdr_info": (C.c_int, [vp, sz, vp, C.c_char_p, sz]), "awsm_host_hdr_decode": (C.c_int, [vp, sz, vp, sz, vp, C.c_char_p, sz]),
+        "awsm_host_env_cube_from_equirect": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+        "awsm_host_env_cube_load_hdr": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, C.c_char_p, sz]),
+        "awsm_host_env_cube_load_hdr_memory": (C.c_int, [vp, C.c_int, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp, C.c_char_p, sz]),
         "awsm_host_set_render_hooks": (C.c_int, [vp, vp, vp, vp, vp]),
         "awsm_host_brdf_lut_generate": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_resize": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "awsm_host_set_shard_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_set_shard_bands": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_set_render_timings": (C.c_int, [vp, C.c_int]),
@@ -186,6 +190,47 @@ class Ktx2Info(C.Structure):
         d["format_name"] = hip_backend.CUBE_FORMAT_NAMES.get(d["format"])
         d["level"] = [(int(self.level[i].offset), int(self.level[i].length)) for i in range(d["levels"])]
         return d
+
+
+class HdrInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flipped_y", C.c_uint32), ("rle", C.c_uint32), ("exposure", C.c_float)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("width", "height", "flipped_y", "rle")}
+        d["exposure"] = float(self.exposure)
+        return d
+
+
+def _hdr_error(where: str, rc: int, err) -> "HostError":
+    e = HostError(f"{where} failed ({rc}): {err.value.decode(errors='replace')}")
+    e.code = rc
+    return e
+
+
+def hdr_info(data: bytes) -> dict:
+    """awsm_host_hdr_info: the header of a Radiance .hdr picture (no host, no device); raises HostError with the reason."""
+    info = HdrInfo(struct_size=C.sizeof(HdrInfo))
+    err = C.create_string_buffer(512)
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
+    rc = load_library().awsm_host_hdr_info(buf, len(data), C.byref(info), err, 512)
+    if rc != 0:
+        raise _hdr_error("hdr_info", rc, err)
+    return info.as_dict()
+
+
+def hdr_decode(data: bytes, out_cap: Optional[int] = None):
+    """awsm_host_hdr_decode: -> (uint8 [H, W, 4] RGBE, top-down; the header dict).  out_cap: the size of the output buffer handed to the reader
+    (default: what the header asks for)."""
+    head = hdr_info(data)
+    need = head["width"] * head["height"] * 4
+    out = np.zeros(need if out_cap is None else out_cap, dtype=np.uint8)
+    info = HdrInfo(struct_size=C.sizeof(HdrInfo))
+    err = C.create_string_buffer(512)
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
+    rc = load_library().awsm_host_hdr_decode(buf, len(data), out.ctypes.data if out.size else None, out.size, C.byref(info), err, 512)
+    if rc != 0:
+        raise _hdr_error("hdr_decode", rc, err)
+    return out[:need].reshape(head["height"], head["width"], 4), info.as_dict()
 
 
 def ktx2_parse(data: bytes) -> dict:
@@ -487,6 +532,27 @@ class Host:
             e = HostError(f"env_cube_load_ktx2 failed ({rc}): {err.value.decode(errors='replace')}")
             e.code = rc
             raise e
+        return info.as_dict()
+
+    def env_cube_from_equirect(self, which: int, array, yaw: float = 0.0, samples: int = 0, scale: float = 1.0) -> dict:
+        """An equirectangular panorama (uint8 [H, W, 4] RGBE or float32 [H, W, 4]) into level 0 of an existing texel cube (DESIGN.md section 16);
+        env_cube_regenerate_mipmaps follows.  Returns what was sent: width, height, format, samples (0 = auto), yaw, scale."""
+        a, pano = hip_backend.equirect_source(array, yaw, samples, scale)
+        self._chk(self.lib.awsm_host_env_cube_from_equirect(self.h, which, a.ctypes.data, a.nbytes, C.byref(pano)), "env_cube_from_equirect")
+        return {"width": a.shape[1], "height": a.shape[0], "format": int(pano.format), "samples": samples, "yaw": yaw, "scale": scale}
+
+    def env_cube_load_hdr(self, which: int, source, size: int, samples: int = 0, yaw: float = 0.0, scale: float = 1.0) -> dict:
+        """A Radiance .hdr panorama from a path or from bytes: decoded, projected into a `size`^2 cube with its full chain.  Returns the header
+        (width, height, flipped_y, rle, exposure: EXPOSURE= is reported, not applied — pass scale = 1 / exposure for radiance)."""
+        info = HdrInfo(struct_size=C.sizeof(HdrInfo))
+        err = C.create_string_buffer(512)
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            buf = (C.c_uint8 * max(1, len(source))).from_buffer_copy(bytes(source) or b"\0")
+            rc = self.lib.awsm_host_env_cube_load_hdr_memory(self.h, which, buf, len(source), size, samples, yaw, scale, C.byref(info), err, 512)
+        else:
+            rc = self.lib.awsm_host_env_cube_load_hdr(self.h, which, os.fsencode(source), size, samples, yaw, scale, C.byref(info), err, 512)
+        if rc != 0:
+            raise _hdr_error("env_cube_load_hdr", rc, err)
         return info.as_dict()
 
     def brdf_lut_generate(self, w: int, h: int):

@@ -35,6 +35,7 @@
 #include "buffers.hpp"
 #include "glam.hpp"
 #include "ktx2.hpp"
+#include "rgbe.hpp"
 #include "../csrc/tex_pool.hpp"      // the sRGB table and the integer premultiply, shared with the device library
 
 using namespace awsm_host;
@@ -75,6 +76,7 @@ struct Backend {
     int (*env_cube_fill_colors)(AwsmHipCtx*, AwsmCube, uint32_t, const float*) = nullptr;
     int (*env_cube_fill_sky_gradient)(AwsmHipCtx*, AwsmCube, uint32_t, const float*, const float*) = nullptr;
     int (*env_cube_filter)(AwsmHipCtx*, AwsmCube, AwsmCube, const AwsmEnvFilter*) = nullptr;      // optional (awsm_host_env_bake_ibl)
+    int (*env_cube_from_equirect)(AwsmHipCtx*, AwsmCube, const void*, size_t, const AwsmEquirect*) = nullptr;      // optional (awsm_host_env_cube_from_equirect / _load_hdr)
     // optional: the texture pool at run time (awsm_host_texture_insert_ex / _update; finalize of a resident array)
     int (*texture_array_create)(AwsmHipCtx*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) = nullptr;
     int (*texture_array_resize_layers)(AwsmHipCtx*, uint32_t, uint32_t) = nullptr;
@@ -689,6 +691,7 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.env_cube_fill_colors = reinterpret_cast<decltype(b.env_cube_fill_colors)>(dlsym(b.dl, "awsm_hip_env_cube_fill_colors"));
     b.env_cube_fill_sky_gradient = reinterpret_cast<decltype(b.env_cube_fill_sky_gradient)>(dlsym(b.dl, "awsm_hip_env_cube_fill_sky_gradient"));
     b.env_cube_filter = reinterpret_cast<decltype(b.env_cube_filter)>(dlsym(b.dl, "awsm_hip_env_cube_filter"));
+    b.env_cube_from_equirect = reinterpret_cast<decltype(b.env_cube_from_equirect)>(dlsym(b.dl, "awsm_hip_env_cube_from_equirect"));
     b.texture_array_create = reinterpret_cast<decltype(b.texture_array_create)>(dlsym(b.dl, "awsm_hip_texture_array_create"));      // optional (the texture pool at run time)
     b.texture_array_resize_layers = reinterpret_cast<decltype(b.texture_array_resize_layers)>(dlsym(b.dl, "awsm_hip_texture_array_resize_layers"));
     b.texture_array_write_layers = reinterpret_cast<decltype(b.texture_array_write_layers)>(dlsym(b.dl, "awsm_hip_texture_array_write_layers"));
@@ -1238,6 +1241,9 @@ int awsm_host_env_cube_colors(AwsmHost* h, AwsmCube which, uint32_t size, const 
 int awsm_host_env_cube_sky_gradient(AwsmHost* h, AwsmCube which, uint32_t size, const float zenith[4], const float nadir[4]) {
     AWSM_ENV_CUBE_CALL(env_cube_fill_sky_gradient, "awsm_hip_env_cube_fill_sky_gradient", which, size, zenith, nadir);
 }
+int awsm_host_env_cube_from_equirect(AwsmHost* h, AwsmCube which, const void* data, size_t len, const AwsmEquirect* pano) {
+    AWSM_ENV_CUBE_CALL(env_cube_from_equirect, "awsm_hip_env_cube_from_equirect", which, data, len, pano);
+}
 #undef AWSM_ENV_CUBE_CALL
 // The two cubes the opaque pass lights with, filtered on the device from the skybox as it is now (the reference loads them ready-made: ibl.rs:19-28)
 int awsm_host_env_bake_ibl(AwsmHost* h, uint32_t prefiltered_size, uint32_t prefiltered_mips, uint32_t irradiance_size, uint32_t sample_count) {
@@ -1292,6 +1298,63 @@ int awsm_host_env_cube_load_ktx2(AwsmHost* h, AwsmCube which, const char* path, 
         return AWSM_ERR_INVALID_ARGUMENT;
     }
     return awsm_host_env_cube_load_ktx2_memory(h, which, bytes.data(), bytes.size(), info_out, err_out, err_cap);
+}
+
+// Radiance pictures (host/rgbe.hpp) and the skybox from one: the reference's first offline step, `cmgen -x skybox`, on the device
+int awsm_host_hdr_info(const uint8_t* data, size_t len, AwsmHdrInfo* out, char* err, size_t err_cap) { return rgbe::info(data, len, out, err, err_cap); }
+int awsm_host_hdr_decode(const uint8_t* data, size_t len, uint8_t* rgbe_out, size_t out_cap, AwsmHdrInfo* out, char* err, size_t err_cap) {
+    return rgbe::decode(data, len, rgbe_out, out_cap, out, err, err_cap);
+}
+
+// decode, create(size, full chain), from_equirect, generate_mips
+int awsm_host_env_cube_load_hdr_memory(AwsmHost* h, AwsmCube which, const uint8_t* data, size_t len, uint32_t size, uint32_t samples, float yaw, float scale,
+                                       AwsmHdrInfo* info_out, char* err_out, size_t err_cap) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    AwsmHdrInfo info{};
+    info.struct_size = sizeof info;
+    int rc = rgbe::info(data, len, &info, err_out, err_cap);
+    std::vector<uint8_t> pixels;
+    if (!rc) {
+        try { pixels.resize((size_t)info.width * info.height * 4u); }      // at most 2^30 bytes: the reader checked the extent
+        catch (const std::bad_alloc&) { return fail(h, AWSM_ERR_OUT_OF_MEMORY, "hdr: no memory for %u x %u pixels", info.width, info.height); }
+        rc = rgbe::decode(data, len, pixels.data(), pixels.size(), &info, err_out, err_cap);
+    }
+    if (rc) { h->last_error = (err_out && err_cap) ? err_out : "hdr: the file was refused"; return rc; }
+    uint32_t mips = 0;
+    for (uint32_t s = size; s; s >>= 1) mips++;
+    if (size == 0) rc = fail(h, AWSM_ERR_INVALID_ARGUMENT, "env_cube_load_hdr: size 0");
+    if (!rc) rc = awsm_host_env_cube_create(h, which, size, mips);
+    if (!rc) {
+        AwsmEquirect pano{};
+        pano.struct_size = sizeof pano; pano.width = info.width; pano.height = info.height; pano.format = AWSM_PANO_RGBE8;
+        pano.samples = samples; pano.yaw = yaw; pano.scale = scale;
+        rc = awsm_host_env_cube_from_equirect(h, which, pixels.data(), pixels.size(), &pano);
+    }
+    if (!rc && mips > 1) rc = awsm_host_env_cube_regenerate_mipmaps(h, which);
+    if (rc) { if (err_out && err_cap) snprintf(err_out, err_cap, "%s", h->last_error.c_str()); return rc; }
+    if (info_out) { const uint32_t theirs = info_out->struct_size; memcpy(info_out, &info, std::min<size_t>(theirs, sizeof info)); info_out->struct_size = std::min<uint32_t>(theirs, sizeof info); }
+    return AWSM_OK;
+}
+
+int awsm_host_env_cube_load_hdr(AwsmHost* h, AwsmCube which, const char* path, uint32_t size, uint32_t samples, float yaw, float scale, AwsmHdrInfo* info_out,
+                                char* err_out, size_t err_cap) {
+    if (!h || !path) return AWSM_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> bytes;
+    FILE* f = fopen(path, "rb");
+    bool ok = f != nullptr;
+    if (ok) {
+        uint8_t chunk[65536];
+        size_t got;
+        while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) bytes.insert(bytes.end(), chunk, chunk + got);
+        ok = !ferror(f);
+        fclose(f);
+    }
+    if (!ok) {
+        fail(h, AWSM_ERR_INVALID_ARGUMENT, "hdr: cannot read %s", path);
+        if (err_out && err_cap) snprintf(err_out, err_cap, "%s", h->last_error.c_str());
+        return AWSM_ERR_INVALID_ARGUMENT;
+    }
+    return awsm_host_env_cube_load_hdr_memory(h, which, bytes.data(), bytes.size(), size, samples, yaw, scale, info_out, err_out, err_cap);
 }
 
 int awsm_host_env(AwsmHost* h, const AwsmEnv* env) { int rc = h->be.env_upload(h->ctx, env); return rc ? dev_fail(h, rc, "env_upload") : AWSM_OK; }

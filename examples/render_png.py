@@ -9,6 +9,8 @@ RGBA8 display image as it stands (--dof uses the reference's focus distance 10 a
 --sky-gradient makes the skybox the reference's default gradient sky (CubemapImage::new_sky_gradient, 256^2 with its mip chain, built on the
 device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefiltered environment of the IBL.  With --bake-ibl the scene is lit
 by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
+--hdr FILE projects an equirectangular Radiance .hdr panorama into the skybox (--hdr-size N, default 512; --hdr-yaw R radians turns it about the
+vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl the scene is lit from the file.
 """
 import argparse
 import os
@@ -38,7 +40,10 @@ def main():
     ap.add_argument("--aperture", type=float, default=5.6)
     ap.add_argument("--sky-gradient", action="store_true", help="skybox = the default zenith / nadir gradient cube")
     ap.add_argument("--env-ktx2", metavar="PATH", help="a KTX2 cube map for the skybox and the prefiltered environment")
-    ap.add_argument("--bake-ibl", action="store_true", help="with --sky-gradient / --env-ktx2: filter the IBL cubes from the skybox on the device")
+    ap.add_argument("--hdr", metavar="FILE", help="an equirectangular Radiance .hdr panorama for the skybox")
+    ap.add_argument("--hdr-size", type=int, default=512, metavar="N", help="side of the skybox cube made from --hdr")
+    ap.add_argument("--hdr-yaw", type=float, default=0.0, metavar="R", help="radians added to the panorama's azimuth")
+    ap.add_argument("--bake-ibl", action="store_true", help="with --sky-gradient / --env-ktx2 / --hdr: filter the IBL cubes from the skybox on the device")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -53,14 +58,21 @@ def main():
     r = Renderer(sc, msaa=a.msaa, mipmap=a.mipmap, gltf=gltf)
     if a.sky_gradient:
         r.host.env_cube_sky_gradient(0, 256)
-    if a.bake_ibl and not (a.sky_gradient or a.env_ktx2):
-        ap.error("--bake-ibl filters the skybox cube: give --sky-gradient or --env-ktx2")
+    if a.bake_ibl and not (a.sky_gradient or a.env_ktx2 or a.hdr):
+        ap.error("--bake-ibl filters the skybox cube: give --sky-gradient, --env-ktx2 or --hdr")
     if a.env_ktx2:
         info = r.host.env_cube_load_ktx2(0, a.env_ktx2)
         if not a.bake_ibl:
             r.host.env_cube_load_ktx2(1, a.env_ktx2)
             r.host.set_ibl_mip_counts(info["mips"], sc.irradiance_mip_count)      # the prefiltered lookup scales roughness by the file's level count
         print(f"{a.env_ktx2}: {info['size']}^2 {info['format_name']}, {info['levels']} stored level(s), {info['mips']} in the cube")
+    if a.hdr:
+        from awsm_renderer_amd.host import hdr_info
+        with open(a.hdr, "rb") as fh:
+            data = fh.read()
+        exposure = hdr_info(data)["exposure"]
+        info = r.host.env_cube_load_hdr(0, data, a.hdr_size, yaw=a.hdr_yaw, scale=1.0 / exposure)
+        print(f"{a.hdr}: {info['width']}x{info['height']}{' (+Y)' if info['flipped_y'] else ''}, exposure {info['exposure']:g} -> skybox {a.hdr_size}^2 with its chain")
     if a.bake_ibl:
         r.host.env_bake_ibl(128, 6, 32)                                           # 128 64 32 16 8 4; sets the IBL mip counts
     post = a.tonemap is not None or a.bloom or a.dof or a.smaa

@@ -492,6 +492,29 @@ typedef struct AwsmEnvFilter {
 } AwsmEnvFilter;
 int awsm_hip_env_cube_filter(AwsmHipCtx* ctx, AwsmCube src, AwsmCube dst, const AwsmEnvFilter* filter);
 
+/* ---- a cube's level 0 from an equirectangular panorama (the reference gets its skybox from an offline tool) ----
+ * Projects a `width` x `height` panorama — row 0 the zenith, the centre column along -Z at yaw 0, +X at u = 0.75 — into level 0 of an existing texel
+ * cube (awsm_hip_env_cube_create first) and rebuilds that level's apron.  It makes no mips: awsm_hip_env_cube_generate_mips follows.  Each texel is the
+ * mean of samples x samples bilinear taps (columns wrap, rows clamp), times `scale`, NaN -> 0, clamped to +-65504 and rounded to f16 once; alpha 1.0.
+ *   AWSM_PANO_RGBE8    4 bytes per pixel, Radiance's R G B E: e == 0 is black, else m * 2^(e - 136) per channel (what awsm_host_hdr_decode writes).
+ *   AWSM_PANO_RGBA32F  four floats per pixel; the fourth is ignored.
+ * The §12 rules hold: enqueued on the context's stream behind the opaque passes in flight, no reallocation of the cube and no stream synchronise; a
+ * source of up to 4 MiB goes through the pinned staging ring, a larger one is copied from the caller's memory and the call waits for that copy alone.
+ * AWSM_ERR_NOT_READY: the cube is a uniform colour or was never created; AWSM_ERR_INVALID_ARGUMENT: a wrong struct_size, zero width or height,
+ * samples > 8, a non-finite yaw or scale, bytes_per_row below a tight row; AWSM_ERR_OUT_OF_RANGE: data_len too short for the layout;
+ * AWSM_ERR_UNSUPPORTED: an unknown format.  A refused call leaves the cube as it was. ---- */
+typedef enum AwsmPanoFormat { AWSM_PANO_RGBE8 = 0, AWSM_PANO_RGBA32F = 1 } AwsmPanoFormat;
+typedef struct AwsmEquirect {
+    uint32_t struct_size;     /* sizeof(AwsmEquirect) */
+    uint32_t width, height;   /* of the panorama, in pixels */
+    uint32_t format;          /* AwsmPanoFormat */
+    uint32_t bytes_per_row;   /* 0 = tight */
+    uint32_t samples;         /* S: S x S taps per texel; 0 = auto = clamp(ceil(width / (4 N)), 1, 8), else 1..8 */
+    float    yaw;             /* radians added to the azimuth */
+    float    scale;           /* multiplies every value; 0 means 1.0 */
+} AwsmEquirect;
+int awsm_hip_env_cube_from_equirect(AwsmHipCtx* ctx, AwsmCube which, const void* data, size_t data_len, const AwsmEquirect* pano);
+
 /* ---- the texture pool at run time (renderer-core/src/texture/texture_pool.rs:233-303, texture/convert_srgb.rs, texture/mipmap.rs).
  * Storage is what awsm_hip_texture_array_upload makes — RGBA8 UNORM, [level][layer][y][x] — and these entries fill and change it in place.
  *   create               a zero-filled array of `layers` images and `mips` levels (0 = 1); may reallocate and synchronise, as _upload does.

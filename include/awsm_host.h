@@ -211,6 +211,25 @@ typedef struct AwsmKtx2Info {
 int awsm_host_ktx2_parse(const uint8_t* data, size_t len, AwsmKtx2Info* out, char* err_out, size_t err_cap);
 int awsm_host_env_cube_load_ktx2(AwsmHost* h, AwsmCube which, const char* path, AwsmKtx2Info* info_out, char* err_out, size_t err_cap);
 int awsm_host_env_cube_load_ktx2_memory(AwsmHost* h, AwsmCube which, const uint8_t* data, size_t len, AwsmKtx2Info* info_out, char* err_out, size_t err_cap);
+/* Radiance pictures (.hdr) and the skybox from an equirectangular panorama (host/rgbe.hpp has the reader's rules).
+ * awsm_host_hdr_info and awsm_host_hdr_decode are pure functions: no host, no device.  The first line must start with "#?"; FORMAT=32-bit_rle_rgbe (or no
+ * FORMAT line) is read, 32-bit_rle_xyze is AWSM_ERR_UNSUPPORTED; EXPOSURE= values are multiplied into `exposure` and NOT applied (pass 1 / exposure as
+ * `scale` for radiance); "-Y H +X W" and "+Y H +X W" are read (flipped_y = 1 for the second: its rows are reversed, the output is always top-down),
+ * any other orientation is AWSM_ERR_UNSUPPORTED; 1 <= W, H <= 32768 and W * H <= 2^28.  Flat scanlines, the old run pixels and the new run-length
+ * coded planes are all read; every other rejection is AWSM_ERR_INVALID_ARGUMENT with the reason (a truncated scanline names its index).
+ * awsm_host_hdr_decode writes width * height RGBE quadruples (4 bytes each) to rgbe_out, which must hold them (out_cap): AWSM_PANO_RGBE8 as it is.
+ * awsm_host_env_cube_from_equirect is the thin wrapper over awsm_hip_env_cube_from_equirect (awsm_hip.h has the rules; AWSM_ERR_UNSUPPORTED, naming
+ * the symbol, with a backend library that lacks it).  awsm_host_env_cube_load_hdr[_memory] decode the file, create the cube `size`^2 with its full
+ * chain, project the panorama into level 0 (samples 0 = auto, yaw in radians, scale 0 = 1.0) and generate the mips.  None of them changes the IBL
+ * mip counts; awsm_host_env_bake_ibl afterwards lights the scene from the new skybox. */
+typedef struct AwsmHdrInfo { uint32_t struct_size, width, height, flipped_y, rle; float exposure; } AwsmHdrInfo;
+int awsm_host_hdr_info(const uint8_t* data, size_t len, AwsmHdrInfo* out, char* err, size_t err_cap);
+int awsm_host_hdr_decode(const uint8_t* data, size_t len, uint8_t* rgbe_out, size_t out_cap, AwsmHdrInfo* out, char* err, size_t err_cap);
+int awsm_host_env_cube_from_equirect(AwsmHost* h, AwsmCube which, const void* data, size_t len, const AwsmEquirect* pano);
+int awsm_host_env_cube_load_hdr(AwsmHost* h, AwsmCube which, const char* path, uint32_t size, uint32_t samples, float yaw, float scale, AwsmHdrInfo* info_out,
+                                char* err, size_t err_cap);
+int awsm_host_env_cube_load_hdr_memory(AwsmHost* h, AwsmCube which, const uint8_t* data, size_t len, uint32_t size, uint32_t samples, float yaw, float scale,
+                                       AwsmHdrInfo* info_out, char* err, size_t err_cap);
 int awsm_host_brdf_lut_generate(AwsmHost* h, uint32_t w, uint32_t height);
 int awsm_host_resize(AwsmHost* h, uint32_t width, uint32_t height);
 /* AwsmRenderer::set_anti_aliasing (anti_alias.rs:9-45): msaa_sample_count 0 (None) or 4 (recreates the render targets);
