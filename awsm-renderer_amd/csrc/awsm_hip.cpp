@@ -597,7 +597,12 @@ int enqueue_transparent(AwsmHipCtx* c) {
         if (f.total_tris) { awsm_launch_bin_count(&f, ss); awsm_launch_bin_big(&f, 0, ss); }
         awsm_launch_bin_scan(&f, ss);
         if (f.total_tris) { awsm_launch_bin_fill(&f, ss); awsm_launch_bin_big(&f, 1, ss); }
-        awsm_launch_forward(c->scene_dev, &f, ss);
+        // the editor's ground grid: the world pass only, with the record this pass was submitted with and the frame's camera snapshot
+        EditorGridDev grid;
+        const AwsmHipCtx::GridState& gs = c->grid_pass[c->slot];
+        const bool with_grid = gs.on && !c->hud_transparent;
+        if (with_grid) { grid.camera = f.camera; memcpy(grid.p, gs.p, sizeof grid.p); }
+        awsm_launch_forward(c->scene_dev, &f, with_grid ? &grid : nullptr, ss);
     }
     if ((rc = record(c, EV_FWD, ss))) return rc;
     if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));
@@ -900,7 +905,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->merged_vis) fr(b);
     fr(c->pose_records);
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
-    fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); for (auto& b : c->lights_pre) fr(b);
+    fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); fr(c->grid_layer); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 4 * kSlots; k++) {
         FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : c->htr[k - 3 * kSlots]));
@@ -1370,6 +1375,7 @@ static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t 
         HIPCHK(c, hipEventRecord(c->ev_geom_done[c->slot], c->stream));
         HIPCHK(c, hipStreamWaitEvent(shade_stream_of(c), c->ev_geom_done[c->slot], 0));
     }
+    if (!hud) c->grid_pass[c->slot] = c->grid;
     if ((rc = enqueue_transparent(c))) return rc;
     if (hud) c->hud_transparent_done = true; else { c->transparent_done = true; c->hud_transparent_done = false; }
     return AWSM_OK;
@@ -1695,6 +1701,54 @@ int awsm_hip_read_composite_f32(AwsmHipCtx* c, float* out) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
     HIPCHK(c, hipMemcpy(out, c->comp32.ptr, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+// ---- the editor's ground grid (editor_grid.hpp) ----
+int awsm_hip_editor_grid_defaults(AwsmEditorGrid* out) {      // grid.wgsl:87-98
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    static const AwsmEditorGrid d = {(uint32_t)sizeof(AwsmEditorGrid), {0.18f, 0.18f, 0.18f}, 0.7f, {0.28f, 0.28f, 0.28f}, 0.9f, {0.38f, 0.38f, 0.38f}, 1.0f,
+                                     {0.3f, 0.5f, 0.95f}, 1.0f, {0.95f, 0.3f, 0.3f}, 1e-4f};
+    *out = d;
+    return AWSM_OK;
+}
+static_assert(sizeof(AwsmEditorGrid) == 4 + sizeof(EditorGridDev::p) && offsetof(AwsmEditorGrid, color_background) == 4, "EditorGridDev.p is AwsmEditorGrid behind struct_size");
+int awsm_hip_set_editor_grid(AwsmHipCtx* c, const AwsmEditorGrid* g) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    AwsmEditorGrid full;
+    awsm_hip_editor_grid_defaults(&full);
+    if (g) {
+        if (g->struct_size < 4u || g->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_editor_grid: AwsmEditorGrid.struct_size = %u (set it to sizeof(AwsmEditorGrid))", g->struct_size);
+        const size_t known = std::min<size_t>(g->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
+        memcpy((uint8_t*)&full + 4, (const uint8_t*)g + 4, known - 4);
+        const float* p = full.color_background;
+        for (size_t i = 0; i < sizeof(EditorGridDev::p) / 4; i++)
+            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_editor_grid: value %zu of the record is not finite", i);
+    }
+    { int rcb = scene_write_barrier(c); if (rcb) return rcb; }      // scene state like any other; the pass itself carries the record it was enqueued with
+    c->grid.on = g != nullptr;
+    memcpy(c->grid.p, full.color_background, sizeof c->grid.p);
+    return AWSM_OK;
+}
+int awsm_hip_read_editor_grid(AwsmHipCtx* c, float* rgba, float* depth, uint8_t* kept) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!FB(c).camera.ptr || !c->width || !c->height) return fail(c, AWSM_ERR_NOT_READY, "read_editor_grid before the first geometry pass");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    const size_t px = (size_t)c->width * c->height;
+    int rc = dev_reserve(c, c->grid_layer, px * 21);      // [px] float4, [px] float, [px] byte
+    if (rc) return rc;
+    EditorGridDev g;
+    g.camera = (const uint8_t*)FB(c).camera.ptr;
+    if (c->grid.on) memcpy(g.p, c->grid.p, sizeof g.p);
+    else { AwsmEditorGrid d; awsm_hip_editor_grid_defaults(&d); memcpy(g.p, d.color_background, sizeof g.p); }
+    float* d_rgba = (float*)c->grid_layer.ptr; float* d_depth = d_rgba + px * 4; uint8_t* d_kept = (uint8_t*)(d_depth + px);
+    awsm_launch_editor_grid_layer(&g, c->width, c->height, d_rgba, d_depth, d_kept, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rgba) HIPCHK(c, hipMemcpy(rgba, d_rgba, px * 16, hipMemcpyDeviceToHost));
+    if (depth) HIPCHK(c, hipMemcpy(depth, d_depth, px * 4, hipMemcpyDeviceToHost));
+    if (kept) HIPCHK(c, hipMemcpy(kept, d_kept, px, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 

@@ -173,6 +173,10 @@ struct AwsmHipCtx {
     uint32_t tr_total_tris[2] = {0, 0}, tr_n_blocks[2] = {0, 0};
     bool transparent_done = false, hud_transparent_done = false;
     FrameBufs htr[kSlots];
+    // the editor's ground grid (awsm_hip_set_editor_grid): what the caller last set, and per frame slot what the slot's world transparent pass was
+    // enqueued with (awsm_hip_frame_end replays the pass with that); grid_layer: awsm_hip_read_editor_grid's scratch
+    struct GridState { bool on = false; float p[20] = {}; } grid, grid_pass[kSlots];
+    DevBuf grid_layer;
     DevBuf comp16, comp32;       // composite image (after the transparent pass) + parity tap
     // the effects + display passes (awsm_hip_post_pass): the display image per frame slot (or the caller's), the effects image (parity tap only),
     // the bloom chain's two f16 images and the per-pixel DoF terms — the last four per context: a post pass waits for the other slot's to end

@@ -277,6 +277,13 @@ struct PostArgs {
     uint32_t frame_serial;
 };
 
+// The editor's ground grid (editor_grid.hpp, awsm_hip_set_editor_grid): an argument of its own of the kernels that draw it — FrameDev, and with
+// it every other kernel's arguments, stays as it is.
+struct EditorGridDev {
+    const uint8_t* camera;               // the frame's camera snapshot (512 B)
+    float p[20];                         // AwsmEditorGrid behind struct_size: four {rgb, alpha} (background, minor, major, z axis + the axes' alpha), x axis rgb, depth_epsilon
+};
+
 #ifdef __HIPCC__
 // A hand-off gate that gave up (its signal never came within the time budget) has poisoned the frame it guarded: its kernels must not run on
 // buffers that are half written, or still being read.  Wave-uniform, one scalar load.

@@ -25,6 +25,7 @@
 #include "shade_gbuffer.hpp"
 #include "shade_samplers.hpp"
 #include "cube_seam.hpp"
+#include "editor_grid.hpp"
 #include "launch.hpp"
 
 #ifndef AWSM_LEAN_WAVES
@@ -1084,34 +1085,59 @@ __global__ __launch_bounds__(256) void k_forward_shade(const DevScene* __restric
     f.frag_color[i] = make_float4(o.color.x * a, o.color.y * a, o.color.z * a, a);          // fragment.wgsl:283-285 premultiplied
 }
 
+// The editor's ground grid under the pixel's fragments (editor_grid.hpp; render.rs before_transparent_pass: after the blit, before the transparent
+// meshes).  One fragment per pixel, tested per sample against the WORLD's depth — the geometry pass's keys, never a depth this pass writes.
 template <int S>
-__global__ __launch_bounds__(256) void k_forward_blend(FrameDev f) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= f.width * f.height || frame_poisoned(f)) return;
-    if (!row_owned(f, (int)(p / f.width))) return;                               // sharded: only this shard's rows of the composite
-    const uint2 c0 = reinterpret_cast<const uint2*>(f.opaque_rgba16f)[p];       // opaque -> transparent blit: every sample starts as the opaque colour
-    float dst[S][4];
+AWSM_DI void grid_under(const FrameDev& f, const EditorGridDev& g, uint32_t p, float (&dst)[S][4]) {
+    const GridFragment gf = grid_fragment(g, f.width, f.height, (int)(p % f.width), (int)(p / f.width));
+    if (!gf.kept) return;
 #pragma unroll
-    for (int s = 0; s < S; s++) {
-        dst[s][0] = f16_bits_to_f32((unsigned short)(c0.x & 0xFFFFu)); dst[s][1] = f16_bits_to_f32((unsigned short)(c0.x >> 16));
-        dst[s][2] = f16_bits_to_f32((unsigned short)(c0.y & 0xFFFFu)); dst[s][3] = f16_bits_to_f32((unsigned short)(c0.y >> 16));
-    }
-    for (uint32_t i = f.frag_first[p]; i != kFragNone && i < f.frag_cap;) {
-        const uint4 rec = f.frag_rec[i];
-        const float4 src = f.frag_color[i];
-        const float om = 1.0f - src.w;
-#pragma unroll
-        for (int s = 0; s < S; s++) {
-            if (!(rec.w & (1u << s))) continue;
-            dst[s][0] = blend_over_f16(src.x, dst[s][0], om); dst[s][1] = blend_over_f16(src.y, dst[s][1], om);
-            dst[s][2] = blend_over_f16(src.z, dst[s][2], om); dst[s][3] = blend_over_f16(src.w, dst[s][3], om);
-        }
-        i = rec.z;
-    }
-    float c[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) c[k] = S == 1 ? dst[0][k] : resolve4_f16(dst[0][k], dst[S > 1 ? 1 : 0][k], dst[S > 2 ? 2 : 0][k], dst[S > 3 ? 3 : 0][k]);
+    for (int s = 0; s < S; s++) if (gf.depth < key_depth(f.vis[(size_t)p * S + s])) grid_blend(gf.color, dst[s]);
+}
+// The one body of the two blend kernels, UNDER = what is drawn between the blit and the fragments.  As text, not as an AWSM_DI template: inlined from
+// a template, k_forward_blend's fragment loop comes out with the operands of its four products and of one sum the other way round (the optimiser
+// orders commutative operands by what they are when it first sees them) — the same bits, but tools/isa_diff.py holds that kernel to the text it had.
+#define AWSM_FORWARD_BLEND_BODY(UNDER)                                                                                                                      \
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;                                                                                                     \
+    if (p >= f.width * f.height || frame_poisoned(f)) return;                                                                                               \
+    if (!row_owned(f, (int)(p / f.width))) return;                               /* sharded: only this shard's rows of the composite */                      \
+    const uint2 c0 = reinterpret_cast<const uint2*>(f.opaque_rgba16f)[p];       /* opaque -> transparent blit: every sample starts as the opaque colour */    \
+    float dst[S][4];                                                                                                                                        \
+    _Pragma("unroll")                                                                                                                                       \
+    for (int s = 0; s < S; s++) {                                                                                                                           \
+        dst[s][0] = f16_bits_to_f32((unsigned short)(c0.x & 0xFFFFu)); dst[s][1] = f16_bits_to_f32((unsigned short)(c0.x >> 16));                           \
+        dst[s][2] = f16_bits_to_f32((unsigned short)(c0.y & 0xFFFFu)); dst[s][3] = f16_bits_to_f32((unsigned short)(c0.y >> 16));                           \
+    }                                                                                                                                                       \
+    UNDER;                                                                                                                                                  \
+    for (uint32_t i = f.frag_first[p]; i != kFragNone && i < f.frag_cap;) {                                                                                 \
+        const uint4 rec = f.frag_rec[i];                                                                                                                    \
+        const float4 src = f.frag_color[i];                                                                                                                 \
+        const float om = 1.0f - src.w;                                                                                                                      \
+        _Pragma("unroll")                                                                                                                                   \
+        for (int s = 0; s < S; s++) {                                                                                                                       \
+            if (!(rec.w & (1u << s))) continue;                                                                                                             \
+            dst[s][0] = blend_over_f16(src.x, dst[s][0], om); dst[s][1] = blend_over_f16(src.y, dst[s][1], om);                                             \
+            dst[s][2] = blend_over_f16(src.z, dst[s][2], om); dst[s][3] = blend_over_f16(src.w, dst[s][3], om);                                             \
+        }                                                                                                                                                   \
+        i = rec.z;                                                                                                                                          \
+    }                                                                                                                                                       \
+    float c[4];                                                                                                                                             \
+    _Pragma("unroll")                                                                                                                                       \
+    for (int k = 0; k < 4; k++) c[k] = S == 1 ? dst[0][k] : resolve4_f16(dst[0][k], dst[S > 1 ? 1 : 0][k], dst[S > 2 ? 2 : 0][k], dst[S > 3 ? 3 : 0][k]);   \
     store_pixel(f, p, {c[0], c[1], c[2], c[3]});
+template <int S>
+__global__ __launch_bounds__(256) void k_forward_blend(FrameDev f) { AWSM_FORWARD_BLEND_BODY((void)0) }
+template <int S>
+__global__ __launch_bounds__(256) void k_forward_blend_grid(FrameDev f, EditorGridDev g) { AWSM_FORWARD_BLEND_BODY(grid_under<S>(f, g, p, dst)) }
+#undef AWSM_FORWARD_BLEND_BODY
+// Test aid (awsm_hip_read_editor_grid): the raw layer of the whole frame — the fragment's colour, its depth, kept / discarded; zeros where discarded
+__global__ __launch_bounds__(256) void k_editor_grid_layer(EditorGridDev g, uint32_t width, uint32_t height, float4* __restrict__ rgba, float* __restrict__ depth, uint8_t* __restrict__ kept) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= width * height) return;
+    const GridFragment gf = grid_fragment(g, width, height, (int)(p % width), (int)(p / width));
+    rgba[p] = make_float4(gf.color.x, gf.color.y, gf.color.z, gf.color.w);
+    depth[p] = gf.depth;
+    kept[p] = gf.kept ? 1 : 0;
 }
 
 // Block of 16x16 pixels -> pixel of this thread.  Workgroup ids are dealt round-robin over the 8 XCDs (blockIdx & 7), each
@@ -2715,7 +2741,8 @@ extern "C" int awsm_launch_shade_todo(const awsm::DevScene* sc, const awsm::Fram
 }
 // f: the transparent pass's frame (its own draws / vertices / bins; vis = the geometry pass's keys; opaque_rgba16f = the opaque image;
 // out_rgba16f / out_rgba32f = the composite image).  Every tile of the frame is launched: a tile without transparent triangles is a copy.
-extern "C" void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s) {
+// grid: the editor's ground grid under the fragments (null: off — the kernels of a frame without it are untouched).
+extern "C" void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, const awsm::EditorGridDev* grid, hipStream_t s) {
     const uint32_t n_tiles = f->tiles_x * f->tiles_y;
     if (!n_tiles) return;
     const bool ms = f->msaa == 4u;
@@ -2726,7 +2753,12 @@ extern "C" void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameD
         else hipLaunchKernelGGL((awsm::k_forward_cover<1, G>), dim3(n_tiles * awsm::kFwdSubs), dim3(awsm::kFwdThreads), 0, s, sc, *f);
         if (nb_shade) hipLaunchKernelGGL((awsm::k_forward_shade<G>), dim3(nb_shade), dim3(256), 0, s, sc, *f);
     });
-    if (ms) hipLaunchKernelGGL(awsm::k_forward_blend<4>, dim3(nb_blend), dim3(256), 0, s, *f); else hipLaunchKernelGGL(awsm::k_forward_blend<1>, dim3(nb_blend), dim3(256), 0, s, *f);
+    if (grid) { if (ms) hipLaunchKernelGGL(awsm::k_forward_blend_grid<4>, dim3(nb_blend), dim3(256), 0, s, *f, *grid); else hipLaunchKernelGGL(awsm::k_forward_blend_grid<1>, dim3(nb_blend), dim3(256), 0, s, *f, *grid); }
+    else if (ms) hipLaunchKernelGGL(awsm::k_forward_blend<4>, dim3(nb_blend), dim3(256), 0, s, *f); else hipLaunchKernelGGL(awsm::k_forward_blend<1>, dim3(nb_blend), dim3(256), 0, s, *f);
+}
+extern "C" void awsm_launch_editor_grid_layer(const awsm::EditorGridDev* g, uint32_t width, uint32_t height, float* rgba, float* depth, uint8_t* kept, hipStream_t s) {
+    const uint32_t n = width * height;
+    if (n) hipLaunchKernelGGL(awsm::k_editor_grid_layer, dim3((n + 255u) / 256u), dim3(256), 0, s, *g, width, height, reinterpret_cast<float4*>(rgba), depth, kept);
 }
 extern "C" void awsm_launch_msaa_halo_export(const awsm::FrameDev* f, unsigned long long* dst, uint32_t bands_out, hipStream_t s) {
     const uint32_t n = bands_out * 2u * f->width;

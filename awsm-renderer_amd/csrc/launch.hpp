@@ -29,7 +29,8 @@ void awsm_launch_resolve_draws(const awsm::DevScene* sc, const awsm::FrameDev* f
 void awsm_launch_shade(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s);
 int awsm_shade_is_lean(const awsm::FrameDev* f);
 int awsm_launch_shade_todo(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s);
-void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, hipStream_t s);
+void awsm_launch_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, const awsm::EditorGridDev* grid, hipStream_t s);
+void awsm_launch_editor_grid_layer(const awsm::EditorGridDev* g, uint32_t width, uint32_t height, float* rgba, float* depth, uint8_t* kept, hipStream_t s);
 void awsm_launch_msaa_halo_export(const awsm::FrameDev* f, unsigned long long* dst, uint32_t bands_out, hipStream_t s);
 void awsm_launch_count_covered(const awsm::FrameDev* f, hipStream_t s);
 void awsm_launch_gbuffer_dump(const awsm::FrameDev* f, float* out, hipStream_t s);

@@ -39,7 +39,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_env_cube_filter", "awsm_hip_env_cube_from_equirect",
            "awsm_hip_texture_array_create", "awsm_hip_texture_array_resize_layers", "awsm_hip_texture_array_write_layers",
            "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info",
-           "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read"]
+           "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read",
+           "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid"]
 
 
 class AwsmConfig(C.Structure):
@@ -57,6 +58,22 @@ class AwsmOpaqueParams(C.Structure):
 
 class AwsmPostParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tonemapping", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AwsmEditorGrid(C.Structure):
+    """The editor's ground grid (awsm_hip_set_editor_grid): the constants of grid.wgsl:87-98 as a record."""
+    _fields_ = [("struct_size", C.c_uint32), ("color_background", C.c_float * 3), ("alpha_background", C.c_float), ("color_minor", C.c_float * 3), ("alpha_minor", C.c_float),
+                ("color_major", C.c_float * 3), ("alpha_major", C.c_float), ("color_z_axis", C.c_float * 3), ("alpha_axis", C.c_float),
+                ("color_x_axis", C.c_float * 3), ("depth_epsilon", C.c_float)]
+
+    def override(self, **overrides):
+        """Set fields by name (a colour from any three numbers); an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k == "struct_size":
+                raise TypeError("AwsmEditorGrid has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
+            setattr(self, k, (C.c_float * 3)(*v) if k.startswith("color_") else float(v))
+        return self
 
 
 class AwsmCubeLayout(C.Structure):
@@ -224,6 +241,9 @@ def load_library():
     lib.awsm_hip_skin_pose_records_write.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.awsm_hip_skin_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.awsm_hip_buffer_read.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
+    lib.awsm_hip_editor_grid_defaults.argtypes = [C.c_void_p]
+    lib.awsm_hip_set_editor_grid.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_editor_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -505,6 +525,29 @@ class HipDevice:
             n = len(draws)
             draws = self.make_draws(draws)
         self._chk(self.lib.awsm_hip_transparent_pass(self.ctx, draws, n if n is not None else len(draws)), "transparent_pass")
+
+    def editor_grid_defaults(self) -> AwsmEditorGrid:
+        g = AwsmEditorGrid()
+        self._chk(self.lib.awsm_hip_editor_grid_defaults(C.byref(g)), "editor_grid_defaults")
+        return g
+
+    def set_editor_grid(self, on=True, struct_size: Optional[int] = None, **overrides):
+        """The editor's ground grid in every later transparent_pass: the defaults of grid.wgsl with `overrides` (AwsmEditorGrid's field names);
+        set_editor_grid(None) turns it off.  struct_size: what the record claims as its size (tests)."""
+        if not on:
+            return self._chk(self.lib.awsm_hip_set_editor_grid(self.ctx, None), "set_editor_grid")
+        g = self.editor_grid_defaults().override(**overrides)
+        if struct_size is not None:
+            g.struct_size = struct_size
+        self._chk(self.lib.awsm_hip_set_editor_grid(self.ctx, C.byref(g)), "set_editor_grid")
+
+    def read_editor_grid(self):
+        """The raw grid layer for the last submitted frame's camera and size -> (rgba float32 [H, W, 4], depth float32 [H, W], kept bool [H, W])."""
+        rgba = np.empty((self.height, self.width, 4), np.float32)
+        depth = np.empty((self.height, self.width), np.float32)
+        kept = np.empty((self.height, self.width), np.uint8)
+        self._chk(self.lib.awsm_hip_read_editor_grid(self.ctx, rgba.ctypes.data, depth.ctypes.data, kept.ctypes.data), "read_editor_grid")
+        return rgba, depth, kept.astype(bool)
 
     def hud_geometry_pass(self, draws):
         """The hud meshes' visibility geometry, between geometry_pass and opaque_pass (render.rs:169-178)."""

@@ -140,6 +140,7 @@ def load_library():
         "awsm_host_set_post_processing": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_int]),
         "awsm_host_clear_post_processing": (C.c_int, [vp]),
         "awsm_host_camera_set_dof": (C.c_int, [vp, C.c_float, C.c_float]),
+        "awsm_host_editor_grid_defaults": (C.c_int, [vp, vp]), "awsm_host_set_editor_grid": (C.c_int, [vp, vp]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
         "awsm_host_texture_insert_kind": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_update_transforms": (C.c_int, [vp]),
         "awsm_host_render": (C.c_int, [vp, C.c_int, vp]), "awsm_host_mirror": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
@@ -594,6 +595,16 @@ class Host:
         """No post pass again (this library's default)."""
         self._chk(self.lib.awsm_host_clear_post_processing(self.h), "clear_post_processing")
 
+    def set_editor_grid(self, on: bool = True, **overrides):
+        """The editor's ground grid (crates/editor/src/grid), drawn by the transparent pass of every later render(): grid.wgsl's constants with
+        `overrides` (hip_backend.AwsmEditorGrid's field names).  on=False turns it off."""
+        if not on:
+            return self._chk(self.lib.awsm_host_set_editor_grid(self.h, None), "set_editor_grid")
+        g = hip_backend.AwsmEditorGrid()
+        self._chk(self.lib.awsm_host_editor_grid_defaults(self.h, C.byref(g)), "editor_grid_defaults")
+        g.override(**overrides)
+        self._chk(self.lib.awsm_host_set_editor_grid(self.h, C.byref(g)), "set_editor_grid")
+
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         """CameraMatrices.focus_distance / .aperture (camera bytes 496-503; the reference's defaults 10.0 and 5.6)."""
         self._chk(self.lib.awsm_host_camera_set_dof(self.h, focus_distance, aperture), "camera_set_dof")
@@ -979,6 +990,9 @@ class Renderer:
 
     def clear_post_processing(self):
         self.host.clear_post_processing()
+
+    def set_editor_grid(self, on: bool = True, **overrides):
+        self.host.set_editor_grid(on, **overrides)
 
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         self.host.camera_set_dof(focus_distance, aperture)

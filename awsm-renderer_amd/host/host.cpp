@@ -68,6 +68,8 @@ struct Backend {
     int (*hud_transparent_pass)(AwsmHipCtx*, const AwsmDraw*, uint32_t) = nullptr;
     int (*frame_end)(AwsmHipCtx*, AwsmFrameStats*) = nullptr;
     int (*post_pass)(AwsmHipCtx*, const AwsmPostParams*) = nullptr;     // optional: a backend without it cannot post-process
+    int (*editor_grid_defaults)(AwsmEditorGrid*) = nullptr;             // optional: the editor's ground grid (awsm_host_set_editor_grid)
+    int (*set_editor_grid)(AwsmHipCtx*, const AwsmEditorGrid*) = nullptr;
     // optional: environment cubes at run time (awsm_host_env_cube_*)
     int (*env_cube_create)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t) = nullptr;
     int (*env_cube_write_face)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
@@ -246,6 +248,7 @@ struct AwsmHost {
     // ---- post_process.rs + AntiAliasing.smaa: off until awsm_host_set_post_processing ----
     bool post_on = false;
     AwsmPostParams post{};
+    bool grid_on = false;                      // awsm_host_set_editor_grid: the world transparent pass runs every frame, with no draws if need be
     bool sharded = false;                      // awsm_host_set_shard_rows / _bands gave this host a part of the frame (the post pass needs all of it)
     Mat4 cam_view = mat4_identity(), cam_proj = mat4_identity();
     uint32_t frame_count = 0;
@@ -684,6 +687,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
               load_sym(h.get(), b.frame_end, "awsm_hip_frame_end");
     if (!ok) { fprintf(stderr, "awsm_host: %s\n", h->last_error.c_str()); dlclose(b.dl); return AWSM_ERR_NOT_READY; }
     b.post_pass = reinterpret_cast<decltype(b.post_pass)>(dlsym(b.dl, "awsm_hip_post_pass"));      // optional (awsm_host_set_post_processing)
+    b.editor_grid_defaults = reinterpret_cast<decltype(b.editor_grid_defaults)>(dlsym(b.dl, "awsm_hip_editor_grid_defaults"));      // optional (awsm_host_set_editor_grid)
+    b.set_editor_grid = reinterpret_cast<decltype(b.set_editor_grid)>(dlsym(b.dl, "awsm_hip_set_editor_grid"));
     b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
     b.env_cube_write_face = reinterpret_cast<decltype(b.env_cube_write_face)>(dlsym(b.dl, "awsm_hip_env_cube_write_face"));
     b.env_cube_write_all_faces = reinterpret_cast<decltype(b.env_cube_write_all_faces)>(dlsym(b.dl, "awsm_hip_env_cube_write_all_faces"));
@@ -1658,8 +1663,8 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     if ((rc = h->be.opaque_pass(h->ctx, &op))) return dev_fail(h, rc, "opaque_pass");
     if (h->after_opaque && (rc = h->after_opaque(h->after_opaque_user))) { h->last_error = "after_opaque_pass hook failed"; return rc; }
     // ---- opaque -> transparent blit + world transparent pass (render.rs:224-297).  A scene without transparent meshes skips it:
-    // the composite image then IS the opaque image (the reference would copy it). ----
-    if (h->has_transparent_meshes || h->has_hud_meshes) { if ((rc = h->be.transparent_pass(h->ctx, h->last_transparent_draws.data(), (uint32_t)h->last_transparent_draws.size()))) return dev_fail(h, rc, "transparent_pass"); }
+    // the composite image then IS the opaque image (the reference would copy it) — unless the editor's grid is on, which that pass draws. ----
+    if (h->has_transparent_meshes || h->has_hud_meshes || h->grid_on) { if ((rc = h->be.transparent_pass(h->ctx, h->last_transparent_draws.data(), (uint32_t)h->last_transparent_draws.size()))) return dev_fail(h, rc, "transparent_pass"); }
     // ---- the HUD transparent pass over the composite (render.rs:301-312) ----
     if (h->has_hud_meshes && (rc = h->be.hud_transparent_pass(h->ctx, h->last_hud_transparent_draws.data(), (uint32_t)h->last_hud_transparent_draws.size()))) return dev_fail(h, rc, "hud_transparent_pass");
     // ---- the effects + display passes (render.rs:339-356), when post-processing was turned on ----
@@ -1677,6 +1682,23 @@ int awsm_host_set_post_processing(AwsmHost* h, uint32_t tonemapping, int bloom, 
     h->post.struct_size = sizeof(AwsmPostParams); h->post.tonemapping = tonemapping; h->post.reserved = 0;
     h->post.flags = (smaa ? AWSM_POST_SMAA : 0u) | (bloom ? AWSM_POST_BLOOM : 0u) | (dof ? AWSM_POST_DOF : 0u);
     h->post_on = true;
+    return AWSM_OK;
+}
+
+// The editor's ground grid (crates/editor/src/grid, drawn by the reference's editor in its before_transparent_pass hook): a built-in of the
+// backend's transparent pass.
+int awsm_host_editor_grid_defaults(AwsmHost* h, AwsmEditorGrid* out) {
+    if (!h || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.editor_grid_defaults) return fail(h, AWSM_ERR_UNSUPPORTED, "editor_grid_defaults: the backend library has no %s", "awsm_hip_editor_grid_defaults");
+    const int rc = h->be.editor_grid_defaults(out);
+    return rc ? dev_fail(h, rc, "editor_grid_defaults") : AWSM_OK;
+}
+int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.set_editor_grid) return fail(h, AWSM_ERR_UNSUPPORTED, "set_editor_grid: the backend library has no %s", "awsm_hip_set_editor_grid");
+    const int rc = h->be.set_editor_grid(h->ctx, grid);
+    if (rc) return dev_fail(h, rc, "set_editor_grid");
+    h->grid_on = grid != nullptr;
     return AWSM_OK;
 }
 

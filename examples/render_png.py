@@ -11,6 +11,7 @@ device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefilte
 by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
 --hdr FILE projects an equirectangular Radiance .hdr panorama into the skybox (--hdr-size N, default 512; --hdr-yaw R radians turns it about the
 vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl the scene is lit from the file.
+--grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
 """
 import argparse
 import os
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--hdr-size", type=int, default=512, metavar="N", help="side of the skybox cube made from --hdr")
     ap.add_argument("--hdr-yaw", type=float, default=0.0, metavar="R", help="radians added to the panorama's azimuth")
     ap.add_argument("--bake-ibl", action="store_true", help="with --sky-gradient / --env-ktx2 / --hdr: filter the IBL cubes from the skybox on the device")
+    ap.add_argument("--grid", action="store_true", help="the editor's ground grid, drawn by the transparent pass")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -81,6 +83,8 @@ def main():
         r.set_post_processing(TONEMAP[a.tonemap or "khronos"], bloom=a.bloom, dof=a.dof, smaa=a.smaa)
         if a.dof:
             r.camera_set_dof(a.focus, a.aperture)
+    if a.grid:
+        r.set_editor_grid(True)
     stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
     if post:
@@ -90,7 +94,7 @@ def main():
         Image.fromarray(rgba[..., :3]).save(a.out)
         print(f"{a.out}: {W}x{H}, post pass {a.tonemap or 'khronos'} bloom={a.bloom} dof={a.dof} smaa={a.smaa}, the device's RGBA8 display image")
         return
-    final = dev.read_composite() if stats["forward_triangles"] else dev.read_opaque()      # the image after the transparent pass, when the scene has one
+    final = dev.read_composite() if stats["forward_triangles"] or a.grid else dev.read_opaque()      # the image after the transparent pass, when the scene has one
     img = final.view(np.float16).astype(np.float32)[..., :3]
     r.close()
     ldr = np.clip(img / (1.0 + img), 0.0, 1.0) ** (1.0 / 2.2)

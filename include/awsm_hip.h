@@ -570,6 +570,35 @@ int awsm_hip_skin_pose_records_write(AwsmHipCtx* ctx, uint32_t first, uint32_t n
 int awsm_hip_skin_pose(AwsmHipCtx* ctx, const uint32_t* record_ids, uint32_t n);
 int awsm_hip_buffer_read(AwsmHipCtx* ctx, AwsmBuf which, size_t offset, void* dst, size_t len);
 
+/* ---- the editor's ground grid (crates/editor/src/grid/{shaders/grid.wgsl,render.rs,pipelines.rs}, drawn by the reference's editor in
+ * its before_transparent_pass hook).  A built-in of awsm_hip_transparent_pass: between the opaque -> transparent blit and the transparent meshes every
+ * pixel intersects its camera ray with the plane y = 0 and draws anti-aliased minor lines (every unit), major lines (every 10) and the X and Z axes over
+ * a background tint, tested `Less` per sample against the WORLD's depth (the geometry pass's; never hud_depth, never what the transparent meshes
+ * write), writing no depth, blended SrcAlpha / OneMinusSrcAlpha into the RGBA16F target.  The opaque image is untouched, so screen-space transmission
+ * does not see the grid, and the depth-of-field pass's depth does not change.  Off by default; with the grid off the pass runs the kernels it ran
+ * before this entry existed.
+ *   defaults         the constants of grid.wgsl:87-98 (struct_size = sizeof(AwsmEditorGrid)).
+ *   set_editor_grid  NULL turns the grid off.  struct_size says how much of the record the caller knows (at least the four bytes of struct_size, at
+ *                    most 4096): nothing is read beyond it and fields it does not reach keep their defaults.  A non-finite value:
+ *                    AWSM_ERR_INVALID_ARGUMENT, and the grid stays as it was.  Takes effect from the next awsm_hip_transparent_pass; a pass already
+ *                    enqueued (AWSM_CFG_OVERLAP_FRAMES) keeps the record it was enqueued with.  The HUD transparent pass never draws it.
+ *   read_editor_grid the raw layer for the last submitted frame's camera snapshot and size, whether the grid is on or off (off: the defaults) and
+ *                    whatever the shard: per pixel RGBA f32, depth f32 and 1 = kept / 0 = discarded (zeros where discarded).  Any pointer may be
+ *                    NULL.  Synchronous.  AWSM_ERR_NOT_READY before the first geometry pass.
+ * The grid runs on sharded contexts (this shard's rows, absolute pixel coordinates), under MSAA x4 and with n_draws = 0.  awsm_hip_frame_end's replay
+ * of an overflowed transparent pass needs nothing of its own: the grid is part of that pass and is replayed with the record the pass was given. ---- */
+typedef struct AwsmEditorGrid {
+    uint32_t struct_size;
+    float color_background[3], alpha_background;
+    float color_minor[3], alpha_minor;
+    float color_major[3], alpha_major;
+    float color_z_axis[3], alpha_axis;      /* one alpha for both axes */
+    float color_x_axis[3], depth_epsilon;   /* added to the fragment's depth: coplanar scene geometry wins */
+} AwsmEditorGrid;
+int awsm_hip_editor_grid_defaults(AwsmEditorGrid* out);
+int awsm_hip_set_editor_grid(AwsmHipCtx* ctx, const AwsmEditorGrid* grid /* NULL = off */);
+int awsm_hip_read_editor_grid(AwsmHipCtx* ctx, float* rgba_out, float* depth_out, uint8_t* kept_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -243,6 +243,14 @@ int awsm_host_set_anti_aliasing(AwsmHost* h, uint32_t msaa_sample_count, uint32_
  * settings; awsm_host_clear_post_processing turns the post pass off again. */
 int awsm_host_set_post_processing(AwsmHost* h, uint32_t tonemapping, int bloom, int dof, int smaa);
 int awsm_host_clear_post_processing(AwsmHost* h);
+/* The editor's ground grid (crates/editor/src/grid; the reference's editor draws it in its before_transparent_pass hook,
+ * crates/frontend/src/pages/app/scene/editor.rs:87-99).  Here it is a built-in of the backend's transparent pass (awsm_hip_set_editor_grid in
+ * awsm_hip.h has the rules): set it once at set-up.  With the grid on awsm_host_render runs the world transparent pass in every frame — with no draws
+ * when the scene has no transparent or hud mesh — so the composite image is what the post pass and the caller read.  NULL turns it off again.
+ * editor_grid_defaults fills the constants of grid.wgsl, to change a colour from.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library
+ * lacks awsm_hip_set_editor_grid / awsm_hip_editor_grid_defaults; the backend's own refusals (a non-finite value, a bad struct_size) pass through. */
+int awsm_host_editor_grid_defaults(AwsmHost* h, AwsmEditorGrid* out);
+int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid /* NULL = off */);
 /* CameraMatrices.focus_distance / .aperture (camera.rs:40-52; the reference's defaults are 10.0 and 5.6): camera bytes 496-503, uploaded with
  * the next frame.  Until this is called the host writes 0 and 0. */
 int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture);
