@@ -523,7 +523,23 @@ int enqueue_opaque(AwsmHipCtx* c) {
         if (c->stage_timers && awsm_shade_is_lean(&f) && (rc = record(c, EV_SHADE_LEAN, ss))) return rc;
         (void)awsm_launch_shade_todo(c->scene_dev, &f, ss);
     }
-    if ((rc = record(c, EV_SHADE, ss))) return rc;
+    // screen-space ambient occlusion, with the record this pass was submitted with: behind the shading kernels — it modulates their image in place —
+    // and in front of the shade-done signal below: it reads the slot's keys, which the slot's next geometry pass overwrites.  A replay
+    // (awsm_hip_frame_end) comes through here again behind shading kernels that wrote every pixel anew, so the image is modulated once.
+    const AwsmHipCtx::SsaoState& so = c->ssao_pass[c->slot];
+    if (so.on && f.has_opaque && f.sy1 > f.sy0) {
+        const size_t px = (size_t)c->width * c->height;
+        SsaoArgs sa{};
+        sa.width = c->width; sa.height = c->height;
+        sa.vis = (const unsigned long long*)FB(c).vis.ptr;      // the WORLD geometry pass's own buffer — not merged_vis, which the opaque pass itself reads in an MSAA frame with hud meshes
+        sa.camera = (const float*)f.camera;
+        sa.radius = so.p[0]; sa.intensity = so.p[1]; sa.bias = so.p[2]; sa.strength = so.p[3];
+        sa.ao_raw = (float*)c->ssao_layers[c->slot].ptr; sa.ao_smoothed = sa.ao_raw + px; sa.view_z = sa.ao_raw + 2 * px;
+        sa.out16 = (uint2*)f.out_rgba16f; sa.out32 = (float4*)f.out_rgba32f;
+        sa.poison = f.poison; sa.frame_serial = f.frame_serial;
+        awsm_launch_ssao(&sa, c->msaa == 4 ? 4u : 1u, ss);
+    }
+    if ((rc = record(c, EV_SHADE, ss))) return rc;      // behind the SSAO kernels: with SSAO on AwsmFrameStats.ms_shade is the shading kernels and the occlusion
     ht.mark("opaque: shade launches");
     if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));
     else if (c->trace_dev) awsm_launch_handoff_signal(nullptr, 0u, trace_slot(c, 2), ss);
@@ -906,6 +922,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     fr(c->pose_records);
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); fr(c->grid_layer); for (auto& b : c->lights_pre) fr(b);
+    for (auto& b : c->ssao_layers) fr(b);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 4 * kSlots; k++) {
         FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : c->htr[k - 3 * kSlots]));
@@ -1319,7 +1336,15 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
         if (!c->msaa_halo || c->msaa_halo_bytes < need)
             return fail(c, AWSM_ERR_NOT_READY, "opaque_pass: MSAA with band sharding needs the gathered halo keys (awsm_hip_msaa_halo_export -> all-gather -> awsm_hip_msaa_halo_bind, %zu bytes)", need);
     }
+    // screen-space ambient occlusion (awsm_hip_set_ssao): this pass carries the record as it stands now, into a replay too
+    const bool ssao_on = c->ssao.on && p->has_opaque;
+    if (ssao_on && (c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height))))
+        return fail(c, AWSM_ERR_UNSUPPORTED, "opaque_pass with SSAO on a sharded context: its taps and its smoothing read depth in rows the shard never rasterised (no halo exchange)");
     HIPCHK(c, hipSetDevice(c->device));
+    if (ssao_on) { const int rcs = dev_reserve(c, c->ssao_layers[c->slot], (size_t)c->width * c->height * 12); if (rcs) return rcs; }
+    c->ssao_pass[c->slot] = c->ssao;
+    c->ssao_pass[c->slot].on = ssao_on;
+    c->ssao_px[c->slot] = ssao_on ? (size_t)c->width * c->height : 0;
     c->last_opaque = *p;
     if (!p->has_opaque && c->camera_written_since_snapshot && c->bufs[AWSM_BUF_CAMERA].ptr) {
         // the "empty" pipeline (skybox only) may run without a geometry pass of its own: it then has no snapshot of the camera it was given.  Rare
@@ -1749,6 +1774,46 @@ int awsm_hip_read_editor_grid(AwsmHipCtx* c, float* rgba, float* depth, uint8_t*
     if (rgba) HIPCHK(c, hipMemcpy(rgba, d_rgba, px * 16, hipMemcpyDeviceToHost));
     if (depth) HIPCHK(c, hipMemcpy(depth, d_depth, px * 4, hipMemcpyDeviceToHost));
     if (kept) HIPCHK(c, hipMemcpy(kept, d_kept, px, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+// ---- screen-space ambient occlusion (kernels_ssao.hip) ----
+int awsm_hip_ssao_defaults(AwsmSsao* out) {
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    static const AwsmSsao d = {(uint32_t)sizeof(AwsmSsao), 0.5f, 1.0f, 0.02f, 1.0f};
+    *out = d;
+    return AWSM_OK;
+}
+static_assert(sizeof(AwsmSsao) == 4 + sizeof(AwsmHipCtx::SsaoState::p) && offsetof(AwsmSsao, radius) == 4, "SsaoState.p is AwsmSsao behind struct_size");
+int awsm_hip_set_ssao(AwsmHipCtx* c, const AwsmSsao* s) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    AwsmSsao full;
+    awsm_hip_ssao_defaults(&full);
+    if (s) {
+        if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: AwsmSsao.struct_size = %u (set it to sizeof(AwsmSsao))", s->struct_size);
+        const size_t known = std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
+        memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, known - 4);
+        const float* p = &full.radius;
+        for (size_t i = 0; i < 4; i++)
+            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: value %zu of the record is not finite", i);
+        if (!(full.radius > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: radius = %g (world units, > 0)", (double)full.radius);
+        if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: strength = %g (0 .. 1)", (double)full.strength);
+    }
+    // host state only: a pass already enqueued carries the record it was enqueued with as kernel arguments
+    c->ssao.on = s != nullptr;
+    memcpy(c->ssao.p, &full.radius, sizeof c->ssao.p);
+    return AWSM_OK;
+}
+int awsm_hip_read_ssao(AwsmHipCtx* c, float* ao_raw, float* ao_smoothed, float* view_z) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    const size_t px = (size_t)c->width * c->height;
+    if (!px || c->ssao_px[c->slot] != px || !c->ssao_layers[c->slot].ptr) return fail(c, AWSM_ERR_NOT_READY, "read_ssao: the last submitted frame had no opaque pass with SSAO on");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    const float* d = (const float*)c->ssao_layers[c->slot].ptr;
+    if (ao_raw) HIPCHK(c, hipMemcpy(ao_raw, d, px * 4, hipMemcpyDeviceToHost));
+    if (ao_smoothed) HIPCHK(c, hipMemcpy(ao_smoothed, d + px, px * 4, hipMemcpyDeviceToHost));
+    if (view_z) HIPCHK(c, hipMemcpy(view_z, d + 2 * px, px * 4, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 

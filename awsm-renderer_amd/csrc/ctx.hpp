@@ -218,6 +218,13 @@ struct AwsmHipCtx {
     // of frame `serial` at index serial % trace_cap, written by one-lane kernels in stream order (the hand-off's signal kernels where they exist)
     unsigned long long* trace_dev = nullptr;
     uint32_t trace_cap = 0;
+
+    // screen-space ambient occlusion (awsm_hip_set_ssao): what the caller last set, and per frame slot what the slot's opaque pass was enqueued with
+    // (awsm_hip_frame_end replays the pass with that); ssao_layers: per slot [3][px] f32 — A, A', view z — sized for ssao_px pixels.
+    // (Last in the struct: every member above keeps the offset it had.)
+    struct SsaoState { bool on = false; float p[4] = {}; } ssao, ssao_pass[kSlots];
+    DevBuf ssao_layers[kSlots];
+    size_t ssao_px[kSlots] = {};     // pixels of the frame the slot's layers were last written for (0: never)
 };
 
 #define HIPCHK(c, call)                                                                            \

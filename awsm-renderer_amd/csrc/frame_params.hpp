@@ -284,6 +284,21 @@ struct EditorGridDev {
     float p[20];                         // AwsmEditorGrid behind struct_size: four {rgb, alpha} (background, minor, major, z axis + the axes' alpha), x axis rgb, depth_epsilon
 };
 
+// Screen-space ambient occlusion (kernels_ssao.hip, awsm_hip_set_ssao): what the two kernels enqueued behind an opaque pass read and write.
+struct SsaoArgs {
+    uint32_t width, height;
+    const unsigned long long* vis;       // the WORLD geometry pass's keys (x4 with MSAA): never the hud's, never the merged ones
+    const float* camera;                 // the frame's camera snapshot (512 B): proj at floats 16..31, inv_proj at 64..79
+    float radius, intensity, bias, strength;      // AwsmSsao behind struct_size
+    float* ao_raw;                       // per pixel, per frame slot: A, A' and view z (NaN where nothing was hit)
+    float* ao_smoothed;
+    float* view_z;
+    uint2* out16;                        // the opaque image, modulated in place
+    float4* out32;                       // its f32 parity tap (may be null)
+    const uint32_t* poison;              // FrameDev.poison / frame_serial
+    uint32_t frame_serial;
+};
+
 #ifdef __HIPCC__
 // A hand-off gate that gave up (its signal never came within the time budget) has poisoned the frame it guarded: its kernels must not run on
 // buffers that are half written, or still being read.  Wave-uniform, one scalar load.

@@ -40,7 +40,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_texture_array_create", "awsm_hip_texture_array_resize_layers", "awsm_hip_texture_array_write_layers",
            "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info",
            "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read",
-           "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid"]
+           "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid",
+           "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao"]
 
 
 class AwsmConfig(C.Structure):
@@ -73,6 +74,20 @@ class AwsmEditorGrid(C.Structure):
             if k not in names or k == "struct_size":
                 raise TypeError("AwsmEditorGrid has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
             setattr(self, k, (C.c_float * 3)(*v) if k.startswith("color_") else float(v))
+        return self
+
+
+class AwsmSsao(C.Structure):
+    """Screen-space ambient occlusion (awsm_hip_set_ssao): radius in world units, intensity, bias as a fraction of the radius, strength 0 .. 1."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_float), ("intensity", C.c_float), ("bias", C.c_float), ("strength", C.c_float)]
+
+    def override(self, **overrides):
+        """Set fields by name; an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k == "struct_size":
+                raise TypeError("AwsmSsao has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
+            setattr(self, k, float(v))
         return self
 
 
@@ -244,6 +259,9 @@ def load_library():
     lib.awsm_hip_editor_grid_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_set_editor_grid.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_editor_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_ssao_defaults.argtypes = [C.c_void_p]
+    lib.awsm_hip_set_ssao.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_ssao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -548,6 +566,27 @@ class HipDevice:
         kept = np.empty((self.height, self.width), np.uint8)
         self._chk(self.lib.awsm_hip_read_editor_grid(self.ctx, rgba.ctypes.data, depth.ctypes.data, kept.ctypes.data), "read_editor_grid")
         return rgba, depth, kept.astype(bool)
+
+    def ssao_defaults(self) -> AwsmSsao:
+        s = AwsmSsao()
+        self._chk(self.lib.awsm_hip_ssao_defaults(C.byref(s)), "ssao_defaults")
+        return s
+
+    def set_ssao(self, on=True, struct_size: Optional[int] = None, **overrides):
+        """Screen-space ambient occlusion in every later opaque_pass: the defaults with `overrides` (radius, intensity, bias, strength);
+        set_ssao(None) turns it off.  struct_size: what the record claims as its size (tests)."""
+        if not on:
+            return self._chk(self.lib.awsm_hip_set_ssao(self.ctx, None), "set_ssao")
+        s = self.ssao_defaults().override(**overrides)
+        if struct_size is not None:
+            s.struct_size = struct_size
+        self._chk(self.lib.awsm_hip_set_ssao(self.ctx, C.byref(s)), "set_ssao")
+
+    def read_ssao(self):
+        """The last submitted frame's layers -> (A before the smoothing, A' after it, view z; float32 [H, W] each, view z NaN where nothing was hit)."""
+        raw, smoothed, view_z = (np.empty((self.height, self.width), np.float32) for _ in range(3))
+        self._chk(self.lib.awsm_hip_read_ssao(self.ctx, raw.ctypes.data, smoothed.ctypes.data, view_z.ctypes.data), "read_ssao")
+        return raw, smoothed, view_z
 
     def hud_geometry_pass(self, draws):
         """The hud meshes' visibility geometry, between geometry_pass and opaque_pass (render.rs:169-178)."""

@@ -141,6 +141,7 @@ def load_library():
         "awsm_host_clear_post_processing": (C.c_int, [vp]),
         "awsm_host_camera_set_dof": (C.c_int, [vp, C.c_float, C.c_float]),
         "awsm_host_editor_grid_defaults": (C.c_int, [vp, vp]), "awsm_host_set_editor_grid": (C.c_int, [vp, vp]),
+        "awsm_host_ssao_defaults": (C.c_int, [vp, vp]), "awsm_host_set_ssao": (C.c_int, [vp, vp]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
         "awsm_host_texture_insert_kind": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_update_transforms": (C.c_int, [vp]),
         "awsm_host_render": (C.c_int, [vp, C.c_int, vp]), "awsm_host_mirror": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
@@ -605,6 +606,16 @@ class Host:
         g.override(**overrides)
         self._chk(self.lib.awsm_host_set_editor_grid(self.h, C.byref(g)), "set_editor_grid")
 
+    def set_ssao(self, on: bool = True, **overrides):
+        """Screen-space ambient occlusion in the opaque pass of every later render(): the backend's defaults with `overrides`
+        (hip_backend.AwsmSsao's field names: radius, intensity, bias, strength).  on=False turns it off."""
+        if not on:
+            return self._chk(self.lib.awsm_host_set_ssao(self.h, None), "set_ssao")
+        s = hip_backend.AwsmSsao()
+        self._chk(self.lib.awsm_host_ssao_defaults(self.h, C.byref(s)), "ssao_defaults")
+        s.override(**overrides)
+        self._chk(self.lib.awsm_host_set_ssao(self.h, C.byref(s)), "set_ssao")
+
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         """CameraMatrices.focus_distance / .aperture (camera bytes 496-503; the reference's defaults 10.0 and 5.6)."""
         self._chk(self.lib.awsm_host_camera_set_dof(self.h, focus_distance, aperture), "camera_set_dof")
@@ -993,6 +1004,9 @@ class Renderer:
 
     def set_editor_grid(self, on: bool = True, **overrides):
         self.host.set_editor_grid(on, **overrides)
+
+    def set_ssao(self, on: bool = True, **overrides):
+        self.host.set_ssao(on, **overrides)
 
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         self.host.camera_set_dof(focus_distance, aperture)

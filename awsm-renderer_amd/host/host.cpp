@@ -70,6 +70,8 @@ struct Backend {
     int (*post_pass)(AwsmHipCtx*, const AwsmPostParams*) = nullptr;     // optional: a backend without it cannot post-process
     int (*editor_grid_defaults)(AwsmEditorGrid*) = nullptr;             // optional: the editor's ground grid (awsm_host_set_editor_grid)
     int (*set_editor_grid)(AwsmHipCtx*, const AwsmEditorGrid*) = nullptr;
+    int (*ssao_defaults)(AwsmSsao*) = nullptr;                          // optional: screen-space ambient occlusion (awsm_host_set_ssao)
+    int (*set_ssao)(AwsmHipCtx*, const AwsmSsao*) = nullptr;
     // optional: environment cubes at run time (awsm_host_env_cube_*)
     int (*env_cube_create)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t) = nullptr;
     int (*env_cube_write_face)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
@@ -689,6 +691,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.post_pass = reinterpret_cast<decltype(b.post_pass)>(dlsym(b.dl, "awsm_hip_post_pass"));      // optional (awsm_host_set_post_processing)
     b.editor_grid_defaults = reinterpret_cast<decltype(b.editor_grid_defaults)>(dlsym(b.dl, "awsm_hip_editor_grid_defaults"));      // optional (awsm_host_set_editor_grid)
     b.set_editor_grid = reinterpret_cast<decltype(b.set_editor_grid)>(dlsym(b.dl, "awsm_hip_set_editor_grid"));
+    b.ssao_defaults = reinterpret_cast<decltype(b.ssao_defaults)>(dlsym(b.dl, "awsm_hip_ssao_defaults"));      // optional (awsm_host_set_ssao)
+    b.set_ssao = reinterpret_cast<decltype(b.set_ssao)>(dlsym(b.dl, "awsm_hip_set_ssao"));
     b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
     b.env_cube_write_face = reinterpret_cast<decltype(b.env_cube_write_face)>(dlsym(b.dl, "awsm_hip_env_cube_write_face"));
     b.env_cube_write_all_faces = reinterpret_cast<decltype(b.env_cube_write_all_faces)>(dlsym(b.dl, "awsm_hip_env_cube_write_all_faces"));
@@ -1700,6 +1704,20 @@ int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid) {
     if (rc) return dev_fail(h, rc, "set_editor_grid");
     h->grid_on = grid != nullptr;
     return AWSM_OK;
+}
+
+// Screen-space ambient occlusion: a built-in of the backend's opaque pass; the record goes through as it is.
+int awsm_host_ssao_defaults(AwsmHost* h, AwsmSsao* out) {
+    if (!h || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.ssao_defaults) return fail(h, AWSM_ERR_UNSUPPORTED, "ssao_defaults: the backend library has no %s", "awsm_hip_ssao_defaults");
+    const int rc = h->be.ssao_defaults(out);
+    return rc ? dev_fail(h, rc, "ssao_defaults") : AWSM_OK;
+}
+int awsm_host_set_ssao(AwsmHost* h, const AwsmSsao* ssao) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.set_ssao) return fail(h, AWSM_ERR_UNSUPPORTED, "set_ssao: the backend library has no %s", "awsm_hip_set_ssao");
+    const int rc = h->be.set_ssao(h->ctx, ssao);
+    return rc ? dev_fail(h, rc, "set_ssao") : AWSM_OK;
 }
 
 // back to no post pass (this library's default; the reference always runs the effects and display passes)

@@ -11,6 +11,7 @@ device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefilte
 by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
 --hdr FILE projects an equirectangular Radiance .hdr panorama into the skybox (--hdr-size N, default 512; --hdr-yaw R radians turns it about the
 vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl the scene is lit from the file.
+--ssao darkens creases and contact lines: ambient occlusion estimated from the geometry pass's depth (--ssao-radius R in world units, --ssao-intensity I).
 --grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
 """
 import argparse
@@ -46,6 +47,9 @@ def main():
     ap.add_argument("--hdr-yaw", type=float, default=0.0, metavar="R", help="radians added to the panorama's azimuth")
     ap.add_argument("--bake-ibl", action="store_true", help="with --sky-gradient / --env-ktx2 / --hdr: filter the IBL cubes from the skybox on the device")
     ap.add_argument("--grid", action="store_true", help="the editor's ground grid, drawn by the transparent pass")
+    ap.add_argument("--ssao", action="store_true", help="screen-space ambient occlusion from the visibility depth, multiplied into the opaque image")
+    ap.add_argument("--ssao-radius", type=float, default=None, metavar="R", help="with --ssao: the sampling radius in world units (default 0.5)")
+    ap.add_argument("--ssao-intensity", type=float, default=None, metavar="I", help="with --ssao: the estimator's scale (default 1.0)")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -85,6 +89,8 @@ def main():
             r.camera_set_dof(a.focus, a.aperture)
     if a.grid:
         r.set_editor_grid(True)
+    if a.ssao:
+        r.set_ssao(True, **{k: v for k, v in (("radius", a.ssao_radius), ("intensity", a.ssao_intensity)) if v is not None})
     stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
     if post:

@@ -149,7 +149,7 @@ typedef struct AwsmFrameStats {
     float ms_transform;   /* k_deform_transform */
     float ms_bin;         /* k_bin_count + scan + k_bin_fill */
     float ms_raster;      /* k_raster_tile */
-    float ms_shade;       /* k_shade */
+    float ms_shade;       /* k_shade; with SSAO on (awsm_hip_set_ssao) k_ssao_ao + k_ssao_apply too */
     float ms_total;       /* first kernel start -> last kernel end */
     uint32_t triangles_in;      /* sum of tri_count over draws */
     uint32_t triangles_binned;  /* survived cull */
@@ -159,7 +159,7 @@ typedef struct AwsmFrameStats {
     float ms_forward;           /* transparent pass: transform + binning + k_forward_tile */
     uint32_t forward_triangles; /* sum of tri_count (x instances) over the transparent draws */
     uint32_t forward_fragment_slots; /* fragment-list slots the transparent pass used (fragments + the unused tails of the wavefronts' chunks) */
-    float ms_shade_lean;          /* k_shade_lean alone when the opaque pass took the lean route (then ms_shade = this + k_shade_todo), else 0 */
+    float ms_shade_lean;          /* k_shade_lean alone when the opaque pass took the lean route (then ms_shade = this + k_shade_todo), else 0; with SSAO on the two SSAO kernels are in ms_shade as well */
     uint32_t shade_general_wavefronts; /* 16x4-pixel groups of the last opaque pass that went through the general kernel instead of the lean one */
     uint32_t frames_with_dropped_bin_entries; /* enqueue-only frames (no frame_end) whose (triangle, tile) list overflowed since the context was created:
                                          such a frame lost geometry.  The library sizes the list from the need the GPU reports for earlier
@@ -598,6 +598,35 @@ typedef struct AwsmEditorGrid {
 int awsm_hip_editor_grid_defaults(AwsmEditorGrid* out);
 int awsm_hip_set_editor_grid(AwsmHipCtx* ctx, const AwsmEditorGrid* grid /* NULL = off */);
 int awsm_hip_read_editor_grid(AwsmHipCtx* ctx, float* rgba_out, float* depth_out, uint8_t* kept_out);
+
+/* ---- screen-space ambient occlusion (the open "SSAO" box of the reference's docs/ROADMAP.md).  A built-in of awsm_hip_opaque_pass:
+ * behind the shading kernels an occlusion term is estimated per pixel from the WORLD geometry pass's depth (the least of the four samples with MSAA;
+ * never hud_depth, never what the transparent pass writes later) — view positions through the camera snapshot's inv_proj, a normal from the
+ * neighbours' positions, twelve spiral taps within `radius` world units (at most 16 pixels), a 5x5 depth-aware mean — and the RGB of the opaque
+ * image (and of its f32 parity tap) is multiplied by 1 - strength (1 - A') where the pixel was hit: before the opaque -> transparent blit, the
+ * transmission background, the HUD passes, the post pass and any collective read that image.  Transparent meshes and the editor's grid are drawn
+ * over it and not darkened; refraction sees it; the skybox and alpha are untouched.  The whole opaque colour is multiplied, direct light included
+ * (the roadmap would multiply the ambient term inside the shader: no shading kernel is touched here).  Off by default; with it off the pass
+ * runs the kernels it ran before this entry existed.
+ *   defaults   radius 0.5 (world units), intensity 1.0, bias 0.02 (a fraction of the radius), strength 1.0; struct_size = sizeof(AwsmSsao).
+ *   set_ssao   NULL turns it off.  struct_size as for awsm_hip_set_editor_grid (at least its own four bytes, at most 4096; nothing beyond it is
+ *              read, fields it does not reach keep their defaults).  A non-finite value, radius <= 0 or strength outside [0, 1]:
+ *              AWSM_ERR_INVALID_ARGUMENT, and the state stays as it was.  Takes effect from the next awsm_hip_opaque_pass; a pass already
+ *              enqueued (AWSM_CFG_OVERLAP_FRAMES) and a replay by awsm_hip_frame_end keep the record the pass was given.
+ *   read_ssao  the layers of the last submitted frame, width x height f32 each: A before the smoothing, A' after it, and view-space z (NaN where
+ *              nothing was hit).  Any pointer may be NULL.  Synchronous.  AWSM_ERR_NOT_READY unless that frame's opaque pass ran with SSAO on.
+ * On a sharded context (row strips or bands) an opaque pass with SSAO on returns AWSM_ERR_UNSUPPORTED, like the post pass: the stencil needs
+ * rows the shard never rasterised.  A pass with has_opaque = 0 runs without it. ---- */
+typedef struct AwsmSsao {
+    uint32_t struct_size;
+    float radius;        /* world units, > 0 */
+    float intensity;
+    float bias;          /* a fraction of the radius */
+    float strength;      /* 0 .. 1 */
+} AwsmSsao;
+int awsm_hip_ssao_defaults(AwsmSsao* out);
+int awsm_hip_set_ssao(AwsmHipCtx* ctx, const AwsmSsao* ssao /* NULL = off */);
+int awsm_hip_read_ssao(AwsmHipCtx* ctx, float* ao_raw_out, float* ao_smoothed_out, float* view_z_out);
 
 #ifdef __cplusplus
 }

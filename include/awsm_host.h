@@ -251,6 +251,13 @@ int awsm_host_clear_post_processing(AwsmHost* h);
  * lacks awsm_hip_set_editor_grid / awsm_hip_editor_grid_defaults; the backend's own refusals (a non-finite value, a bad struct_size) pass through. */
 int awsm_host_editor_grid_defaults(AwsmHost* h, AwsmEditorGrid* out);
 int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid /* NULL = off */);
+/* Screen-space ambient occlusion (awsm_hip_set_ssao in awsm_hip.h has the rules): a built-in of the backend's opaque pass, off until this is called;
+ * the record is passed through unchanged and holds for every later awsm_host_render.  NULL turns it off again.  ssao_defaults fills the backend's
+ * defaults, to change a field from.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library lacks awsm_hip_set_ssao /
+ * awsm_hip_ssao_defaults; the backend's own refusals (a non-finite value, radius <= 0, strength outside [0, 1], a bad struct_size) pass through, and
+ * so does its AWSM_ERR_UNSUPPORTED from the render of a sharded host. */
+int awsm_host_ssao_defaults(AwsmHost* h, AwsmSsao* out);
+int awsm_host_set_ssao(AwsmHost* h, const AwsmSsao* ssao /* NULL = off */);
 /* CameraMatrices.focus_distance / .aperture (camera.rs:40-52; the reference's defaults are 10.0 and 5.6): camera bytes 496-503, uploaded with
  * the next frame.  Until this is called the host writes 0 and 0. */
 int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture);
