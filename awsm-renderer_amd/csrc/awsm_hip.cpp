@@ -222,6 +222,7 @@ int sync_scene(AwsmHipCtx* c) {
     int rc = upload_small(c, c->scene_dev, &c->scene, sizeof(DevScene));
     if (rc) return rc;
     c->scene_dirty = false;
+    c->scene_uploads++;
     return AWSM_OK;
 }
 
@@ -523,6 +524,25 @@ int enqueue_opaque(AwsmHipCtx* c) {
         if (c->stage_timers && awsm_shade_is_lean(&f) && (rc = record(c, EV_SHADE_LEAN, ss))) return rc;
         (void)awsm_launch_shade_todo(c->scene_dev, &f, ss);
     }
+    // shadows, with the record the frame's shadow pass was submitted with: behind the shading kernels and in FRONT of the occlusion below — both
+    // multiply the same image and each rounds to f16, so the order is part of the contract — and in front of the shade-done signal:
+    // the kernel reads the slot's keys and the slot's map, which the slot's next geometry and shadow passes overwrite.  A replay comes through here
+    // again behind shading kernels that wrote every pixel anew.
+    const AwsmHipCtx::ShadowState& sh = c->shadow_pass[c->slot];
+    if (sh.on && c->shadow_px[c->slot] && f.has_opaque && f.sy1 > f.sy0) {
+        const size_t px = (size_t)c->width * c->height;
+        ShadowArgs a{};
+        a.width = c->width; a.height = c->height;
+        a.vis = (const unsigned long long*)FB(c).vis.ptr;       // the WORLD's keys (see below)
+        a.camera = (const float*)f.camera;
+        a.map = (const uint32_t*)c->shadow[c->slot].vis.ptr; a.map_size = sh.p.map_size; a.pcf_radius = (int32_t)sh.p.pcf_radius;
+        memcpy(a.light_view_proj, sh.light_view_proj, sizeof a.light_view_proj); memcpy(a.light, sh.p.light, sizeof a.light);
+        a.bias = sh.p.bias; a.slope_bias = sh.p.slope_bias; a.max_slope = sh.p.max_slope; a.strength = sh.p.strength; a.facing_fade = sh.p.facing_fade;
+        a.visibility = (float*)c->shadow_layers[c->slot].ptr; a.multiplier = a.visibility + px;
+        a.out16 = (uint2*)f.out_rgba16f; a.out32 = (float4*)f.out_rgba32f;
+        a.poison = f.poison; a.frame_serial = f.frame_serial;
+        awsm_launch_shadow_resolve(&a, c->msaa == 4 ? 4u : 1u, ss);
+    }
     // screen-space ambient occlusion, with the record this pass was submitted with: behind the shading kernels — it modulates their image in place —
     // and in front of the shade-done signal below: it reads the slot's keys, which the slot's next geometry pass overwrites.  A replay
     // (awsm_hip_frame_end) comes through here again behind shading kernels that wrote every pixel anew, so the image is modulated once.
@@ -684,23 +704,30 @@ int build_draw_list(AwsmHipCtx* c, const char* pass, const AwsmDraw* draws, uint
 
 // per-pass device state sized for `draws_host` / total_tris; uploads the draw list when it changed
 // raster items: one per tile + one per extra slice of a split tile (<= entries / 256); scratch tiles: one per slice of a split tile
-int reserve_raster_items(AwsmHipCtx* c, FrameBufs& b, bool forward) {
-    const uint32_t tiles_x = (c->width + kTile - 1) / kTile, tiles_y_full = (c->height + kTile - 1) / kTile;
+// The frame a pass's tile tables are sized for: the context's, or the light's S x S single-sampled map (awsm_hip_shadow_pass).
+struct PassDims { uint32_t w, h, samples; };
+inline PassDims dims_of(const AwsmHipCtx* c, const FrameBufs& b) {
+    if (b.kind == kPassShadow) { const uint32_t S = c->shadow_pass[b.slot].p.map_size; return {S, S, 1u}; }
+    return {c->width, c->height, c->msaa == 4u ? 4u : 1u};
+}
+
+int reserve_raster_items(AwsmHipCtx* c, FrameBufs& b, bool forward, PassDims dm) {
+    const uint32_t tiles_x = (dm.w + kTile - 1) / kTile, tiles_y_full = (dm.h + kTile - 1) / kTile;
     const size_t n_tiles_full = (size_t)tiles_x * tiles_y_full;
     const uint32_t extra_cap = forward ? 0u : b.bin_capacity / 256u + 1u, slot_cap = forward ? 0u : b.bin_capacity / 128u + 2u;
     int rc;
     if ((rc = dev_reserve(c, b.tile_order, (n_tiles_full + extra_cap) * 4))) return rc;
-    if (!forward && (rc = dev_reserve(c, b.raster_scratch, (size_t)slot_cap * kTile * kTile * 8 * (c->msaa == 4u ? 4u : 1u)))) return rc;
+    if (!forward && (rc = dev_reserve(c, b.raster_scratch, (size_t)slot_cap * kTile * kTile * 8 * dm.samples))) return rc;
     b.raster_extra_cap = extra_cap; b.raster_slot_cap = slot_cap;
     return AWSM_OK;
 }
 
 // Device state of one pass in one frame slot, sized for `tri_cap` triangles and `draw_cap` draws.
-int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_cap, bool forward) {
+int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_cap, bool forward, PassDims dm) {
     int rc;
     const size_t nd = std::max<size_t>(draw_cap, 1), nv = std::max<size_t>(3 * tri_cap, 1), nt = std::max<size_t>(tri_cap, 1);
     if ((rc = dev_reserve(c, b.draws_dev, nd * sizeof(DrawDev)))) return rc;
-    const bool world_pass = &b >= c->fb && &b < c->fb + kSlots;
+    const bool world_pass = b.kind == kPassWorld, shadow = b.kind == kPassShadow;
     if (world_pass && c->geometry_cache) {      // geometry cache: the previous list beside the current one, world positions per vertex
         if ((rc = dev_reserve(c, b.draws_prev, nd * sizeof(DrawDev)))) return rc;
         if ((rc = dev_reserve(c, b.wcache, nv * 16))) return rc;
@@ -710,19 +737,20 @@ int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_c
         if (b.cache_mark.size < blocks_bound * 4) { if ((rc = dev_realloc(c, b.cache_mark, (blocks_bound + blocks_bound / 2) * 4, true))) return rc; }
     }
     b.cache_valid = false;      // the arrays may have moved
-    if ((rc = dev_reserve(c, b.draw_shade, nd * sizeof(DrawShadeDev)))) return rc;
-    if ((rc = dev_reserve(c, b.tex_slots, nd * kCoreTextures * sizeof(TexSlotDev)))) return rc;
-    if ((rc = dev_reserve(c, b.draw_mat, nd * sizeof(DrawMatDev)))) return rc;
+    // (the shadow pass has no per-draw resolve and nothing shades from it: no per-draw records, no per-triangle attribute offsets, no lean records)
+    if (!shadow && (rc = dev_reserve(c, b.draw_shade, nd * sizeof(DrawShadeDev)))) return rc;
+    if (!shadow && (rc = dev_reserve(c, b.tex_slots, nd * kCoreTextures * sizeof(TexSlotDev)))) return rc;
+    if (!shadow && (rc = dev_reserve(c, b.draw_mat, nd * sizeof(DrawMatDev)))) return rc;
     if ((rc = dev_reserve(c, b.clip, nv * 16))) return rc;
     if ((rc = dev_reserve(c, b.nrm, nv * 16))) return rc;
     if ((rc = dev_reserve(c, b.tan, nv * 16))) return rc;
     if (forward && (rc = dev_reserve(c, b.wpos, nv * 16))) return rc;
     if ((rc = dev_reserve(c, b.tri_flags, nt * 4))) return rc;
-    if (!forward && (rc = dev_reserve(c, b.tri_shade, nt * 32))) return rc;
-    if (!forward && (rc = dev_reserve(c, b.draw_lean, nd * sizeof(LeanDrawDev)))) return rc;
+    if (!forward && !shadow && (rc = dev_reserve(c, b.tri_shade, nt * 32))) return rc;
+    if (!forward && !shadow && (rc = dev_reserve(c, b.draw_lean, nd * sizeof(LeanDrawDev)))) return rc;
     if ((rc = dev_reserve(c, b.big_list, nt * 4))) return rc;
     if ((rc = dev_reserve(c, b.tri_rec, nt * kTriRecBytes))) return rc;
-    const uint32_t tiles_x = (c->width + kTile - 1) / kTile, tiles_y_full = (c->height + kTile - 1) / kTile;
+    const uint32_t tiles_x = (dm.w + kTile - 1) / kTile, tiles_y_full = (dm.h + kTile - 1) / kTile;
     const size_t n_tiles_full = (size_t)tiles_x * tiles_y_full;
     if ((rc = dev_reserve(c, b.tile_count, n_tiles_full * 4))) return rc;
     if ((rc = dev_reserve(c, b.tile_offset, (n_tiles_full + 1) * 4))) return rc;
@@ -730,25 +758,28 @@ int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_c
     if ((rc = dev_reserve(c, b.tile_split, n_tiles_full * 8))) return rc;
     if ((rc = dev_reserve(c, b.scan_tmp, (((n_tiles_full + 255) / 256) * 2 + 1) * 40 * 4))) return rc;      // kScanWords = 40: aggregates, bases, run starts (kernels_geometry.hip)
     if ((rc = ensure_bin_capacity_of(c, b, (c->flags & AWSM_CFG_SMALL_BIN_LIST) ? 4096u : (uint32_t)std::min<size_t>(std::max<size_t>(4 * tri_cap + 65536u, 1u << 18), 0xFFFFFFF0u)))) return rc;
-    if ((rc = reserve_raster_items(c, b, forward))) return rc;
-    b.tri_cap = tri_cap; b.draw_cap = draw_cap; b.sized_w = c->width; b.sized_h = c->height;
+    if ((rc = reserve_raster_items(c, b, forward, dm))) return rc;
+    b.tri_cap = tri_cap; b.draw_cap = draw_cap; b.sized_w = dm.w; b.sized_h = dm.h;
     return AWSM_OK;
 }
 
 // Sizes the pass's device state for `draws_host` / total_tris (see reserve_pass_buffers).
 int ensure_pass_capacity(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>& draws_host, uint32_t total_tris, bool forward) {
     int rc;
-    if (total_tris > b.tri_cap || draws_host.size() > b.draw_cap || b.sized_w != c->width || b.sized_h != c->height || !b.bin_list.ptr) {
+    const PassDims dm = dims_of(c, b);
+    if (total_tris > b.tri_cap || draws_host.size() > b.draw_cap || b.sized_w != dm.w || b.sized_h != dm.h || !b.bin_list.ptr) {
         bool instanced = false;
         for (const DrawDev& d : draws_host) instanced |= (d.flags & kDrawInstanced) != 0;
         const size_t tri_bound = forward || instanced ? ~size_t(0) : c->bufs[AWSM_BUF_VIS_GEOM_DATA].size / 168u;
         const size_t tri_cap = std::max<size_t>(std::min<size_t>((size_t)total_tris + total_tris / 4 + 4096, std::max<size_t>(tri_bound, total_tris)), b.tri_cap);
         const size_t draw_cap = std::max<size_t>(draws_host.size() + draws_host.size() / 4 + 64, b.draw_cap);
-        FrameBufs* set = forward ? ((&b >= c->htr && &b < c->htr + kSlots) ? c->htr : c->tr) : ((&b >= c->hud && &b < c->hud + kSlots) ? c->hud : c->fb);
-        for (int sl = 0; sl < n_slots(c); sl++) {
+        const bool shadow = b.kind == kPassShadow;      // (the light's pass: this slot's alone — the other slot's map may have another size)
+        FrameBufs* const sets[] = {c->fb, c->tr, c->hud, c->htr, c->shadow};      // in PassKind's order
+        FrameBufs* set = sets[b.kind];
+        for (int sl = 0; sl < (shadow ? 1 : n_slots(c)); sl++) {
             // (the slot in use first: if memory runs out half-way the current frame still has its buffers)
             FrameBufs& t = set[(c->slot + sl) % kSlots];
-            if ((rc = size_pass_buffers(c, t, std::max(tri_cap, t.tri_cap), std::max(draw_cap, t.draw_cap), forward))) return rc;
+            if ((rc = size_pass_buffers(c, t, std::max(tri_cap, t.tri_cap), std::max(draw_cap, t.draw_cap), forward, dm))) return rc;
         }
     }
     return AWSM_OK;
@@ -801,7 +832,7 @@ int upload_draw_list(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>& dr
 int reserve_pass_buffers(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>& draws_host, uint32_t total_tris, bool forward) {
     int rc = ensure_pass_capacity(c, b, draws_host, total_tris, forward);
     if (rc) return rc;
-    return upload_draw_list(c, b, draws_host, !forward && &b >= c->fb && &b < c->fb + kSlots);
+    return upload_draw_list(c, b, draws_host, b.kind == kPassWorld);
 }
 
 int ensure_bin_capacity(AwsmHipCtx* c, uint32_t entries) { return ensure_bin_capacity_of(c, FB(c), entries); }
@@ -824,6 +855,10 @@ int awsm_hip_create(const AwsmConfig* cfg, AwsmHipCtx** out) {
     if (!c) return AWSM_ERR_OUT_OF_MEMORY;
     c->device = cfg->device;
     c->flags = cfg->flags;
+    for (int s = 0; s < kSlots; s++) {
+        FrameBufs* const of_kind[] = {&c->fb[s], &c->tr[s], &c->hud[s], &c->htr[s], &c->shadow[s]};      // in PassKind's order
+        for (int k = 0; k < 5; k++) { of_kind[k]->kind = (PassKind)k; of_kind[k]->slot = (uint8_t)s; }
+    }
     auto bail = [&](int code) { awsm_hip_destroy(c); return code; };
     if (hipSetDevice(c->device) != hipSuccess) return bail(AWSM_ERR_DEVICE);
     hipDeviceProp_t prop;
@@ -923,9 +958,10 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); fr(c->grid_layer); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->ssao_layers) fr(b);
+    for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
-    for (int k = 0; k < 4 * kSlots; k++) {
-        FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : c->htr[k - 3 * kSlots]));
+    for (int k = 0; k < 5 * kSlots; k++) {
+        FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : (k < 4 * kSlots ? c->htr[k - 3 * kSlots] : c->shadow[k - 4 * kSlots])));
         fr(b.vis); fr(b.wpos); fr(b.frag_rec); fr(b.frag_color); fr(b.frag_first); fr(b.tex_slots); fr(b.draw_mat); fr(b.clip); fr(b.nrm); fr(b.tan); fr(b.tri_rec); fr(b.tri_flags); fr(b.tri_shade); fr(b.draw_lean); fr(b.draws_dev); fr(b.draw_shade); fr(b.tile_count); fr(b.tile_offset);
         fr(b.wcache); fr(b.draws_prev); fr(b.cache_mark); fr(b.block_map); fr(b.tile_cursor); fr(b.tile_order); fr(b.scan_tmp); fr(b.tile_split); fr(b.raster_scratch); fr(b.bin_list); fr(b.big_list); fr(b.counters); fr(b.camera);
     }
@@ -1182,6 +1218,7 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
         }
     }
     ht.mark("geometry_pass: slot-free wait");
+    c->shadow_done = false; c->shadow_pass[c->slot].on = false; c->shadow_px[c->slot] = 0;      // no shadow pass in a frame: no shadow in that frame
     c->draws_api.assign(draws, draws + n);
     c->draws_host.swap(new_draws);
     {   // What earlier frames needed in their (triangle, tile) lists, as far as the GPU has reported it (pinned words written by k_bin_scan;
@@ -1199,7 +1236,7 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
         for (int s = 0; s < n_slots(c); s++)
             if (need && (uint64_t)need * 4 > (uint64_t)c->fb[s].bin_capacity * 3 && c->fb[s].bin_list.ptr && !(c->flags & AWSM_CFG_SMALL_BIN_LIST)) {
                 if ((rc = ensure_bin_capacity_of(c, c->fb[s], need + need / 2 + 1024))) return rc;
-                if ((rc = reserve_raster_items(c, c->fb[s], false))) return rc;
+                if ((rc = reserve_raster_items(c, c->fb[s], false, dims_of(c, c->fb[s])))) return rc;
             }
     }
     c->total_tris = (uint32_t)tris; c->total_verts = (uint32_t)(3 * tris); c->n_blocks = (uint32_t)blocks;
@@ -1320,6 +1357,143 @@ int awsm_hip_hud_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n)
     return AWSM_OK;
 }
 
+// ---- shadows: the geometry pass from the light (kernels_shadow.hip holds the resolve) ----
+// The casters through the world pass's kernels into the slot's S x S map, with buffers of its own and the precautions of enqueue_hud_geometry: no
+// camera snapshot, no status words, the opaque pass's lists nulled, no geometry cache — nothing the world pass left is reset.  k_deform_transform
+// reads view_proj through the scene table: it is given the slot's second copy of the table, whose camera entry is the slot's copy of the light block.
+static int enqueue_shadow(AwsmHipCtx* c) {
+    FrameBufs& sb = c->shadow[c->slot];
+    const uint32_t S = c->shadow_pass[c->slot].p.map_size;
+    FrameDev f;
+    memset(&f, 0, sizeof f);
+    f.width = S; f.height = S; f.y0 = 0; f.y1 = S; f.sy0 = 0; f.sy1 = S;
+    f.tiles_x = (S + kTile - 1) / kTile; f.tiles_y = f.tiles_x; f.tile_row0 = 0;
+    f.band_n = 1; f.band_r = 0; f.out_compact = 0;
+    f.n_draws = (uint32_t)c->shadow_draws_host.size();
+    f.total_tris = c->shadow_total_tris; f.total_verts = 3u * c->shadow_total_tris;
+    f.bin_capacity = sb.bin_capacity;
+    f.msaa = 0;                                  // single-sampled, whatever the frame is
+    f.camera = (const uint8_t*)c->shadow_cam[c->slot].ptr;
+    f.draws = (const DrawDev*)sb.draws_dev.ptr;
+    f.clip = (float4*)sb.clip.ptr; f.nrm = (float4*)sb.nrm.ptr; f.tan = (float4*)sb.tan.ptr;
+    f.tri_info = (uint32_t*)sb.tri_flags.ptr;
+    f.tri_rec = (TriRec*)sb.tri_rec.ptr;
+    f.tile_count = (uint32_t*)sb.tile_count.ptr; f.tile_offset = (uint32_t*)sb.tile_offset.ptr;
+    f.tile_cursor = (uint32_t*)sb.tile_cursor.ptr; f.bin_list = (uint32_t*)sb.bin_list.ptr;
+    f.tile_order = (uint32_t*)sb.tile_order.ptr; f.scan_tmp = (uint32_t*)sb.scan_tmp.ptr;
+    f.tile_split = (uint32_t*)sb.tile_split.ptr; f.raster_scratch = (unsigned long long*)sb.raster_scratch.ptr;
+    f.raster_extra_cap = sb.raster_extra_cap; f.raster_slot_cap = sb.raster_slot_cap;
+    f.big_list = (uint32_t*)sb.big_list.ptr;
+    f.counters = (uint32_t*)sb.counters.ptr;
+    f.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
+    f.frame_serial = c->frame_serial;
+    f.vis = (unsigned long long*)sb.vis.ptr;     // every tile of the map is written: a tile without casters becomes "no hit"
+    int rc;
+    if ((rc = sync_scene(c))) return rc;
+    if (c->shadow_scene_seq[c->slot] != c->scene_uploads) {      // the scene table was uploaded since the copy was made
+        DevScene sc = c->scene;
+        sc.buf[AWSM_BUF_CAMERA] = (const uint8_t*)c->shadow_cam[c->slot].ptr;
+        if ((rc = upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc))) return rc;
+        c->shadow_scene_seq[c->slot] = c->scene_uploads;
+    }
+    const uint32_t n_tiles = f.tiles_x * f.tiles_y;
+    if (!f.total_tris) {      // otherwise k_deform_transform clears counters + tile_count (enqueue_geometry)
+        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, 8 * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync((uint32_t*)sb.counters.ptr + 12, 0, 2 * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(sb.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), c->stream));
+    } else {
+        awsm_launch_transform(c->shadow_scene[c->slot], &f, c->shadow_n_blocks, c->stream);
+        awsm_launch_bin_count(&f, c->stream); awsm_launch_bin_big(&f, 0, c->stream);
+    }
+    awsm_launch_bin_scan(&f, c->stream);
+    if (f.total_tris) { awsm_launch_bin_fill(&f, c->stream); awsm_launch_bin_big(&f, 1, c->stream); }
+    awsm_launch_raster(&f, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+int awsm_hip_shadow_defaults(AwsmShadow* out) {
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    static const AwsmShadow d = {(uint32_t)sizeof(AwsmShadow), 2048u, 1u, {0.0f, 1.0f, 0.0f, 0.0f}, 1e-3f, 1.0f, 0.05f, 0.7f, 0.1f};
+    *out = d;
+    return AWSM_OK;
+}
+
+int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_camera, size_t camera_bytes, const AwsmDraw* casters, uint32_t n) {
+    if (!c || !s || (!casters && n)) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!c->geometry_done || c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass goes between the geometry pass and the opaque pass of a frame");
+    if (c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height)))
+        return fail(c, AWSM_ERR_UNSUPPORTED, "shadow_pass on a sharded context: the resolve's neighbours need rows the shard never rasterised (no halo exchange)");
+    AwsmShadow full;
+    awsm_hip_shadow_defaults(&full);
+    if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: AwsmShadow.struct_size = %u (set it to sizeof(AwsmShadow))", s->struct_size);
+    memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, (std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3) - 4);      // whole fields only; the rest keeps its defaults
+    if (!light_camera || camera_bytes != 512) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", camera_bytes);
+    const float* v = full.light;
+    for (size_t i = 0; i < 9; i++)      // light[4] and the five parameters are contiguous
+        if (!std::isfinite(v[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: value %zu of the record is not finite", i);
+    static_assert(offsetof(AwsmShadow, facing_fade) == offsetof(AwsmShadow, light) + 8 * sizeof(float) && sizeof(AwsmShadow) == 48, "AwsmShadow: light[4] and five floats behind three words");
+    float lvp[16];
+    memcpy(lvp, (const uint8_t*)light_camera + 128, sizeof lvp);
+    for (float m : lvp) if (!std::isfinite(m)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: the light camera's view_proj is not finite");
+    if (full.map_size < 1u || full.map_size > 8192u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: map_size = %u (1 .. 8192)", full.map_size);
+    if (full.pcf_radius > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: pcf_radius = %u (0, 1 or 2)", full.pcf_radius);
+    if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: strength = %g (0 .. 1)", (double)full.strength);
+    if (!(full.facing_fade > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: facing_fade = %g (> 0)", (double)full.facing_fade);
+    if (!(full.max_slope >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: max_slope = %g (>= 0)", (double)full.max_slope);
+    if (full.light[3] != 0.0f && full.light[3] != 1.0f) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: light[3] = %g (0: directional, 1: spot)", (double)full.light[3]);
+    static const AwsmBuf need[] = {AWSM_BUF_TRANSFORMS, AWSM_BUF_GEOM_META, AWSM_BUF_VIS_GEOM_DATA};
+    if (n) for (AwsmBuf b : need) if (!c->bufs[b].ptr) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass: buffer %d missing", (int)b);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<DrawDev> list;
+    uint64_t tris = 0, blocks = 0;
+    int rc = build_draw_list(c, "shadow_pass", casters, n, AWSM_BUF_VIS_GEOM_DATA, 168u, list, &tris, &blocks);
+    if (rc) return rc;
+    // nothing refused from here on but for memory: the slot's state is this pass's
+    FrameBufs& sb = c->shadow[c->slot];
+    AwsmHipCtx::ShadowState& st = c->shadow_pass[c->slot];
+    c->shadow_done = false; st.on = false;
+    st.p = full; memcpy(st.light_view_proj, lvp, sizeof lvp);
+    c->shadow_draws_host.swap(list);
+    c->shadow_total_tris = (uint32_t)tris; c->shadow_n_blocks = (uint32_t)blocks;
+    if (!sb.counters.ptr) {
+        HIPCHK(c, hipMalloc(&sb.counters.ptr, 16 * sizeof(uint32_t)));
+        sb.counters.size = 16 * sizeof(uint32_t);
+        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, sb.counters.size, c->stream));
+    }
+    if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
+    if ((rc = dev_reserve(c, c->shadow_cam[c->slot], 512))) return rc;
+    if ((rc = dev_reserve(c, sb.vis, (size_t)full.map_size * full.map_size * 8))) return rc;
+    if ((rc = reserve_pass_buffers(c, sb, c->shadow_draws_host, c->shadow_total_tris, false))) return rc;
+    if ((rc = upload_small(c, c->shadow_cam[c->slot].ptr, light_camera, 512))) return rc;      // through the pinned ring, as small writes are
+    if ((rc = enqueue_shadow(c))) return rc;
+    st.on = true; c->shadow_done = true;
+    return AWSM_OK;
+}
+
+int awsm_hip_read_shadow_map(AwsmHipCtx* c, uint64_t* keys) {
+    if (!c || !keys) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!c->shadow_done || !c->shadow[c->slot].vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_shadow_map: the last submitted frame had no shadow pass");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    const size_t S = c->shadow_pass[c->slot].p.map_size;
+    HIPCHK(c, hipMemcpy(keys, c->shadow[c->slot].vis.ptr, S * S * 8, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+int awsm_hip_read_shadow(AwsmHipCtx* c, float* visibility, float* multiplier) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    const size_t px = (size_t)c->width * c->height;
+    if (!px || !c->shadow_done || !c->opaque_done || c->shadow_px[c->slot] != px || !c->shadow_layers[c->slot].ptr)
+        return fail(c, AWSM_ERR_NOT_READY, "read_shadow: the last submitted frame had no shadow pass with an opaque pass (has_opaque) behind it");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    const float* d = (const float*)c->shadow_layers[c->slot].ptr;
+    if (visibility) HIPCHK(c, hipMemcpy(visibility, d, px * 4, hipMemcpyDeviceToHost));
+    if (multiplier) HIPCHK(c, hipMemcpy(multiplier, d + px, px * 4, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
 int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     if (!c || !p) return AWSM_ERR_INVALID_ARGUMENT;
     if (p->mipmap > 1) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "opaque_pass: mipmap must be 0 (MipmapMode::None) or 1 (MipmapMode::Gradient)");
@@ -1345,6 +1519,10 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     c->ssao_pass[c->slot] = c->ssao;
     c->ssao_pass[c->slot].on = ssao_on;
     c->ssao_px[c->slot] = ssao_on ? (size_t)c->width * c->height : 0;
+    // shadows: the frame had a shadow pass (awsm_hip_shadow_pass) — its resolve goes behind this pass's shading kernels; V and m per frame slot, allocated at the first use
+    const bool shadow_on = c->shadow_done && c->shadow_pass[c->slot].on && p->has_opaque;
+    if (shadow_on) { const int rcs = dev_reserve(c, c->shadow_layers[c->slot], (size_t)c->width * c->height * 8); if (rcs) return rcs; }
+    c->shadow_px[c->slot] = shadow_on ? (size_t)c->width * c->height : 0;
     c->last_opaque = *p;
     if (!p->has_opaque && c->camera_written_since_snapshot && c->bufs[AWSM_BUF_CAMERA].ptr) {
         // the "empty" pipeline (skybox only) may run without a geometry pass of its own: it then has no snapshot of the camera it was given.  Rare
@@ -1481,14 +1659,16 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         if (c->overlap) { HIPCHK(c, sync_shade_streams(c)); for (bool& b : c->shade_pending) b = false; }
         { int rch = handoff_check(c); if (rch) return rch; }      // a gate ended unopened: the frame it guarded was dropped
         memset(c->counters_host + 8, 0, 8 * sizeof(uint32_t));
-        uint32_t hud_fwd[8] = {}, hud_geo[8] = {};      // the HUD transparent pass's and the HUD geometry pass's own counters (same layout)
+        uint32_t hud_fwd[8] = {}, hud_geo[8] = {}, shadow_geo[8] = {};      // the HUD transparent pass's, the HUD geometry pass's and the shadow pass's own counters (same layout)
+        if (c->shadow_done) HIPCHK(c, hipMemcpy(shadow_geo, c->shadow[c->slot].counters.ptr, sizeof shadow_geo, hipMemcpyDeviceToHost));
         if (c->transparent_done) HIPCHK(c, hipMemcpy(c->counters_host + 8, c->tr[c->slot].counters.ptr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (c->hud_transparent_done) HIPCHK(c, hipMemcpy(hud_fwd, c->htr[c->slot].counters.ptr, sizeof hud_fwd, hipMemcpyDeviceToHost));
         if (c->hud_geometry_done) HIPCHK(c, hipMemcpy(hud_geo, c->hud[c->slot].counters.ptr, sizeof hud_geo, hipMemcpyDeviceToHost));
         const bool geom_over = c->geometry_done && c->counters_host[2] != 0, fwd_over = c->transparent_done && c->counters_host[10] != 0;
         const bool frag_over = c->transparent_done && c->counters_host[14] != 0;      // a pixel's fragment list did not fit
         const bool hud_geo_over = c->hud_geometry_done && hud_geo[2] != 0, hud_fwd_over = c->hud_transparent_done && hud_fwd[2] != 0, hud_frag_over = c->hud_transparent_done && hud_fwd[6] != 0;
-        still_over = geom_over || fwd_over || frag_over || hud_geo_over || hud_fwd_over || hud_frag_over;
+        const bool shadow_over = c->shadow_done && shadow_geo[2] != 0;
+        still_over = geom_over || fwd_over || frag_over || hud_geo_over || hud_fwd_over || hud_frag_over || shadow_over;
         if (!still_over || attempt >= 4) break;
         // a list overflowed: grow it to the measured need and replay from the first pass that lost entries.  The passes of a frame are replayed in their
         // order — the HUD transparent pass blends into the composite in place, so it is never replayed by itself: the world transparent pass (which
@@ -1497,16 +1677,22 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         c->overflow_retries++;
         if (geom_over) {
             if ((rc = ensure_bin_capacity(c, c->counters_host[1] + c->counters_host[1] / 4 + 1024))) return rc;
-            if ((rc = reserve_raster_items(c, FB(c), false))) return rc;
+            if ((rc = reserve_raster_items(c, FB(c), false, dims_of(c, FB(c))))) return rc;
             if ((rc = enqueue_geometry(c, true))) return rc;
         }
         if (hud_geo_over || (geom_over && c->hud_geometry_done && c->hud_merged)) {      // (merged keys: a new world pass needs a new merge)
             FrameBufs& hb = c->hud[c->slot];
             if (hud_geo_over && (rc = ensure_bin_capacity_of(c, hb, hud_geo[1] + hud_geo[1] / 4 + 1024))) return rc;
-            if (hud_geo_over && (rc = reserve_raster_items(c, hb, false))) return rc;
+            if (hud_geo_over && (rc = reserve_raster_items(c, hb, false, dims_of(c, hb)))) return rc;
             if ((rc = enqueue_hud_geometry(c))) return rc;
         }
-        if ((geom_over || hud_geo_over) && c->opaque_done && (rc = enqueue_opaque(c))) return rc;
+        if (shadow_over) {      // the light's pass, in its place between the geometry passes and the opaque pass; the light block is still in the slot's copy
+            FrameBufs& sb = c->shadow[c->slot];
+            if ((rc = ensure_bin_capacity_of(c, sb, shadow_geo[1] + shadow_geo[1] / 4 + 1024))) return rc;
+            if ((rc = reserve_raster_items(c, sb, false, dims_of(c, sb)))) return rc;
+            if ((rc = enqueue_shadow(c))) return rc;
+        }
+        if ((geom_over || hud_geo_over || shadow_over) && c->opaque_done && (rc = enqueue_opaque(c))) return rc;
         if (fwd_over && (rc = ensure_bin_capacity_of(c, c->tr[c->slot], c->counters_host[9] + c->counters_host[9] / 4 + 1024))) return rc;
         if (frag_over && (rc = ensure_fragment_capacity(c, c->tr[c->slot], c->counters_host[13] + c->counters_host[13] / 4 + 1024))) return rc;
         if (hud_fwd_over && (rc = ensure_bin_capacity_of(c, c->htr[c->slot], hud_fwd[1] + hud_fwd[1] / 4 + 1024))) return rc;

@@ -25,6 +25,9 @@ struct DevBuf {
 
 enum { EV_START = 0, EV_TRANSFORM, EV_BIN, EV_RASTER, EV_SHADE_BEGIN, EV_SHADE_LEAN, EV_SHADE, EV_FWD_BEGIN, EV_FWD, EV_COUNT };
 
+// Which pass a FrameBufs serves: AwsmHipCtx::fb, tr, hud, htr, shadow in that order (set once by awsm_hip_create).
+enum PassKind : uint8_t { kPassWorld = 0, kPassTransparent, kPassHud, kPassHudTransparent, kPassShadow };
+
 // Everything the geometry pass produces for one frame and the opaque pass consumes.
 struct FrameBufs {
     DevBuf wpos;                           // transparent pass only
@@ -65,6 +68,8 @@ struct FrameBufs {
     bool cache_had_tri_shade = false;
     uint64_t cache_seq = 0;                // write_seq when that geometry pass was enqueued: dirty ranges logged after it apply
     uint32_t cache_serial = 0;             // its frame serial
+    PassKind kind = kPassWorld;            // which pass this is, and its frame slot (two bytes of the struct's tail padding: every other member keeps its offset)
+    uint8_t slot = 0;
 };
 
 }  // namespace awsm
@@ -221,10 +226,25 @@ struct AwsmHipCtx {
 
     // screen-space ambient occlusion (awsm_hip_set_ssao): what the caller last set, and per frame slot what the slot's opaque pass was enqueued with
     // (awsm_hip_frame_end replays the pass with that); ssao_layers: per slot [3][px] f32 — A, A', view z — sized for ssao_px pixels.
-    // (Last in the struct: every member above keeps the offset it had.)
+    // (New state goes to the end of the struct, the shadows' below likewise: every older member keeps the offset it had.)
     struct SsaoState { bool on = false; float p[4] = {}; } ssao, ssao_pass[kSlots];
     DevBuf ssao_layers[kSlots];
     size_t ssao_px[kSlots] = {};     // pixels of the frame the slot's layers were last written for (0: never)
+
+    // shadows (awsm_hip_shadow_pass).  shadow[slot]: the light's geometry pass's own vertex arrays, setup records, tile tables, lists and
+    // keys (vis = the S x S map), as hud[slot] is the HUD geometry pass's.  shadow_scene[slot]: a second device copy of the scene table whose camera
+    // entry is shadow_cam[slot], the slot's copy of the light block — k_deform_transform reads view_proj through the table (shadow_scene_seq: the
+    // scene_uploads count it was copied at).  shadow_pass[slot]: what the slot's pass was enqueued with, into the resolve's arguments and a replay.
+    FrameBufs shadow[kSlots];
+    DevScene* shadow_scene[kSlots] = {};
+    uint64_t shadow_scene_seq[kSlots] = {}, scene_uploads = 0;
+    DevBuf shadow_cam[kSlots];
+    std::vector<DrawDev> shadow_draws_host;
+    uint32_t shadow_total_tris = 0, shadow_n_blocks = 0;
+    bool shadow_done = false;        // this frame had a shadow pass
+    struct ShadowState { bool on = false; AwsmShadow p{}; float light_view_proj[16] = {}; } shadow_pass[kSlots];
+    DevBuf shadow_layers[kSlots];    // per slot [2][px] f32: V, m
+    size_t shadow_px[kSlots] = {};   // pixels of the frame the slot's layers were last written for (0: that frame had no resolve)
 };
 
 #define HIPCHK(c, call)                                                                            \

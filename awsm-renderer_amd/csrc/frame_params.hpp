@@ -299,6 +299,25 @@ struct SsaoArgs {
     uint32_t frame_serial;
 };
 
+// Shadows (kernels_shadow.hip, awsm_hip_shadow_pass): what k_shadow_resolve, enqueued behind an opaque pass whose frame had a shadow pass, reads and writes.
+struct ShadowArgs {
+    uint32_t width, height;
+    const unsigned long long* vis;       // the WORLD geometry pass's keys (x4 with MSAA): never the hud's, never the merged ones
+    const float* camera;                 // the frame's camera snapshot (512 B): inv_view_proj at floats 48..63, position at 96..98
+    const uint32_t* map;                 // the slot's S x S shadow keys as words: [2 i] the low word, [2 i + 1] the depth
+    uint32_t map_size;                   // S
+    int32_t pcf_radius;                  // R
+    float light_view_proj[16];           // bytes 128..191 of the light block, column-major
+    float light[4];
+    float bias, slope_bias, max_slope, strength, facing_fade;
+    float* visibility;                   // per pixel, per frame slot: V and m
+    float* multiplier;
+    uint2* out16;                        // the opaque image, modulated in place
+    float4* out32;                       // its f32 parity tap (may be null)
+    const uint32_t* poison;              // FrameDev.poison / frame_serial
+    uint32_t frame_serial;
+};
+
 #ifdef __HIPCC__
 // A hand-off gate that gave up (its signal never came within the time budget) has poisoned the frame it guarded: its kernels must not run on
 // buffers that are half written, or still being read.  Wave-uniform, one scalar load.

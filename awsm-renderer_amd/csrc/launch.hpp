@@ -43,6 +43,8 @@ void awsm_launch_rgba16f_to_rg16f(const uint16_t* in, uint32_t* out, uint32_t n,
 void awsm_launch_post(const awsm::PostArgs* args, uint32_t flags, uint32_t msaa, void* bloom_a, void* bloom_b, hipStream_t s);
 // kernels_ssao.hip
 void awsm_launch_ssao(const awsm::SsaoArgs* args, uint32_t msaa, hipStream_t s);
+// kernels_shadow.hip
+void awsm_launch_shadow_resolve(const awsm::ShadowArgs* args, uint32_t msaa, hipStream_t s);
 // kernels_env.hip
 void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s);
 void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, uint2* dst, uint32_t n, hipStream_t s);

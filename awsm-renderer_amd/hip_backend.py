@@ -41,7 +41,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_texture_array_generate_mips_layers", "awsm_hip_texture_array_info",
            "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read",
            "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid",
-           "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao"]
+           "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao",
+           "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow"]
 
 
 class AwsmConfig(C.Structure):
@@ -88,6 +89,25 @@ class AwsmSsao(C.Structure):
             if k not in names or k == "struct_size":
                 raise TypeError("AwsmSsao has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
             setattr(self, k, float(v))
+        return self
+
+
+class AwsmShadow(C.Structure):
+    """One shadowed light (awsm_hip_shadow_pass): map_size S, pcf_radius R, light = (unit vector towards the light, 0) or (position, 1), the depth
+    bias, the slope bias, the largest slope (NDC depth per texel), strength 0 .. 1, and the cosine from which a surface counts as facing the light."""
+    _fields_ = [("struct_size", C.c_uint32), ("map_size", C.c_uint32), ("pcf_radius", C.c_uint32), ("light", C.c_float * 4),
+                ("bias", C.c_float), ("slope_bias", C.c_float), ("max_slope", C.c_float), ("strength", C.c_float), ("facing_fade", C.c_float)]
+
+    def override(self, **overrides):
+        """Set fields by name; an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k == "struct_size":
+                raise TypeError("AwsmShadow has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
+            if k == "light":
+                self.light = (C.c_float * 4)(*[float(x) for x in v])
+            else:
+                setattr(self, k, int(v) if k in ("map_size", "pcf_radius") else float(v))
         return self
 
 
@@ -262,6 +282,10 @@ def load_library():
     lib.awsm_hip_ssao_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_set_ssao.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_ssao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_shadow_defaults.argtypes = [C.c_void_p]
+    lib.awsm_hip_shadow_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
+    lib.awsm_hip_read_shadow_map.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_shadow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -282,6 +306,7 @@ class HipDevice:
         self.owns = True
         self.width = self.height = 0
         self.lut_size = (0, 0)
+        self._shadow_size = None      # map_size of the last shadow_pass made through this object (read_shadow_map's default)
 
     @classmethod
     def from_ctx(cls, ctx: int, width: int, height: int) -> "HipDevice":
@@ -289,6 +314,7 @@ class HipDevice:
         self = cls.__new__(cls)
         self.lib, self.ctx, self.owns = load_library(), C.c_void_p(ctx), False
         self.width, self.height, self.lut_size = width, height, (0, 0)
+        self._shadow_size = None
         return self
 
     def _chk(self, rc: int, where: str):
@@ -587,6 +613,39 @@ class HipDevice:
         raw, smoothed, view_z = (np.empty((self.height, self.width), np.float32) for _ in range(3))
         self._chk(self.lib.awsm_hip_read_ssao(self.ctx, raw.ctypes.data, smoothed.ctypes.data, view_z.ctypes.data), "read_ssao")
         return raw, smoothed, view_z
+
+    def shadow_defaults(self) -> AwsmShadow:
+        s = AwsmShadow()
+        self._chk(self.lib.awsm_hip_shadow_defaults(C.byref(s)), "shadow_defaults")
+        return s
+
+    def shadow_pass(self, light_camera, casters, struct_size: Optional[int] = None, **overrides):
+        """The shadow map of this frame, between geometry_pass and opaque_pass: `casters` (draws) rasterised from `light_camera` (512 bytes in the
+        camera buffer's layout), with the defaults and `overrides` (map_size, pcf_radius, light, bias, slope_bias, max_slope, strength,
+        facing_fade).  The frame's opaque pass then multiplies the shadow in.  struct_size: what the record claims as its size (tests)."""
+        s = self.shadow_defaults().override(**overrides)
+        if struct_size is not None:
+            s.struct_size = struct_size
+        block = np.frombuffer(bytes(light_camera), dtype=np.uint8)
+        arr = self.make_draws(casters)
+        self._chk(self.lib.awsm_hip_shadow_pass(self.ctx, C.byref(s), block.ctypes.data if block.size else None, block.size, arr, len(casters)), "shadow_pass")
+        self._shadow_size = int(s.map_size)
+
+    def read_shadow_map(self, size: Optional[int] = None) -> np.ndarray:
+        """The last submitted frame's shadow map -> (S, S) uint64 keys (no hit = all ones).  size: the map's S; it may be left out when the pass was
+        made through this object's shadow_pass (a host's pass was not: give the size Host.set_shadow was given)."""
+        if size is None and self._shadow_size is None:
+            raise ValueError("read_shadow_map: no shadow_pass was made through this object; give the map's size")
+        S = int(size if size is not None else self._shadow_size)
+        keys = np.empty((S, S), np.uint64)
+        self._chk(self.lib.awsm_hip_read_shadow_map(self.ctx, keys.ctypes.data), "read_shadow_map")
+        return keys
+
+    def read_shadow(self):
+        """The last submitted frame's layers -> (V, m), float32 [H, W] each: the light's visibility and the multiplier the opaque image received."""
+        vis, mul = (np.empty((self.height, self.width), np.float32) for _ in range(2))
+        self._chk(self.lib.awsm_hip_read_shadow(self.ctx, vis.ctypes.data, mul.ctypes.data), "read_shadow")
+        return vis, mul
 
     def hud_geometry_pass(self, draws):
         """The hud meshes' visibility geometry, between geometry_pass and opaque_pass (render.rs:169-178)."""

@@ -74,6 +74,21 @@ class HostLight(C.Structure):
                 ("direction", C.c_float * 3), ("inner_angle", C.c_float), ("outer_angle", C.c_float)]
 
 
+class HostShadow(C.Structure):
+    """AwsmHostShadow (awsm_host_set_shadow): the light's key and hip_backend.AwsmShadow's parameters."""
+    _fields_ = [("struct_size", C.c_uint32), ("light", C.c_uint64), ("map_size", C.c_uint32), ("pcf_radius", C.c_uint32), ("bias", C.c_float),
+                ("slope_bias", C.c_float), ("max_slope", C.c_float), ("strength", C.c_float), ("facing_fade", C.c_float)]
+
+    def override(self, **overrides):
+        """Set fields by name; an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k in ("struct_size", "light"):
+                raise TypeError("AwsmHostShadow has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[2:])))
+            setattr(self, k, int(v) if k in ("map_size", "pcf_radius") else float(v))
+        return self
+
+
 class AnimationClip(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("n_keys", C.c_uint32), ("width", C.c_uint32),
                 ("times", C.POINTER(C.c_double)), ("values", F32P), ("in_tangents", F32P), ("out_tangents", F32P), ("duration", C.c_double)]
@@ -142,6 +157,8 @@ def load_library():
         "awsm_host_camera_set_dof": (C.c_int, [vp, C.c_float, C.c_float]),
         "awsm_host_editor_grid_defaults": (C.c_int, [vp, vp]), "awsm_host_set_editor_grid": (C.c_int, [vp, vp]),
         "awsm_host_ssao_defaults": (C.c_int, [vp, vp]), "awsm_host_set_ssao": (C.c_int, [vp, vp]),
+        "awsm_host_shadow_defaults": (C.c_int, [vp, vp]), "awsm_host_set_shadow": (C.c_int, [vp, vp]),
+        "awsm_host_shadow_camera": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
         "awsm_host_texture_insert_kind": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_update_transforms": (C.c_int, [vp]),
         "awsm_host_render": (C.c_int, [vp, C.c_int, vp]), "awsm_host_mirror": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
@@ -616,6 +633,30 @@ class Host:
         s.override(**overrides)
         self._chk(self.lib.awsm_host_set_ssao(self.h, C.byref(s)), "set_ssao")
 
+    def set_shadow(self, light: Optional[int] = None, struct_size: Optional[int] = None, **overrides):
+        """Shadows from one directional or spot light in every later render(): `light` is a key light_insert returned; the backend's defaults with
+        `overrides` (map_size, pcf_radius, bias, slope_bias, max_slope, strength, facing_fade).  light=None turns them off."""
+        if light is None:
+            return self._chk(self.lib.awsm_host_set_shadow(self.h, None), "set_shadow")
+        s = HostShadow()
+        self._chk(self.lib.awsm_host_shadow_defaults(self.h, C.byref(s)), "shadow_defaults")
+        s.override(**overrides)
+        s.light = light
+        if struct_size is not None:
+            s.struct_size = struct_size
+        self._chk(self.lib.awsm_host_set_shadow(self.h, C.byref(s)), "set_shadow")
+
+    def shadow_camera(self, cap: int = 65536):
+        """What the last render() handed the backend's shadow pass -> (the 512-byte light block, the caster draws as dicts)."""
+        block = (C.c_uint8 * 512)()
+        draws = (hip_backend.AwsmDraw * max(1, cap))()
+        n = C.c_uint32(0)
+        self._chk(self.lib.awsm_host_shadow_camera(self.h, block, draws, cap, C.byref(n)), "shadow_camera")
+        if n.value > cap:
+            return self.shadow_camera(n.value)
+        fields = [f for f, _ in hip_backend.AwsmDraw._fields_]
+        return bytes(block), [{f: int(getattr(draws[i], f)) for f in fields} for i in range(n.value)]
+
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         """CameraMatrices.focus_distance / .aperture (camera bytes 496-503; the reference's defaults 10.0 and 5.6)."""
         self._chk(self.lib.awsm_host_camera_set_dof(self.h, focus_distance, aperture), "camera_set_dof")
@@ -1007,6 +1048,20 @@ class Renderer:
 
     def set_ssao(self, on: bool = True, **overrides):
         self.host.set_ssao(on, **overrides)
+
+    def set_shadow(self, light=True, **overrides):
+        """Shadows from one of the scene's lights: an index into scene.lights, True for the first directional light (the first spot light if
+        there is none), False / None for off."""
+        if light is None or light is False:
+            return self.host.set_shadow(None)
+        if light is True:
+            kinds = [l.get("kind", "directional") for l in self.scene.lights]
+            light = kinds.index("directional") if "directional" in kinds else (kinds.index("spot") if "spot" in kinds else None)
+            if light is None:
+                raise HostError("set_shadow: the scene has no directional or spot light")
+        if self.keys is None:
+            raise HostError("set_shadow: a scene populated from a glTF file keeps no light keys here; use Host.set_shadow with a key of light_insert")
+        self.host.set_shadow(self.keys.light_keys[light], **overrides)
 
     def camera_set_dof(self, focus_distance: float = 10.0, aperture: float = 5.6):
         self.host.camera_set_dof(focus_distance, aperture)

@@ -72,6 +72,8 @@ struct Backend {
     int (*set_editor_grid)(AwsmHipCtx*, const AwsmEditorGrid*) = nullptr;
     int (*ssao_defaults)(AwsmSsao*) = nullptr;                          // optional: screen-space ambient occlusion (awsm_host_set_ssao)
     int (*set_ssao)(AwsmHipCtx*, const AwsmSsao*) = nullptr;
+    int (*shadow_defaults)(AwsmShadow*) = nullptr;                      // optional: shadows (awsm_host_set_shadow)
+    int (*shadow_pass)(AwsmHipCtx*, const AwsmShadow*, const void*, size_t, const AwsmDraw*, uint32_t) = nullptr;
     // optional: environment cubes at run time (awsm_host_env_cube_*)
     int (*env_cube_create)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t) = nullptr;
     int (*env_cube_write_face)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
@@ -252,6 +254,11 @@ struct AwsmHost {
     AwsmPostParams post{};
     bool grid_on = false;                      // awsm_host_set_editor_grid: the world transparent pass runs every frame, with no draws if need be
     bool sharded = false;                      // awsm_host_set_shard_rows / _bands gave this host a part of the frame (the post pass needs all of it)
+    // ---- shadows (awsm_host_set_shadow): the record, and what the last render handed the backend (awsm_host_shadow_camera) ----
+    bool shadow_on = false, shadow_rendered = false;
+    AwsmHostShadow shadow{};
+    uint8_t shadow_block[512] = {};
+    std::vector<AwsmDraw> shadow_casters;
     Mat4 cam_view = mat4_identity(), cam_proj = mat4_identity();
     uint32_t frame_count = 0;
     uint32_t width = 0, height = 0;
@@ -470,7 +477,8 @@ bool is_transparency_pass(const AwsmHostMaterial& m) {   // pbr.rs:213-224, unli
 }
 
 void collect_draws(AwsmHost* h, std::vector<AwsmDraw>& out_opaque, std::vector<AwsmDraw>* transparent_out = nullptr,
-                   std::vector<AwsmDraw>* hud_geometry_out = nullptr, std::vector<AwsmDraw>* hud_transparent_out = nullptr) {   // renderable.rs:38-150
+                   std::vector<AwsmDraw>* hud_geometry_out = nullptr, std::vector<AwsmDraw>* hud_transparent_out = nullptr,
+                   const Mat4* cull_view_proj = nullptr) {   // renderable.rs:38-150.  cull_view_proj: the frustum that culls instead of the camera's (the shadow casters: the light's); the order stays the camera's
     out_opaque.clear();
     if (transparent_out) transparent_out->clear();
     if (hud_geometry_out) hud_geometry_out->clear();
@@ -479,7 +487,8 @@ void collect_draws(AwsmHost* h, std::vector<AwsmDraw>& out_opaque, std::vector<A
     std::vector<Item> items;
     const Mat4 view_proj = mat4_mul(h->cam_proj, h->cam_view);
     std::unique_ptr<Frustum> fr;
-    if (h->have_camera) fr.reset(new Frustum(view_proj));
+    if (cull_view_proj) fr.reset(new Frustum(*cull_view_proj));
+    else if (h->have_camera) fr.reset(new Frustum(view_proj));
     const auto& keys = h->meshes.keys();
     const auto& vals = h->meshes.values();
     for (size_t i = 0; i < keys.size(); i++) {
@@ -693,6 +702,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.set_editor_grid = reinterpret_cast<decltype(b.set_editor_grid)>(dlsym(b.dl, "awsm_hip_set_editor_grid"));
     b.ssao_defaults = reinterpret_cast<decltype(b.ssao_defaults)>(dlsym(b.dl, "awsm_hip_ssao_defaults"));      // optional (awsm_host_set_ssao)
     b.set_ssao = reinterpret_cast<decltype(b.set_ssao)>(dlsym(b.dl, "awsm_hip_set_ssao"));
+    b.shadow_defaults = reinterpret_cast<decltype(b.shadow_defaults)>(dlsym(b.dl, "awsm_hip_shadow_defaults"));      // optional (awsm_host_set_shadow)
+    b.shadow_pass = reinterpret_cast<decltype(b.shadow_pass)>(dlsym(b.dl, "awsm_hip_shadow_pass"));
     b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
     b.env_cube_write_face = reinterpret_cast<decltype(b.env_cube_write_face)>(dlsym(b.dl, "awsm_hip_env_cube_write_face"));
     b.env_cube_write_all_faces = reinterpret_cast<decltype(b.env_cube_write_all_faces)>(dlsym(b.dl, "awsm_hip_env_cube_write_all_faces"));
@@ -1193,14 +1204,12 @@ int awsm_host_set_ibl_mip_counts(AwsmHost* h, uint32_t prefiltered, uint32_t irr
     return AWSM_OK;
 }
 
-int awsm_host_camera_update(AwsmHost* h, const float view[16], const float projection[16], const float pos[3]) {   // camera.rs:111-227
-    Mat4 v, p;
-    memcpy(&v, view, 64); memcpy(&p, projection, 64);
+// The 512-byte camera block (camera.rs:111-227) from an f32 view and projection: the scene camera's, and the shadow pass's camera at the light
+static void pack_camera_block(const AwsmHost* h, const Mat4& v, const Mat4& p, const float pos[3], float width, float height, uint8_t* o) {
     const Mat4 inv_proj = mat4_inverse(p);
     const Mat4 view_proj = mat4_mul(p, v);
     const Mat4 inv_view_proj = mat4_inverse(view_proj);
     const Mat4 inv_view = mat4_inverse(v);
-    uint8_t* o = h->camera_raw;
     memcpy(o, &v, 64); memcpy(o + 64, &p, 64); memcpy(o + 128, &view_proj, 64);
     memcpy(o + 192, &inv_view_proj, 64); memcpy(o + 256, &inv_proj, 64); memcpy(o + 320, &inv_view, 64);
     const float posw[4] = {pos[0], pos[1], pos[2], 0.0f};
@@ -1215,10 +1224,16 @@ int awsm_host_camera_update(AwsmHost* h, const float view[16], const float proje
         const float ray[4] = {d.x, d.y, d.z, 0.0f};
         memcpy(o + 416 + i * 16, ray, 16);
     }
-    const float viewport[4] = {0.0f, 0.0f, (float)h->width, (float)h->height};
+    const float viewport[4] = {0.0f, 0.0f, width, height};
     memcpy(o + 480, viewport, 16);
     const float dof[4] = {h->dof_params[0], h->dof_params[1], 0.0f, 0.0f};
     memcpy(o + 496, dof, 16);
+}
+
+int awsm_host_camera_update(AwsmHost* h, const float view[16], const float projection[16], const float pos[3]) {
+    Mat4 v, p;
+    memcpy(&v, view, 64); memcpy(&p, projection, 64);
+    pack_camera_block(h, v, p, pos, (float)h->width, (float)h->height, h->camera_raw);
     h->cam_view = v; h->cam_proj = p; h->have_camera = true; h->camera_dirty = true;
     return AWSM_OK;
 }
@@ -1581,8 +1596,14 @@ int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes
     return AWSM_OK;
 }
 
+static int render_shadow_pass(AwsmHost* h);
 int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render.rs:53-383 (hot path only)
     if (!h->width) return fail(h, AWSM_ERR_NOT_READY, "render before resize");
+    h->shadow_rendered = false;
+    if (h->shadow_on && !h->lights.get(h->shadow.light)) {      // the shadowed light was removed: the feature goes off, said once
+        h->shadow_on = false;
+        return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the light awsm_host_set_shadow named was removed; shadows are off from here on");
+    }
     h->upload_bytes = 0;
     h->frame_count += 1;   // render_textures.next_frame()
     int rc;
@@ -1661,6 +1682,7 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     collect_draws(h, h->last_draws, &h->last_transparent_draws, &h->last_hud_geometry_draws, &h->last_hud_transparent_draws);
     if ((rc = h->be.geometry_pass(h->ctx, h->last_draws.data(), (uint32_t)h->last_draws.size()))) return dev_fail(h, rc, "geometry_pass");
     if (h->has_hud_meshes && (rc = h->be.hud_geometry_pass(h->ctx, h->last_hud_geometry_draws.data(), (uint32_t)h->last_hud_geometry_draws.size()))) return dev_fail(h, rc, "hud_geometry_pass");   // render.rs:169-178
+    if (h->shadow_on && (rc = render_shadow_pass(h))) return rc;      // the shadow map of this frame, from the light
     if (h->after_geometry && (rc = h->after_geometry(h->after_geometry_user))) { h->last_error = "after_geometry_pass hook failed"; return rc; }   // hooks.after_geometry_pass (render.rs:181-190)
     AwsmOpaqueParams op{};
     op.mipmap = h->mipmap ? 1u : 0u; op.has_opaque = h->last_draws.empty() ? 0u : 1u;   // material_opaque/render_pass.rs:64-71
@@ -1718,6 +1740,122 @@ int awsm_host_set_ssao(AwsmHost* h, const AwsmSsao* ssao) {
     if (!h->be.set_ssao) return fail(h, AWSM_ERR_UNSUPPORTED, "set_ssao: the backend library has no %s", "awsm_hip_set_ssao");
     const int rc = h->be.set_ssao(h->ctx, ssao);
     return rc ? dev_fail(h, rc, "set_ssao") : AWSM_OK;
+}
+
+// Shadows: the host fits a camera to the light and chooses the casters; the backend rasterises them and resolves.
+int awsm_host_shadow_defaults(AwsmHost* h, AwsmHostShadow* out) {
+    if (!h || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.shadow_defaults) return fail(h, AWSM_ERR_UNSUPPORTED, "shadow_defaults: the backend library has no %s", "awsm_hip_shadow_defaults");
+    AwsmShadow d{};
+    const int rc = h->be.shadow_defaults(&d);
+    if (rc) return dev_fail(h, rc, "shadow_defaults");
+    *out = AwsmHostShadow{(uint32_t)sizeof(AwsmHostShadow), 0, d.map_size, d.pcf_radius, d.bias, d.slope_bias, d.max_slope, d.strength, d.facing_fade};
+    return AWSM_OK;
+}
+int awsm_host_set_shadow(AwsmHost* h, const AwsmHostShadow* s) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.shadow_pass) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow: the backend library has no %s", "awsm_hip_shadow_pass");
+    if (!h->be.shadow_defaults) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow: the backend library has no %s", "awsm_hip_shadow_defaults");
+    if (!s) { h->shadow_on = false; return AWSM_OK; }
+    if (s->struct_size != sizeof(AwsmHostShadow)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow: AwsmHostShadow.struct_size = %u (set it to sizeof(AwsmHostShadow))", s->struct_size);
+    const AwsmHostLight* l = h->lights.get(s->light);
+    if (!l) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow: [light] not found");
+    if (l->kind == 2u) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow: a point light needs a cube map of depths; directional and spot lights only");
+    h->shadow = *s;
+    h->shadow_on = true;
+    return AWSM_OK;
+}
+int awsm_host_shadow_camera(AwsmHost* h, void* block512, AwsmDraw* casters_out, uint32_t cap, uint32_t* n_out) {
+    if (!h || (!casters_out && cap)) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->shadow_rendered) return fail(h, AWSM_ERR_NOT_READY, "shadow_camera: the last render had no shadow pass");
+    if (block512) memcpy(block512, h->shadow_block, 512);
+    const uint32_t n = (uint32_t)h->shadow_casters.size();
+    if (n_out) *n_out = n;
+    if (casters_out) memcpy(casters_out, h->shadow_casters.data(), (size_t)std::min(n, cap) * sizeof(AwsmDraw));
+    return AWSM_OK;
+}
+
+// The camera at the light (include/awsm_host.h has the rules), composed in f64 and rounded once to the f32 view and projection the packer takes.
+static void shadow_light_camera(AwsmHost* h, const AwsmHostLight& l, uint32_t S, uint8_t block[512], float light_out[4]) {
+    double f[3] = {l.direction[0], l.direction[1], l.direction[2]};
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    if (fl > 0.0) { f[0] /= fl; f[1] /= fl; f[2] /= fl; } else { f[0] = 0.0; f[1] = -1.0; f[2] = 0.0; }
+    // the union of the candidates' world boxes
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool any = false;
+    for (const MeshRec& m : h->meshes.values()) {
+        if (m.hidden || m.hud || m.transparent || !m.has_world_aabb) continue;
+        const double a[3] = {m.world_aabb.min.x, m.world_aabb.min.y, m.world_aabb.min.z}, b[3] = {m.world_aabb.max.x, m.world_aabb.max.y, m.world_aabb.max.z};
+        for (int i = 0; i < 3; i++) { lo[i] = any ? std::min(lo[i], a[i]) : a[i]; hi[i] = any ? std::max(hi[i], b[i]) : b[i]; }
+        any = true;
+    }
+    double eye[3], proj[16] = {};
+    if (l.kind == 1u) {
+        double c[3] = {0, 0, 0}, r = 1.0;
+        if (any) {
+            double dd = 0.0;
+            for (int i = 0; i < 3; i++) { c[i] = 0.5 * (lo[i] + hi[i]); dd += (hi[i] - lo[i]) * (hi[i] - lo[i]); }
+            r = 0.5 * std::sqrt(dd);
+            if (!(r > 0.0)) r = 1.0;
+        }
+        for (int i = 0; i < 3; i++) eye[i] = c[i] - 2.0 * r * f[i];
+        const double n = r, fa = 3.0 * r;      // Mat4::orthographic_rh(-r, r, -r, r, near, far), depth 0 .. 1
+        proj[0] = 1.0 / r; proj[5] = 1.0 / r; proj[10] = 1.0 / (n - fa); proj[14] = n / (n - fa); proj[15] = 1.0;
+        for (int i = 0; i < 3; i++) light_out[i] = (float)-f[i];
+        light_out[3] = 0.0f;
+    } else {
+        for (int i = 0; i < 3; i++) eye[i] = l.position[i];
+        double fa = l.range;
+        if (!(fa > 0.0)) {
+            fa = 0.0;
+            if (any) for (int k = 0; k < 8; k++) {
+                double dd = 0.0;
+                for (int i = 0; i < 3; i++) { const double p = ((k >> i) & 1) ? hi[i] : lo[i]; dd += (p - eye[i]) * (p - eye[i]); }
+                fa = std::max(fa, std::sqrt(dd));
+            }
+            fa = std::max(fa, 1.0);
+        }
+        const double n = std::max(0.05, fa * 1e-3), kPi = 3.14159265358979323846;
+        // AwsmHostLight.outer_angle holds the COSINE of the outer cone's half angle (the glTF reader stores cos(outerConeAngle); the spot falloff compares it with cos)
+        const double cone = std::acos(std::min(std::max((double)l.outer_angle, -1.0), 1.0));
+        const double fovy = std::min(std::max(2.0 * cone, kPi / 180.0), 170.0 * kPi / 180.0);
+        const double t = 1.0 / std::tan(0.5 * fovy);      // Mat4::perspective_rh(fovy, 1, near, far), depth 0 .. 1
+        proj[0] = t; proj[5] = t; proj[10] = fa / (n - fa); proj[11] = -1.0; proj[14] = n * fa / (n - fa);
+        for (int i = 0; i < 3; i++) light_out[i] = l.position[i];
+        light_out[3] = 1.0f;
+    }
+    // Mat4::look_to_rh(eye, f, up)
+    const double up[3] = {0.0, std::fabs(f[1]) > 0.999 ? 0.0 : 1.0, std::fabs(f[1]) > 0.999 ? 1.0 : 0.0};
+    double s[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const double sl = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    for (int i = 0; i < 3; i++) s[i] /= sl;
+    const double u[3] = {s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0]};
+    const double view[16] = {s[0], u[0], -f[0], 0.0,   s[1], u[1], -f[1], 0.0,   s[2], u[2], -f[2], 0.0,
+                             -(s[0] * eye[0] + s[1] * eye[1] + s[2] * eye[2]), -(u[0] * eye[0] + u[1] * eye[1] + u[2] * eye[2]), f[0] * eye[0] + f[1] * eye[1] + f[2] * eye[2], 1.0};
+    float vf[16], pf[16];
+    for (int i = 0; i < 16; i++) { vf[i] = (float)view[i]; pf[i] = (float)proj[i]; }
+    Mat4 v, p;
+    memcpy(&v, vf, 64); memcpy(&p, pf, 64);
+    const float pos[3] = {(float)eye[0], (float)eye[1], (float)eye[2]};
+    pack_camera_block(h, v, p, pos, (float)S, (float)S, block);
+}
+
+// called by awsm_host_render between the geometry passes and the opaque pass
+static int render_shadow_pass(AwsmHost* h) {
+    const AwsmHostLight* l = h->lights.get(h->shadow.light);
+    if (!l || l->kind == 2u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the shadowed light is gone");      // (checked at the top of the render too)
+    AwsmShadow s{};
+    s.struct_size = (uint32_t)sizeof s;
+    s.map_size = h->shadow.map_size; s.pcf_radius = h->shadow.pcf_radius;
+    s.bias = h->shadow.bias; s.slope_bias = h->shadow.slope_bias; s.max_slope = h->shadow.max_slope; s.strength = h->shadow.strength; s.facing_fade = h->shadow.facing_fade;
+    shadow_light_camera(h, *l, std::max(1u, s.map_size), h->shadow_block, s.light);
+    Mat4 lvp;
+    memcpy(&lvp, h->shadow_block + 128, 64);
+    collect_draws(h, h->shadow_casters, nullptr, nullptr, nullptr, &lvp);
+    const int rc = h->be.shadow_pass(h->ctx, &s, h->shadow_block, 512, h->shadow_casters.data(), (uint32_t)h->shadow_casters.size());
+    if (rc) return dev_fail(h, rc, "shadow_pass");
+    h->shadow_rendered = true;
+    return AWSM_OK;
 }
 
 // back to no post pass (this library's default; the reference always runs the effects and display passes)

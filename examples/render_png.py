@@ -11,6 +11,8 @@ device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefilte
 by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
 --hdr FILE projects an equirectangular Radiance .hdr panorama into the skybox (--hdr-size N, default 512; --hdr-yaw R radians turns it about the
 vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl the scene is lit from the file.
+--shadow [LIGHT] casts shadows from one directional or spot light of the scene (--shadow-size N, --shadow-strength X): a depth map from the light,
+looked up per pixel and multiplied into the opaque image.
 --ssao darkens creases and contact lines: ambient occlusion estimated from the geometry pass's depth (--ssao-radius R in world units, --ssao-intensity I).
 --grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
 """
@@ -50,6 +52,11 @@ def main():
     ap.add_argument("--ssao", action="store_true", help="screen-space ambient occlusion from the visibility depth, multiplied into the opaque image")
     ap.add_argument("--ssao-radius", type=float, default=None, metavar="R", help="with --ssao: the sampling radius in world units (default 0.5)")
     ap.add_argument("--ssao-intensity", type=float, default=None, metavar="I", help="with --ssao: the estimator's scale (default 1.0)")
+    ap.add_argument("--shadow", nargs="?", const=-1, type=int, default=None, metavar="LIGHT",
+                    help="shadows from one directional or spot light: an index into the scene's lights (default: the first directional light); not with --via-glb, "
+                         "whose lights are the file's and have no index here")
+    ap.add_argument("--shadow-size", type=int, default=None, metavar="N", help="with --shadow: the shadow map is N x N (default 2048)")
+    ap.add_argument("--shadow-strength", type=float, default=None, metavar="X", help="with --shadow: how dark a shadow is, 0 .. 1 (default 0.7)")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -91,6 +98,10 @@ def main():
         r.set_editor_grid(True)
     if a.ssao:
         r.set_ssao(True, **{k: v for k, v in (("radius", a.ssao_radius), ("intensity", a.ssao_intensity)) if v is not None})
+    if a.shadow is not None:
+        if a.via_glb:
+            ap.error("--shadow names a light by its index in the scene description; a scene read from a .glb keeps no such index (Host.set_shadow takes a light's key)")
+        r.set_shadow(True if a.shadow < 0 else a.shadow, **{k: v for k, v in (("map_size", a.shadow_size), ("strength", a.shadow_strength)) if v is not None})
     stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
     if post:

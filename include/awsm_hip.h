@@ -628,6 +628,38 @@ int awsm_hip_ssao_defaults(AwsmSsao* out);
 int awsm_hip_set_ssao(AwsmHipCtx* ctx, const AwsmSsao* ssao /* NULL = off */);
 int awsm_hip_read_ssao(AwsmHipCtx* ctx, float* ao_raw_out, float* ao_smoothed_out, float* view_z_out);
 
+/* ---- shadows from one directional or spot light ("Shadows" of the reference's "Next up" list).
+ *   shadow_pass      between awsm_hip_geometry_pass and awsm_hip_opaque_pass (before or after awsm_hip_hud_geometry_pass): `casters` are rasterised
+ *                    single-sampled, by the world geometry pass's kernels under its depth contract, from `light_camera` — a 512-byte block in
+ *                    the layout of AWSM_BUF_CAMERA (view 0, proj 64, view_proj 128, ...), as the caller would write it for a camera at the light —
+ *                    into the frame slot's map_size x map_size key buffer.  n = 0 is legal: an empty map, everything is lit.
+ *                    The frame's opaque pass (has_opaque set) then runs k_shadow_resolve behind its shading kernels and in front of SSAO's: per
+ *                    pixel the world position from the WORLD keys' depth (the least of the four samples with MSAA) and the camera snapshot's
+ *                    inv_view_proj, the light's texel, a receiver-plane depth bias from the neighbours, (2 pcf_radius + 1)^2 taps -> the
+ *                    visibility V; rgb *= 1 - strength g (1 - V) on the opaque image and its f32 tap, g the facing term (0 where the surface is
+ *                    turned away from the light, 1 from cos >= facing_fade on).  The whole opaque colour is multiplied, not the light's direct
+ *                    term inside the light loop ("modulative" shadows); V is kept for a consumer that does.
+ *                    Parameters travel with the pass: no shadow pass in a frame, no shadow in that frame.
+ *                    AWSM_ERR_UNSUPPORTED on a sharded context; AWSM_ERR_NOT_READY outside that window; AWSM_ERR_INVALID_ARGUMENT (state unchanged)
+ *                    for a non-finite value, map_size outside [1, 8192], pcf_radius > 2, strength outside [0, 1], facing_fade <= 0,
+ *                    max_slope < 0, light[3] other than 0 or 1, camera_bytes != 512.
+ *   read_shadow_map  the map_size^2 keys of the last submitted frame's pass (no hit = all ones).  AWSM_ERR_NOT_READY unless that frame had one.
+ *   read_shadow      V and the multiplier m, width x height f32 each (either may be NULL).  AWSM_ERR_NOT_READY unless that frame had the pass
+ *                    and an opaque pass with has_opaque behind it.
+ *   defaults         map_size 2048, pcf_radius 1, light (0, 1, 0, 0), bias 1e-3, slope_bias 1, max_slope 0.05 (NDC depth per texel),
+ *                    strength 0.7, facing_fade 0.1. ---- */
+typedef struct AwsmShadow {
+    uint32_t struct_size;
+    uint32_t map_size;      /* S: the map is S x S keys, 1 <= S <= 8192 */
+    uint32_t pcf_radius;    /* R in {0, 1, 2}: (2R+1)^2 taps */
+    float    light[4];      /* w == 0: xyz = unit vector TOWARDS the light (directional); w == 1: xyz = the light's position (spot) */
+    float    bias, slope_bias, max_slope, strength, facing_fade;
+} AwsmShadow;
+int awsm_hip_shadow_defaults(AwsmShadow* out);
+int awsm_hip_shadow_pass(AwsmHipCtx* ctx, const AwsmShadow* shadow, const void* light_camera, size_t camera_bytes, const AwsmDraw* casters, uint32_t n);
+int awsm_hip_read_shadow_map(AwsmHipCtx* ctx, uint64_t* keys_out /* map_size^2 */);
+int awsm_hip_read_shadow(AwsmHipCtx* ctx, float* visibility_out, float* multiplier_out /* width x height each */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,33 @@ int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid /* NULL = 
  * so does its AWSM_ERR_UNSUPPORTED from the render of a sharded host. */
 int awsm_host_ssao_defaults(AwsmHost* h, AwsmSsao* out);
 int awsm_host_set_ssao(AwsmHost* h, const AwsmSsao* ssao /* NULL = off */);
+
+/* Shadows from one directional or spot light (awsm_hip_shadow_pass in awsm_hip.h has the device's rules).  While it is on,
+ * awsm_host_render calls the backend's shadow pass after the geometry pass, every frame, with a camera it fits to the light and the casters it
+ * chooses:
+ *   light camera  composed in f64, packed as the scene camera's block is.  Forward f = the light's direction; up = +Y, or +Z when |f.y| > 0.999.
+ *                 Directional: c, r = centre and half diagonal of the union of the world AABBs of the candidates (opaque, non-HUD, not hidden
+ *                 meshes; none: c = 0, r = 1); eye = c - 2 r f; orthographic, half extent r both ways, near r, far 3 r.
+ *                 Spot: eye = the position; perspective, aspect 1, fovy = clamp(2 acos(outer_angle), 1 deg, 170 deg) — outer_angle holds the cosine of the cone's half angle, as the shading reads it; far = range if range > 0, else
+ *                 the distance to the farthest corner of that union (at least 1); near = max(0.05, far / 1000).
+ *   casters       the candidates whose world AABB meets that camera's frustum, in the order the world list would hold them.  Transparent and
+ *                 HUD meshes neither cast nor are looked up.
+ * set_shadow(NULL) turns it off.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library lacks awsm_hip_shadow_pass /
+ * awsm_hip_shadow_defaults, and for a point light; AWSM_ERR_INVALID_ARGUMENT for a key that names no light.  A light removed later turns the
+ * feature off with AWSM_ERR_INVALID_ARGUMENT at the next awsm_host_render.  The record's other fields reach the backend unchanged, and its
+ * refusals (and AWSM_ERR_UNSUPPORTED on a sharded host) come back from awsm_host_render.
+ * shadow_camera: what the last awsm_host_render used — the 512-byte block, and up to `cap` caster draws (n_out: how many there were).
+ * AWSM_ERR_NOT_READY when that render had no shadow pass. */
+typedef struct AwsmHostShadow {
+    uint32_t struct_size;
+    AwsmKey light;            /* at byte 8 */
+    uint32_t map_size;
+    uint32_t pcf_radius;
+    float bias, slope_bias, max_slope, strength, facing_fade;
+} AwsmHostShadow;
+int awsm_host_shadow_defaults(AwsmHost* h, AwsmHostShadow* out);      /* the backend's defaults; light = 0 */
+int awsm_host_set_shadow(AwsmHost* h, const AwsmHostShadow* shadow /* NULL = off */);
+int awsm_host_shadow_camera(AwsmHost* h, void* block512, AwsmDraw* casters_out, uint32_t cap, uint32_t* n_out);
 /* CameraMatrices.focus_distance / .aperture (camera.rs:40-52; the reference's defaults are 10.0 and 5.6): camera bytes 496-503, uploaded with
  * the next frame.  Until this is called the host writes 0 and 0. */
 int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture);
