@@ -610,6 +610,28 @@ void fill_frame_forward(AwsmHipCtx* c, FrameDev* f) {
     }
 }
 
+// The selection kernels' arguments for the current slot's frame with the record `st`: the WORLD geometry pass's keys and draw list (in a frame whose
+// hud draws share the world's rank space the world's draws come first), the camera snapshot, the slot's tables.
+void fill_selection(AwsmHipCtx* c, const AwsmHipCtx::SelectionState& st, SelectionDev* a) {
+    memset(a, 0, sizeof *a);
+    a->width = c->width; a->height = c->height; a->msaa = c->msaa == 4 ? 4u : 1u;
+    a->n_draws = (uint32_t)c->draws_host.size(); a->total_tris = c->total_tris;
+    a->n_keys = (uint32_t)(st.keys.size() / 2); a->n_boxes = (uint32_t)(st.boxes.size() / 6);
+    a->flags = st.flags; a->radius = st.radius;
+    memcpy(a->outline_color, st.outline_color, sizeof a->outline_color); memcpy(a->box_color, st.box_color, sizeof a->box_color);
+    a->half_width = st.half_width; a->hidden_alpha = st.hidden_alpha; a->depth_epsilon = st.depth_epsilon;
+    a->scene = c->scene_dev;
+    a->material_meta_bytes = (uint32_t)std::min<size_t>(c->bufs[AWSM_BUF_MATERIAL_META].size, 0xFFFFFFFFu);
+    a->draws = (const DrawDev*)FB(c).draws_dev.ptr;
+    a->tri_info = (const uint32_t*)FB(c).tri_flags.ptr;
+    a->vis = (const unsigned long long*)FB(c).vis.ptr;
+    a->camera = (const uint8_t*)FB(c).camera.ptr;
+    a->edges = (float*)c->sel_tables[c->slot].ptr;                                                     // (32-byte records first: aligned)
+    a->draw_selected = (uint8_t*)c->sel_tables[c->slot].ptr + (size_t)selection::kMaxEdges * selection::kEdgeFloats * 4;
+    if (a->n_keys) memcpy(a->keys, st.keys.data(), st.keys.size() * 4);
+    if (a->n_boxes) memcpy(a->boxes, st.boxes.data(), st.boxes.size() * 4);
+}
+
 int enqueue_transparent(AwsmHipCtx* c) {
     FrameDev f;
     fill_frame_forward(c, &f);
@@ -639,6 +661,18 @@ int enqueue_transparent(AwsmHipCtx* c) {
         const bool with_grid = gs.on && !c->hud_transparent;
         if (with_grid) { grid.camera = f.camera; memcpy(grid.p, gs.p, sizeof grid.p); }
         awsm_launch_forward(c->scene_dev, &f, with_grid ? &grid : nullptr, ss);
+        // the editor's selection overlay, with the record this pass was submitted with: the world pass only, behind the kernels that leave the
+        // composite — the grid, the transparent meshes, the MSAA resolve — and in front of the shade-done signal below: it reads the slot's keys,
+        // which the slot's next geometry pass overwrites (the ordering argument of the occlusion kernels in enqueue_opaque).  A replay
+        // (awsm_hip_frame_end) comes through here again behind a blit that wrote every pixel anew, so the overlay is blended once.
+        const AwsmHipCtx::SelectionState& sl = c->sel_pass[c->slot];
+        if (sl.on && !c->hud_transparent) {
+            SelectionDev sd;
+            fill_selection(c, sl, &sd);
+            sd.out16 = (uint2*)f.out_rgba16f; sd.out32 = (float4*)f.out_rgba32f;
+            sd.poison = f.poison; sd.frame_serial = f.frame_serial;
+            awsm_launch_selection(&sd, ss);
+        }
     }
     if ((rc = record(c, EV_FWD, ss))) return rc;
     if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));
@@ -958,6 +992,8 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); fr(c->grid_layer); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->ssao_layers) fr(b);
+    for (auto& b : c->sel_tables) fr(b);
+    fr(c->sel_layers);
     for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < 5 * kSlots; k++) {
@@ -1553,6 +1589,10 @@ static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t 
     const bool sharded = c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height));
     if (sharded && !c->opaque_src)
         return fail(c, AWSM_ERR_UNSUPPORTED, "transparent_pass on a sharded context: screen-space transmission reads the whole opaque image — gather it and bind it with awsm_hip_bind_opaque_source first");
+    if (!hud && c->sel.on && sharded)
+        return fail(c, AWSM_ERR_UNSUPPORTED, "transparent_pass with a selection on a sharded context: the outline's ring reads keys in rows the shard never rasterised (no halo exchange)");
+    if (!hud && c->sel.on && !c->draws_host.empty() && (!c->bufs[AWSM_BUF_GEOM_META].ptr || !c->bufs[AWSM_BUF_MATERIAL_META].ptr))
+        return fail(c, AWSM_ERR_NOT_READY, "transparent_pass with a selection: the geometry or material meta buffer is missing");
     if (c->opaque_src && c->opaque_src_bytes < (size_t)c->width * c->height * 8)
         return fail(c, AWSM_ERR_INVALID_ARGUMENT, "transparent_pass: the bound opaque source holds %zu bytes, the frame needs %zu", c->opaque_src_bytes, (size_t)c->width * c->height * 8);
     static const AwsmBuf need[] = {AWSM_BUF_TRANSFORMS, AWSM_BUF_CAMERA, AWSM_BUF_GEOM_META, AWSM_BUF_MATERIAL_META, AWSM_BUF_MATERIALS, AWSM_BUF_ATTR_INDEX,
@@ -1579,6 +1619,10 @@ static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t 
         HIPCHK(c, hipStreamWaitEvent(shade_stream_of(c), c->ev_geom_done[c->slot], 0));
     }
     if (!hud) c->grid_pass[c->slot] = c->grid;
+    if (!hud) {      // the selection overlay: this pass carries the record as it stands now, into a replay too
+        if (c->sel.on && (rc = dev_reserve(c, c->sel_tables[c->slot], (size_t)selection::kMaxEdges * selection::kEdgeFloats * 4 + std::max<size_t>(c->draws_host.size(), 1)))) return rc;
+        c->sel_pass[c->slot] = c->sel;
+    }
     if ((rc = enqueue_transparent(c))) return rc;
     if (hud) c->hud_transparent_done = true; else { c->transparent_done = true; c->hud_transparent_done = false; }
     return AWSM_OK;
@@ -2000,6 +2044,78 @@ int awsm_hip_read_ssao(AwsmHipCtx* c, float* ao_raw, float* ao_smoothed, float* 
     if (ao_raw) HIPCHK(c, hipMemcpy(ao_raw, d, px * 4, hipMemcpyDeviceToHost));
     if (ao_smoothed) HIPCHK(c, hipMemcpy(ao_smoothed, d + px, px * 4, hipMemcpyDeviceToHost));
     if (view_z) HIPCHK(c, hipMemcpy(view_z, d + 2 * px, px * 4, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+// ---- the editor's selection overlay (kernels_selection.hip) ----
+int awsm_hip_selection_defaults(AwsmSelection* out) {
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    static const AwsmSelection d = {(uint32_t)sizeof(AwsmSelection), AWSM_SELECTION_OUTLINE | AWSM_SELECTION_BOXES, 2u, {1.0f, 0.6f, 0.1f, 1.0f}, {1.0f, 0.6f, 0.1f, 0.9f},
+                                    0.75f, 0.25f, 1e-5f};
+    *out = d;
+    return AWSM_OK;
+}
+static_assert(sizeof(AwsmSelection) == 56 && sizeof(AwsmSelectionBox) == 24, "AwsmSelection / AwsmSelectionBox layout");
+static_assert(selection::kFlagOutline == AWSM_SELECTION_OUTLINE && selection::kFlagBoxes == AWSM_SELECTION_BOXES, "selection.hpp's flags are the header's");
+int awsm_hip_set_selection(AwsmHipCtx* c, const AwsmSelection* s, const uint32_t* mesh_keys, uint32_t n_keys, const AwsmSelectionBox* boxes, uint32_t n_boxes) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    AwsmSelection full;
+    awsm_hip_selection_defaults(&full);
+    if (s) {
+        if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: AwsmSelection.struct_size = %u (set it to sizeof(AwsmSelection))", s->struct_size);
+        const size_t known = std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
+        memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, known - 4);
+        const float* p = full.outline_color;
+        for (size_t i = 0; i < 11; i++)
+            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: value %zu of the record is not finite", i);
+        if (full.flags & ~(AWSM_SELECTION_OUTLINE | AWSM_SELECTION_BOXES)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: unknown flags 0x%x", full.flags);
+        if (full.outline_radius < 1u || full.outline_radius > (uint32_t)selection::kMaxRadius) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: outline_radius = %u (1 .. %d pixels)", full.outline_radius, selection::kMaxRadius);
+        if (!(full.box_half_width > 0.0f && full.box_half_width <= selection::kMaxHalfWidth)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: box_half_width = %g (pixels, above 0, at most %g)", (double)full.box_half_width, (double)selection::kMaxHalfWidth);
+        for (float al : {full.outline_color[3], full.box_color[3], full.hidden_alpha})
+            if (!(al >= 0.0f && al <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: an alpha of %g (0 .. 1)", (double)al);
+        if (!(full.depth_epsilon >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: depth_epsilon = %g (>= 0)", (double)full.depth_epsilon);
+        if (n_keys > selection::kMaxKeys || n_boxes > selection::kMaxBoxes) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: %u keys and %u boxes (at most %u and %u)", n_keys, n_boxes, selection::kMaxKeys, selection::kMaxBoxes);
+        if ((n_keys && !mesh_keys) || (n_boxes && !boxes)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: a NULL array with a non-zero count");
+        for (uint32_t b = 0; b < n_boxes; b++)
+            for (int ax = 0; ax < 3; ax++) {
+                if (!std::isfinite(boxes[b].min[ax]) || !std::isfinite(boxes[b].max[ax])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: box %u is not finite", b);
+                if (boxes[b].min[ax] > boxes[b].max[ax]) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: box %u has min > max on axis %d", b, ax);
+            }
+    }
+    // host state only: a pass already enqueued carries the record it was enqueued with as kernel arguments
+    AwsmHipCtx::SelectionState& st = c->sel;
+    st.keys.clear(); st.boxes.clear();
+    st.flags = full.flags; st.radius = full.outline_radius;
+    memcpy(st.outline_color, full.outline_color, sizeof st.outline_color); memcpy(st.box_color, full.box_color, sizeof st.box_color);
+    st.half_width = full.box_half_width; st.hidden_alpha = full.hidden_alpha; st.depth_epsilon = full.depth_epsilon;
+    if (s) {
+        st.keys.assign(mesh_keys, mesh_keys + 2u * (size_t)n_keys);
+        if (n_boxes) st.boxes.assign(boxes[0].min, boxes[0].min + 6u * (size_t)n_boxes);
+    }
+    // nothing to draw is the same as off: no keys and no boxes, or flags that reach neither
+    st.on = s && (((full.flags & AWSM_SELECTION_OUTLINE) && n_keys) || ((full.flags & AWSM_SELECTION_BOXES) && n_boxes));
+    return AWSM_OK;
+}
+int awsm_hip_read_selection(AwsmHipCtx* c, uint8_t* selected, uint8_t* ring, float* box_alpha, float* edges) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    const size_t px = (size_t)c->width * c->height;
+    const AwsmHipCtx::SelectionState& st = c->sel_pass[c->slot];
+    if (!px || !c->transparent_done || !st.on || !c->sel_tables[c->slot].ptr) return fail(c, AWSM_ERR_NOT_READY, "read_selection: the last submitted frame had no world transparent pass with a selection on");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    int rc = dev_reserve(c, c->sel_layers, px * 6);      // [px] float, [px] byte, [px] byte
+    if (rc) return rc;
+    if ((rc = sync_scene(c))) return rc;
+    SelectionDev sd;
+    fill_selection(c, st, &sd);
+    sd.layer_box_alpha = (float*)c->sel_layers.ptr; sd.layer_selected = (uint8_t*)(sd.layer_box_alpha + px); sd.layer_ring = sd.layer_selected + px;
+    awsm_launch_selection_layers(&sd, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (selected) HIPCHK(c, hipMemcpy(selected, sd.layer_selected, px, hipMemcpyDeviceToHost));
+    if (ring) HIPCHK(c, hipMemcpy(ring, sd.layer_ring, px, hipMemcpyDeviceToHost));
+    if (box_alpha) HIPCHK(c, hipMemcpy(box_alpha, sd.layer_box_alpha, px * 4, hipMemcpyDeviceToHost));
+    if (edges && sd.n_boxes) HIPCHK(c, hipMemcpy(edges, sd.edges, (size_t)sd.n_boxes * selection::kEdgesPerBox * selection::kEdgeFloats * 4, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 

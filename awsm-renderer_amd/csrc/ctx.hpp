@@ -182,6 +182,17 @@ struct AwsmHipCtx {
     // enqueued with (awsm_hip_frame_end replays the pass with that); grid_layer: awsm_hip_read_editor_grid's scratch
     struct GridState { bool on = false; float p[20] = {}; } grid, grid_pass[kSlots];
     DevBuf grid_layer;
+    // the editor's selection overlay (awsm_hip_set_selection, kernels_selection.hip): what the caller last set, and per frame slot what the slot's
+    // world transparent pass was enqueued with (awsm_hip_frame_end replays the pass with that); sel_tables: per slot the byte per world draw and the
+    // edge records; sel_layers: awsm_hip_read_selection's scratch
+    struct SelectionState {
+        bool on = false;
+        uint32_t flags = 0, radius = 0;
+        float outline_color[4] = {}, box_color[4] = {}, half_width = 0, hidden_alpha = 0, depth_epsilon = 0;
+        std::vector<uint32_t> keys;       // {high, low} per key
+        std::vector<float> boxes;         // {min xyz, max xyz} per box
+    } sel, sel_pass[kSlots];
+    DevBuf sel_tables[kSlots], sel_layers;
     DevBuf comp16, comp32;       // composite image (after the transparent pass) + parity tap
     // the effects + display passes (awsm_hip_post_pass): the display image per frame slot (or the caller's), the effects image (parity tap only),
     // the bloom chain's two f16 images and the per-pixel DoF terms — the last four per context: a post pass waits for the other slot's to end

@@ -9,6 +9,7 @@
 #include "frame_params.hpp"
 #include "env_cube.hpp"
 #include "tex_pool.hpp"
+#include "selection.hpp"
 
 extern "C" {
 // kernels_geometry.hip
@@ -45,6 +46,9 @@ void awsm_launch_post(const awsm::PostArgs* args, uint32_t flags, uint32_t msaa,
 void awsm_launch_ssao(const awsm::SsaoArgs* args, uint32_t msaa, hipStream_t s);
 // kernels_shadow.hip
 void awsm_launch_shadow_resolve(const awsm::ShadowArgs* args, uint32_t msaa, hipStream_t s);
+// kernels_selection.hip
+void awsm_launch_selection(const awsm::SelectionDev* args, hipStream_t s);
+void awsm_launch_selection_layers(const awsm::SelectionDev* args, hipStream_t s);
 // kernels_env.hip
 void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s);
 void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, uint2* dst, uint32_t n, hipStream_t s);

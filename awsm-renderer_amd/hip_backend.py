@@ -42,7 +42,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_skin_pose_records_write", "awsm_hip_skin_pose", "awsm_hip_buffer_read",
            "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid",
            "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao",
-           "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow"]
+           "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow",
+           "awsm_hip_selection_defaults", "awsm_hip_set_selection", "awsm_hip_read_selection"]
 
 
 class AwsmConfig(C.Structure):
@@ -109,6 +110,35 @@ class AwsmShadow(C.Structure):
             else:
                 setattr(self, k, int(v) if k in ("map_size", "pcf_radius") else float(v))
         return self
+
+
+AWSM_SELECTION_OUTLINE, AWSM_SELECTION_BOXES = 1, 2
+
+
+class AwsmSelection(C.Structure):
+    """The editor's selection overlay (awsm_hip_set_selection): flags (outline, boxes), the outline's radius in pixels and colour, the boxes' colour,
+    half width in pixels, the factor on a box fragment behind the world's depth, and what is subtracted from a fragment's depth before the test."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("outline_radius", C.c_uint32), ("outline_color", C.c_float * 4), ("box_color", C.c_float * 4),
+                ("box_half_width", C.c_float), ("hidden_alpha", C.c_float), ("depth_epsilon", C.c_float)]
+
+    def override(self, **overrides):
+        """Set fields by name (a colour from any four numbers); an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k == "struct_size":
+                raise TypeError("AwsmSelection has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
+            setattr(self, k, (C.c_float * 4)(*[float(x) for x in v]) if k.endswith("_color") else int(v) if k in ("flags", "outline_radius") else float(v))
+        return self
+
+
+def selection_key_words(mesh_keys) -> np.ndarray:
+    """Mesh keys as the device takes them: [n, 2] uint32 {high, low}, from 64-bit keys or from (high, low) pairs."""
+    if len(mesh_keys) == 0:
+        return np.zeros((0, 2), np.uint32)
+    if np.ndim(mesh_keys[0]) == 1:
+        return np.ascontiguousarray(np.array([[int(h), int(l)] for h, l in mesh_keys], dtype=np.uint32))
+    a = np.array([int(k) for k in mesh_keys], dtype=np.uint64)
+    return np.ascontiguousarray(np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.uint32))
 
 
 class AwsmCubeLayout(C.Structure):
@@ -279,6 +309,9 @@ def load_library():
     lib.awsm_hip_editor_grid_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_set_editor_grid.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_editor_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_selection_defaults.argtypes = [C.c_void_p]
+    lib.awsm_hip_set_selection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    lib.awsm_hip_read_selection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.awsm_hip_ssao_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_set_ssao.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_ssao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -613,6 +646,37 @@ class HipDevice:
         raw, smoothed, view_z = (np.empty((self.height, self.width), np.float32) for _ in range(3))
         self._chk(self.lib.awsm_hip_read_ssao(self.ctx, raw.ctypes.data, smoothed.ctypes.data, view_z.ctypes.data), "read_ssao")
         return raw, smoothed, view_z
+
+    def selection_defaults(self) -> AwsmSelection:
+        s = AwsmSelection()
+        self._chk(self.lib.awsm_hip_selection_defaults(C.byref(s)), "selection_defaults")
+        return s
+
+    def set_selection(self, mesh_keys=(), boxes=(), on=True, struct_size: Optional[int] = None, n_keys: Optional[int] = None, n_boxes: Optional[int] = None, **overrides):
+        """The editor's selection overlay in every later transparent_pass: an outline around the visible pixels of the meshes `mesh_keys` (64-bit keys, or
+        (high, low) pairs as pick() reports them) and a wire box around every box of `boxes` ((min xyz, max xyz) in world space), with the defaults and
+        `overrides` (AwsmSelection's field names).  set_selection(on=None) turns it off.  struct_size, n_keys, n_boxes: what the call claims (tests)."""
+        if not on:
+            return self._chk(self.lib.awsm_hip_set_selection(self.ctx, None, None, 0, None, 0), "set_selection")
+        s = self.selection_defaults().override(**overrides)
+        if struct_size is not None:
+            s.struct_size = struct_size
+        keys = selection_key_words(mesh_keys)
+        bx = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 6))
+        self._chk(self.lib.awsm_hip_set_selection(self.ctx, C.byref(s), keys.ctypes.data if keys.size else None, len(keys) if n_keys is None else n_keys,
+                                                  bx.ctypes.data if bx.size else None, len(bx) if n_boxes is None else n_boxes), "set_selection")
+        self._selection_boxes = len(bx)
+
+    def read_selection(self, n_boxes: Optional[int] = None):
+        """The last submitted frame's selection layers -> (selected bool [H, W], ring bool [H, W], box alpha float32 [H, W], edges float32
+        [n_boxes, 12, 8]: x0 y0 z0 x1 y1 z1 valid pad).  n_boxes: the count the frame's record holds; it may be left out when the selection was set
+        through this object's set_selection."""
+        nb = int(n_boxes if n_boxes is not None else getattr(self, "_selection_boxes", 0))
+        selected, ring = np.empty((self.height, self.width), np.uint8), np.empty((self.height, self.width), np.uint8)
+        alpha = np.empty((self.height, self.width), np.float32)
+        edges = np.zeros((nb, 12, 8), np.float32)
+        self._chk(self.lib.awsm_hip_read_selection(self.ctx, selected.ctypes.data, ring.ctypes.data, alpha.ctypes.data, edges.ctypes.data if nb else None), "read_selection")
+        return selected.astype(bool), ring.astype(bool), alpha, edges
 
     def shadow_defaults(self) -> AwsmShadow:
         s = AwsmShadow()

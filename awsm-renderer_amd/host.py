@@ -156,6 +156,7 @@ def load_library():
         "awsm_host_clear_post_processing": (C.c_int, [vp]),
         "awsm_host_camera_set_dof": (C.c_int, [vp, C.c_float, C.c_float]),
         "awsm_host_editor_grid_defaults": (C.c_int, [vp, vp]), "awsm_host_set_editor_grid": (C.c_int, [vp, vp]),
+        "awsm_host_selection_defaults": (C.c_int, [vp, vp]), "awsm_host_set_selection": (C.c_int, [vp, vp, vp, C.c_uint32]),
         "awsm_host_ssao_defaults": (C.c_int, [vp, vp]), "awsm_host_set_ssao": (C.c_int, [vp, vp]),
         "awsm_host_shadow_defaults": (C.c_int, [vp, vp]), "awsm_host_set_shadow": (C.c_int, [vp, vp]),
         "awsm_host_shadow_camera": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
@@ -623,6 +624,20 @@ class Host:
         g.override(**overrides)
         self._chk(self.lib.awsm_host_set_editor_grid(self.h, C.byref(g)), "set_editor_grid")
 
+    def set_selection(self, mesh_keys=(), on: bool = True, struct_size: Optional[int] = None, **overrides):
+        """The editor's selection overlay in every later render(): an outline around the visible pixels of the meshes `mesh_keys` (as pick() and
+        mesh_insert() report them) and a wire box around each one's world AABB, which follows the mesh's transform; the backend's defaults with
+        `overrides` (hip_backend.AwsmSelection's field names).  on=False turns it off.  struct_size: what the record claims as its size (tests)."""
+        if not on:
+            return self._chk(self.lib.awsm_host_set_selection(self.h, None, None, 0), "set_selection")
+        s = hip_backend.AwsmSelection()
+        self._chk(self.lib.awsm_host_selection_defaults(self.h, C.byref(s)), "selection_defaults")
+        s.override(**overrides)
+        if struct_size is not None:
+            s.struct_size = struct_size
+        keys = (C.c_uint64 * max(1, len(mesh_keys)))(*[int(k) for k in mesh_keys])
+        self._chk(self.lib.awsm_host_set_selection(self.h, C.byref(s), keys, len(mesh_keys)), "set_selection")
+
     def set_ssao(self, on: bool = True, **overrides):
         """Screen-space ambient occlusion in the opaque pass of every later render(): the backend's defaults with `overrides`
         (hip_backend.AwsmSsao's field names: radius, intensity, bias, strength).  on=False turns it off."""
@@ -1048,6 +1063,10 @@ class Renderer:
 
     def set_ssao(self, on: bool = True, **overrides):
         self.host.set_ssao(on, **overrides)
+
+    def set_selection(self, mesh_keys=(), on: bool = True, **overrides):
+        """Outline and box the meshes `mesh_keys` (keys from pick()) in every later render(); on=False for off."""
+        self.host.set_selection(mesh_keys, on, **overrides)
 
     def set_shadow(self, light=True, **overrides):
         """Shadows from one of the scene's lights: an index into scene.lights, True for the first directional light (the first spot light if

@@ -72,6 +72,8 @@ struct Backend {
     int (*set_editor_grid)(AwsmHipCtx*, const AwsmEditorGrid*) = nullptr;
     int (*ssao_defaults)(AwsmSsao*) = nullptr;                          // optional: screen-space ambient occlusion (awsm_host_set_ssao)
     int (*set_ssao)(AwsmHipCtx*, const AwsmSsao*) = nullptr;
+    int (*selection_defaults)(AwsmSelection*) = nullptr;                // optional: the editor's selection overlay (awsm_host_set_selection)
+    int (*set_selection)(AwsmHipCtx*, const AwsmSelection*, const uint32_t*, uint32_t, const AwsmSelectionBox*, uint32_t) = nullptr;
     int (*shadow_defaults)(AwsmShadow*) = nullptr;                      // optional: shadows (awsm_host_set_shadow)
     int (*shadow_pass)(AwsmHipCtx*, const AwsmShadow*, const void*, size_t, const AwsmDraw*, uint32_t) = nullptr;
     // optional: environment cubes at run time (awsm_host_env_cube_*)
@@ -253,6 +255,11 @@ struct AwsmHost {
     bool post_on = false;
     AwsmPostParams post{};
     bool grid_on = false;                      // awsm_host_set_editor_grid: the world transparent pass runs every frame, with no draws if need be
+    // awsm_host_set_selection: the record as the caller gave it (its struct_size says how much of it counts) and the mesh keys; every render hands
+    // the backend the key words and the world AABBs of those that are there, shown and not HUD.  While on, the world transparent pass runs every frame.
+    bool selection_on = false;
+    AwsmSelection selection{};
+    std::vector<AwsmKey> selection_keys;
     bool sharded = false;                      // awsm_host_set_shard_rows / _bands gave this host a part of the frame (the post pass needs all of it)
     // ---- shadows (awsm_host_set_shadow): the record, and what the last render handed the backend (awsm_host_shadow_camera) ----
     bool shadow_on = false, shadow_rendered = false;
@@ -702,6 +709,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.set_editor_grid = reinterpret_cast<decltype(b.set_editor_grid)>(dlsym(b.dl, "awsm_hip_set_editor_grid"));
     b.ssao_defaults = reinterpret_cast<decltype(b.ssao_defaults)>(dlsym(b.dl, "awsm_hip_ssao_defaults"));      // optional (awsm_host_set_ssao)
     b.set_ssao = reinterpret_cast<decltype(b.set_ssao)>(dlsym(b.dl, "awsm_hip_set_ssao"));
+    b.selection_defaults = reinterpret_cast<decltype(b.selection_defaults)>(dlsym(b.dl, "awsm_hip_selection_defaults"));      // optional (awsm_host_set_selection)
+    b.set_selection = reinterpret_cast<decltype(b.set_selection)>(dlsym(b.dl, "awsm_hip_set_selection"));
     b.shadow_defaults = reinterpret_cast<decltype(b.shadow_defaults)>(dlsym(b.dl, "awsm_hip_shadow_defaults"));      // optional (awsm_host_set_shadow)
     b.shadow_pass = reinterpret_cast<decltype(b.shadow_pass)>(dlsym(b.dl, "awsm_hip_shadow_pass"));
     b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
@@ -1597,6 +1606,7 @@ int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes
 }
 
 static int render_shadow_pass(AwsmHost* h);
+static int send_selection(AwsmHost* h);
 int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render.rs:53-383 (hot path only)
     if (!h->width) return fail(h, AWSM_ERR_NOT_READY, "render before resize");
     h->shadow_rendered = false;
@@ -1690,7 +1700,8 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     if (h->after_opaque && (rc = h->after_opaque(h->after_opaque_user))) { h->last_error = "after_opaque_pass hook failed"; return rc; }
     // ---- opaque -> transparent blit + world transparent pass (render.rs:224-297).  A scene without transparent meshes skips it:
     // the composite image then IS the opaque image (the reference would copy it) — unless the editor's grid is on, which that pass draws. ----
-    if (h->has_transparent_meshes || h->has_hud_meshes || h->grid_on) { if ((rc = h->be.transparent_pass(h->ctx, h->last_transparent_draws.data(), (uint32_t)h->last_transparent_draws.size()))) return dev_fail(h, rc, "transparent_pass"); }
+    if (h->selection_on && (rc = send_selection(h))) return rc;      // the selected meshes' boxes as update_world left them
+    if (h->has_transparent_meshes || h->has_hud_meshes || h->grid_on || h->selection_on) { if ((rc = h->be.transparent_pass(h->ctx, h->last_transparent_draws.data(), (uint32_t)h->last_transparent_draws.size()))) return dev_fail(h, rc, "transparent_pass"); }
     // ---- the HUD transparent pass over the composite (render.rs:301-312) ----
     if (h->has_hud_meshes && (rc = h->be.hud_transparent_pass(h->ctx, h->last_hud_transparent_draws.data(), (uint32_t)h->last_hud_transparent_draws.size()))) return dev_fail(h, rc, "hud_transparent_pass");
     // ---- the effects + display passes (render.rs:339-356), when post-processing was turned on ----
@@ -1725,6 +1736,53 @@ int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid) {
     const int rc = h->be.set_editor_grid(h->ctx, grid);
     if (rc) return dev_fail(h, rc, "set_editor_grid");
     h->grid_on = grid != nullptr;
+    return AWSM_OK;
+}
+
+// The editor's selection overlay: a built-in of the backend's world transparent pass.  The host remembers the mesh keys; what the
+// backend gets is the key words of the selected meshes that are there, shown and not HUD, and one box per such mesh that has a world AABB — the
+// cull step's, as update_world left it — so a box follows its mesh's transform with nothing more to call.
+static int send_selection(AwsmHost* h) {
+    std::vector<uint32_t> words;
+    std::vector<AwsmSelectionBox> boxes;
+    for (AwsmKey k : h->selection_keys) {
+        const MeshRec* m = h->meshes.get(k);
+        if (!m || m->hidden || m->hud) continue;      // a removed mesh drops out silently
+        words.push_back((uint32_t)(k >> 32)); words.push_back((uint32_t)(k & 0xFFFFFFFFull));
+        if (m->has_world_aabb) boxes.push_back(AwsmSelectionBox{{m->world_aabb.min.x, m->world_aabb.min.y, m->world_aabb.min.z}, {m->world_aabb.max.x, m->world_aabb.max.y, m->world_aabb.max.z}});
+    }
+    const int rc = h->be.set_selection(h->ctx, &h->selection, words.data(), (uint32_t)(words.size() / 2), boxes.data(), (uint32_t)boxes.size());
+    return rc ? dev_fail(h, rc, "set_selection") : AWSM_OK;
+}
+int awsm_host_selection_defaults(AwsmHost* h, AwsmSelection* out) {
+    if (!h || !out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.selection_defaults) return fail(h, AWSM_ERR_UNSUPPORTED, "selection_defaults: the backend library has no %s", "awsm_hip_selection_defaults");
+    const int rc = h->be.selection_defaults(out);
+    return rc ? dev_fail(h, rc, "selection_defaults") : AWSM_OK;
+}
+int awsm_host_set_selection(AwsmHost* h, const AwsmSelection* selection, const uint64_t* mesh_keys, uint32_t n) {
+    if (!h || (n && !mesh_keys)) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.set_selection) return fail(h, AWSM_ERR_UNSUPPORTED, "set_selection: the backend library has no %s", "awsm_hip_set_selection");
+    if (!selection) {
+        const int rc = h->be.set_selection(h->ctx, nullptr, nullptr, 0, nullptr, 0);
+        if (rc) return dev_fail(h, rc, "set_selection");
+        h->selection_on = false; h->selection_keys.clear();
+        return AWSM_OK;
+    }
+    if (selection->struct_size < 4u || selection->struct_size > 4096u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_selection: AwsmSelection.struct_size = %u (set it to sizeof(AwsmSelection))", selection->struct_size);
+    // the backend judges the record, now, with the meshes as they stand; its refusal leaves the selection as it was
+    const AwsmSelection was = h->selection;
+    std::vector<AwsmKey> keys_were(mesh_keys, mesh_keys + n);
+    keys_were.swap(h->selection_keys);
+    memset(&h->selection, 0, sizeof h->selection);
+    memcpy(&h->selection, selection, std::min<size_t>(selection->struct_size, sizeof h->selection));
+    h->selection.struct_size = (uint32_t)std::min<size_t>(selection->struct_size, sizeof h->selection);      // nothing beyond the caller's size is read, here or there
+    const int rc = send_selection(h);
+    if (rc) {
+        h->selection = was; h->selection_keys.swap(keys_were);      // (a refusing backend keeps its own state unchanged)
+        return rc;
+    }
+    h->selection_on = true;
     return AWSM_OK;
 }
 

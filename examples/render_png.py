@@ -15,6 +15,8 @@ vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl th
 looked up per pixel and multiplied into the opaque image.
 --ssao darkens creases and contact lines: ambient occlusion estimated from the geometry pass's depth (--ssao-radius R in world units, --ssao-intensity I).
 --grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
+--select X,Y (may be repeated) picks the mesh under each pixel of a first frame and renders again with those meshes selected: an outline around their
+visible pixels and a wire box around each one's world bounding box, dimmed where other geometry hides it.
 """
 import argparse
 import os
@@ -57,6 +59,7 @@ def main():
                          "whose lights are the file's and have no index here")
     ap.add_argument("--shadow-size", type=int, default=None, metavar="N", help="with --shadow: the shadow map is N x N (default 2048)")
     ap.add_argument("--shadow-strength", type=float, default=None, metavar="X", help="with --shadow: how dark a shadow is, 0 .. 1 (default 0.7)")
+    ap.add_argument("--select", action="append", default=[], metavar="X,Y", help="select the mesh under this pixel (outline + bounding box); may be repeated; not with --via-glb")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -103,6 +106,19 @@ def main():
             ap.error("--shadow names a light by its index in the scene description; a scene read from a .glb keeps no such index (Host.set_shadow takes a light's key)")
         r.set_shadow(True if a.shadow < 0 else a.shadow, **{k: v for k, v in (("map_size", a.shadow_size), ("strength", a.shadow_strength)) if v is not None})
     stats = r.render(sync=True)
+    picked = []
+    if a.select:
+        if a.via_glb:
+            ap.error("--select picks through the scene description's meshes; not with --via-glb")
+        for xy in a.select:
+            x, y = (int(v) for v in xy.split(","))
+            key = r.host.pick(x, y)
+            print(f"--select {x},{y}: " + ("nothing there" if key is None else f"mesh {key:#x}"))
+            if key is not None and key not in picked:
+                picked.append(key)
+        if picked:
+            r.set_selection(picked)
+            stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
     if post:
         rgba = dev.read_display()
@@ -111,7 +127,7 @@ def main():
         Image.fromarray(rgba[..., :3]).save(a.out)
         print(f"{a.out}: {W}x{H}, post pass {a.tonemap or 'khronos'} bloom={a.bloom} dof={a.dof} smaa={a.smaa}, the device's RGBA8 display image")
         return
-    final = dev.read_composite() if stats["forward_triangles"] or a.grid else dev.read_opaque()      # the image after the transparent pass, when the scene has one
+    final = dev.read_composite() if stats["forward_triangles"] or a.grid or picked else dev.read_opaque()      # the image after the transparent pass, when the scene has one
     img = final.view(np.float16).astype(np.float32)[..., :3]
     r.close()
     ldr = np.clip(img / (1.0 + img), 0.0, 1.0) ** (1.0 / 2.2)

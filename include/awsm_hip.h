@@ -660,6 +660,48 @@ int awsm_hip_shadow_pass(AwsmHipCtx* ctx, const AwsmShadow* shadow, const void* 
 int awsm_hip_read_shadow_map(AwsmHipCtx* ctx, uint64_t* keys_out /* map_size^2 */);
 int awsm_hip_read_shadow(AwsmHipCtx* ctx, float* visibility_out, float* multiplier_out /* width x height each */);
 
+/* ---- the editor's selection overlay ("Visual bounding box around selected objects" of the reference's "Next up" list).  A built-in
+ * of awsm_hip_transparent_pass, drawn as its last step — over the grid, the transparent meshes and the MSAA resolve, under the HUD transparent pass,
+ * in front of the post pass: an OUTLINE around the visible pixels of the selected meshes (opaque meshes: from the WORLD visibility keys; a pixel is
+ * selected when any of its samples shows a triangle of a selected mesh, and the ring is every unselected pixel within outline_radius pixels of a
+ * selected one), and a WIRE BOX around every listed world-space box (opaque and transparent meshes alike), anti-aliased lines of half width
+ * box_half_width, tested against the WORLD's depth (the least of the samples; never hud_depth, never what the transparent meshes wrote) and
+ * multiplied by hidden_alpha where behind it.  Both blend SrcAlpha / OneMinusSrcAlpha into the RGBA16F composite, ring first; the opaque image and
+ * the keys are untouched.  Off by default; with it off the pass runs the kernels it ran before this entry existed.
+ *   defaults       both flags, outline_radius 2, outline (1, 0.6, 0.1, 1), box (1, 0.6, 0.1, 0.9), box_half_width 0.75, hidden_alpha 0.25,
+ *                  depth_epsilon 1e-5; struct_size = sizeof(AwsmSelection).
+ *   set_selection  NULL turns it off.  struct_size as for awsm_hip_set_editor_grid.  mesh_keys: n_keys x {high, low} as AwsmPick reports them,
+ *                  n_keys <= 64; boxes: n_boxes <= 64.  Keys and boxes are copied.  AWSM_ERR_INVALID_ARGUMENT, with the state unchanged, for a
+ *                  non-finite value, unknown flag bits, outline_radius outside 1..4, box_half_width outside (0, 4], an alpha or hidden_alpha
+ *                  outside [0, 1], depth_epsilon < 0, a box with min > max on some axis, a count over its cap, a NULL array with a non-zero
+ *                  count.  No keys and no boxes, or flags that leave nothing to draw, is the same as off.  Takes effect from the next
+ *                  awsm_hip_transparent_pass; a pass already enqueued (AWSM_CFG_OVERLAP_FRAMES) and a replay by awsm_hip_frame_end keep the
+ *                  record the pass was given.  The HUD transparent pass never draws it.
+ *   read_selection the layers of the last submitted frame, computed once more from its keys, draw list and camera snapshot with the record its pass
+ *                  was given: selected and ring (1 / 0) and the box alpha A per pixel, and the edge table, 8 floats per edge in box order, edges
+ *                  by axis then corner: x0 y0 z0 x1 y1 z1 (pixels, pixels, NDC depth) valid pad, all zero for an edge that is clipped away.  Any
+ *                  pointer may be NULL.  Synchronous.  AWSM_ERR_NOT_READY unless that frame's world transparent pass ran with selection on.
+ * On a sharded context (row strips or bands) a world transparent pass with selection on returns AWSM_ERR_UNSUPPORTED, as SSAO does: the ring
+ * needs rows the shard never rasterised. ---- */
+#define AWSM_SELECTION_OUTLINE 1u
+#define AWSM_SELECTION_BOXES 2u
+typedef struct AwsmSelection {
+    uint32_t struct_size;
+    uint32_t flags;            /* AWSM_SELECTION_OUTLINE | AWSM_SELECTION_BOXES */
+    uint32_t outline_radius;   /* R, 1..4 pixels */
+    float    outline_color[4]; /* rgb, alpha */
+    float    box_color[4];     /* rgb, alpha */
+    float    box_half_width;   /* pixels, 0 < hw <= 4 */
+    float    hidden_alpha;     /* 0..1: factor on a box fragment behind the world's depth */
+    float    depth_epsilon;    /* subtracted from the fragment's depth before the test */
+} AwsmSelection;
+typedef struct AwsmSelectionBox { float min[3], max[3]; } AwsmSelectionBox;   /* world space */
+int awsm_hip_selection_defaults(AwsmSelection* out);
+int awsm_hip_set_selection(AwsmHipCtx* ctx, const AwsmSelection* selection /* NULL = off */,
+                           const uint32_t* mesh_keys /* n_keys x {high, low} */, uint32_t n_keys, const AwsmSelectionBox* boxes, uint32_t n_boxes);
+int awsm_hip_read_selection(AwsmHipCtx* ctx, uint8_t* selected_out, uint8_t* ring_out, float* box_alpha_out /* width x height each */,
+                            float* edges_out /* n_boxes x 12 x 8 floats */);
+
 #ifdef __cplusplus
 }
 #endif

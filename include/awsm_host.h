@@ -251,6 +251,16 @@ int awsm_host_clear_post_processing(AwsmHost* h);
  * lacks awsm_hip_set_editor_grid / awsm_hip_editor_grid_defaults; the backend's own refusals (a non-finite value, a bad struct_size) pass through. */
 int awsm_host_editor_grid_defaults(AwsmHost* h, AwsmEditorGrid* out);
 int awsm_host_set_editor_grid(AwsmHost* h, const AwsmEditorGrid* grid /* NULL = off */);
+/* The editor's selection overlay (awsm_hip_set_selection in awsm_hip.h has the rules): an outline around the visible pixels of the selected meshes
+ * and a wire box around each one's world AABB, drawn by the backend's world transparent pass.  The host remembers `mesh_keys` (as awsm_host_pick
+ * reports them); every awsm_host_render hands the backend the key words of those that still exist and are neither hidden nor HUD, and one box per
+ * such mesh that has a world AABB — the cull step's, as awsm_host_update_transforms left it — so the box follows a moved or animated transform with
+ * nothing more to call.  Transparent meshes get a box (they have no visibility key to be outlined by).  A removed mesh drops out silently.  While
+ * a selection is set awsm_host_render runs the world transparent pass in every frame, with no draws if need be.  NULL turns it off.
+ * selection_defaults fills the backend's defaults, to change a field from.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library
+ * lacks awsm_hip_set_selection / awsm_hip_selection_defaults; the backend's own refusals pass through and leave the selection as it was. */
+int awsm_host_selection_defaults(AwsmHost* h, AwsmSelection* out);
+int awsm_host_set_selection(AwsmHost* h, const AwsmSelection* selection /* NULL = off */, const uint64_t* mesh_keys, uint32_t n);
 /* Screen-space ambient occlusion (awsm_hip_set_ssao in awsm_hip.h has the rules): a built-in of the backend's opaque pass, off until this is called;
  * the record is passed through unchanged and holds for every later awsm_host_render.  NULL turns it off again.  ssao_defaults fills the backend's
  * defaults, to change a field from.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library lacks awsm_hip_set_ssao /
