@@ -86,6 +86,7 @@ int handoff_check(AwsmHipCtx* c) {
         c->handoff = false;
         c->handoff_error_pending = true;
         for (FrameBufs& b : c->fb) b.cache_valid = false;      // a dropped frame's kernels wrote nothing: the geometry cache's book-keeping no longer describes the arrays
+        c->taa_have = false; c->taa_serial = 0;                // ... and its resolve exited: the image it would have written is no history
     }
     if (!c->handoff_error_pending) return AWSM_OK;
     c->handoff_error_pending = false;
@@ -992,6 +993,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     fr(c->env_stage); fr(c->env_tables); fr(c->env_rows); fr(c->env_filter_tab); if (c->ev_env_copy) (void)hipEventDestroy(c->ev_env_copy);
     fr(c->lut); for (auto& b : c->cube_tex) fr(b); for (auto& b : c->cube_bordered) fr(b); fr(c->digest); for (auto& b : c->shade_todo) fr(b); for (int sl = 0; sl < kSlots; sl++) { fr(c->msaa_color0[sl]); fr(c->msaa_edges[sl]); fr(c->msaa_edge_bits[sl]); fr(c->msaa_cells[sl]); } fr(c->mip_kinds); for (auto& b : c->out16) fr(b); for (auto& b : c->out32) fr(b); fr(c->comp16); fr(c->comp32); fr(c->grid_layer); for (auto& b : c->lights_pre) fr(b);
     for (auto& b : c->ssao_layers) fr(b);
+    for (auto& b : c->taa_img) fr(b); fr(c->taa_layers);
     for (auto& b : c->sel_tables) fr(b);
     fr(c->sel_layers);
     for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
@@ -1176,6 +1178,7 @@ int awsm_hip_resize(AwsmHipCtx* c, uint32_t width, uint32_t height, uint32_t msa
     c->band_n = 1; c->band_r = 0; c->band_compact = 0;
     c->geometry_done = c->opaque_done = c->transparent_done = c->hud_transparent_done = c->post_done = false;
     c->last_display = nullptr;      // the images are sized for the old frame
+    c->taa_have = false; c->taa_serial = 0; c->taa_resolved = false;      // ... and so is the TAA history (a new MSAA mode drops it too)
     return AWSM_OK;
 }
 
@@ -2119,6 +2122,60 @@ int awsm_hip_read_selection(AwsmHipCtx* c, uint8_t* selected, uint8_t* ring, flo
     return AWSM_OK;
 }
 
+// ---- temporal anti-aliasing (kernels_taa.hip) ----
+int awsm_hip_taa_defaults(AwsmTaa* out) {
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    static const AwsmTaa d = {(uint32_t)sizeof(AwsmTaa), 0.1f, 0u, {0.0f, 0.0f}, {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    *out = d;
+    return AWSM_OK;
+}
+int awsm_hip_set_taa(AwsmHipCtx* c, const AwsmTaa* t) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!t) {      // off: the history goes with it
+        c->taa.on = false;
+        c->taa_have = false; c->taa_serial = 0;
+        return AWSM_OK;
+    }
+    AwsmTaa full;
+    awsm_hip_taa_defaults(&full);
+    if (t->struct_size < 4u || t->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: AwsmTaa.struct_size = %u (set it to sizeof(AwsmTaa))", t->struct_size);
+    const size_t known = std::min<size_t>(t->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
+    memcpy((uint8_t*)&full + 4, (const uint8_t*)t + 4, known - 4);
+    if (!std::isfinite(full.feedback) || !(full.feedback > 0.0f && full.feedback <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: feedback = %g (0 < feedback <= 1)", (double)full.feedback);
+    if (full.flags & ~AWSM_TAA_RESET) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: unknown flags 0x%x", full.flags);
+    for (int i = 0; i < 2; i++) if (!std::isfinite(full.jitter_ndc[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: jitter_ndc[%d] is not finite", i);
+    for (int i = 0; i < 16; i++) if (!std::isfinite(full.reproject[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: reproject[%d] is not finite", i);
+    // host state only: a pass already enqueued carries the record it was enqueued with as kernel arguments
+    AwsmHipCtx::TaaState& st = c->taa;
+    st.on = true;
+    st.feedback = full.feedback;
+    st.flags |= full.flags;      // a reset asked for stays asked for until a post pass has taken it
+    memcpy(st.jitter, full.jitter_ndc, sizeof st.jitter); memcpy(st.reproject, full.reproject, sizeof st.reproject);
+    return AWSM_OK;
+}
+int awsm_hip_read_taa(AwsmHipCtx* c, uint16_t* resolved, float* lookup_xy, uint8_t* used) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    const size_t px = (size_t)c->width * c->height;
+    if (!px || !c->taa_resolved || !c->post_done || c->taa_serial != c->frame_serial) return fail(c, AWSM_ERR_NOT_READY, "read_taa: the last post pass did not resolve (awsm_hip_set_taa, then awsm_hip_post_pass)");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    if (resolved) HIPCHK(c, hipMemcpy(resolved, c->taa_args.out, px * 8, hipMemcpyDeviceToHost));
+    if (lookup_xy || used) {
+        // the old history is still what it was and the frame's keys are still in its slot: the layers are computed, not kept
+        const int rc = dev_reserve(c, c->taa_layers, px * 9);      // [px][2] float, [px] byte
+        if (rc) return rc;
+        TaaArgs t = c->taa_args;
+        t.layer_xy = (float*)c->taa_layers.ptr; t.layer_used = (uint8_t*)(t.layer_xy + 2 * px);
+        t.poison = nullptr;
+        awsm_launch_taa_layers(&t, c->msaa == 4 ? 4u : 1u, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (lookup_xy) HIPCHK(c, hipMemcpy(lookup_xy, t.layer_xy, px * 8, hipMemcpyDeviceToHost));
+        if (used) HIPCHK(c, hipMemcpy(used, t.layer_used, px, hipMemcpyDeviceToHost));
+    }
+    return AWSM_OK;
+}
+
 // EffectsRenderPass::render + DisplayRenderPass::render (render.rs:339-356); the kernels and the contract: kernels_post.hip, DESIGN.md §11
 int awsm_hip_post_pass(AwsmHipCtx* c, const AwsmPostParams* p) {
     if (!c || !p) return AWSM_ERR_INVALID_ARGUMENT;
@@ -2128,6 +2185,10 @@ int awsm_hip_post_pass(AwsmHipCtx* c, const AwsmPostParams* p) {
     const bool sharded = c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height));
     if (sharded) return fail(c, AWSM_ERR_UNSUPPORTED, "post_pass on a sharded context: the SMAA / bloom / DoF stencils read neighbouring rows (no halo exchange)");
     if (c->width == 0 || !c->geometry_done || !c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "post_pass needs the frame's opaque pass first");
+    // temporal anti-aliasing (awsm_hip_set_taa): this pass carries the record as it stands now, into a replay too
+    if (c->taa.on && (c->taa.flags & AWSM_TAA_RESET)) { c->taa_have = false; c->taa_serial = 0; c->taa.flags &= ~AWSM_TAA_RESET; }      // one pass, then cleared
+    c->taa_pass = c->taa;
+    if (!c->taa.on) c->taa_resolved = false;
     return enqueue_post(c, *p);
 }
 
@@ -2162,6 +2223,27 @@ static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& pp) {
     hipStream_t ss = shade_stream_of(c);          // in order after the opaque / transparent passes of the frame
     // the bloom / DoF scratch and the effects image are per context: behind the other slot's passes (its post pass among them)
     if (c->overlap && c->shade_recorded[prev_slot(c)]) HIPCHK(c, wait_prev_slot(c, ss));
+    if (c->taa_pass.on) {
+        // the resolve first, behind the other slot's passes — its post pass wrote the history this one reads, and read the image this one
+        // overwrites — and the resolved image is what everything below takes as src
+        if ((rc = dev_reserve(c, c->taa_img[0], px * 8)) || (rc = dev_reserve(c, c->taa_img[1], px * 8))) return rc;
+        if (c->taa_serial != c->frame_serial) {      // once per frame serial: a replay reads the same history and rewrites the same image
+            c->taa_frame_hist = c->taa_have;
+            c->taa_cur ^= 1;
+            c->taa_serial = c->frame_serial;
+        }
+        const AwsmHipCtx::TaaState& ts = c->taa_pass;
+        TaaArgs t{};
+        t.width = c->width; t.height = c->height;
+        t.cur = a.src; t.vis = a.vis;
+        t.history = c->taa_frame_hist ? (const uint2*)c->taa_img[c->taa_cur ^ 1].ptr : nullptr;
+        t.out = (uint2*)c->taa_img[c->taa_cur].ptr;
+        memcpy(t.reproject, ts.reproject, sizeof t.reproject); t.jitter[0] = ts.jitter[0]; t.jitter[1] = ts.jitter[1]; t.feedback = ts.feedback;
+        t.poison = a.poison; t.frame_serial = a.frame_serial;
+        awsm_launch_taa(&t, c->msaa == 4 ? 4u : 1u, ss);
+        a.src = t.out;
+        c->taa_args = t; c->taa_have = true; c->taa_resolved = true;
+    }
     awsm_launch_post(&a, p->flags, c->msaa == 4 ? 4u : 1u, c->bloom_a.ptr, c->bloom_b.ptr, ss);
     HIPCHK(c, hipGetLastError());
     if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));       // the slot's next geometry pass waits for this too

@@ -256,6 +256,25 @@ struct AwsmHipCtx {
     struct ShadowState { bool on = false; AwsmShadow p{}; float light_view_proj[16] = {}; } shadow_pass[kSlots];
     DevBuf shadow_layers[kSlots];    // per slot [2][px] f32: V, m
     size_t shadow_px[kSlots] = {};   // pixels of the frame the slot's layers were last written for (0: that frame had no resolve)
+
+    // temporal anti-aliasing (awsm_hip_set_taa).  taa: what the caller last set; taa_pass: what the frame's post pass was given
+    // (awsm_hip_frame_end enqueues that pass again with it).  taa_img: two RGBA16F images per context — not per frame slot — in ping-pong:
+    // taa_img[taa_cur] is what the last resolve wrote, the other one what it read.  The index advances once per frame serial (taa_serial; 0: no
+    // resolve since the history was last dropped), so a replayed post pass reads the same history and rewrites the same image.
+    struct TaaState {
+        bool on = false;
+        float feedback = 0.1f;
+        uint32_t flags = 0;
+        float jitter[2] = {};
+        float reproject[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    } taa, taa_pass;
+    DevBuf taa_img[2], taa_layers;   // taa_layers: awsm_hip_read_taa's scratch
+    int taa_cur = 0;
+    bool taa_have = false;           // taa_img[taa_cur] holds a resolved image of this size and mode: the next frame's history
+    bool taa_frame_hist = false;     // the resolve of frame taa_serial had a history
+    uint32_t taa_serial = 0;
+    bool taa_resolved = false;       // the last post pass resolved (awsm_hip_read_taa)
+    TaaArgs taa_args{};              // ... with these arguments
 };
 
 #define HIPCHK(c, call)                                                                            \

@@ -318,6 +318,23 @@ struct ShadowArgs {
     uint32_t frame_serial;
 };
 
+// Temporal anti-aliasing (kernels_taa.hip, awsm_hip_set_taa): what k_taa_resolve, enqueued in front of a post pass, and k_taa_layers, run by
+// awsm_hip_read_taa, read and write.
+struct TaaArgs {
+    uint32_t width, height;
+    const uint2* cur;                    // the current image (the composite, or the opaque image when the frame had no transparent pass): RGBA16F
+    const unsigned long long* vis;       // the WORLD geometry pass's keys (x4 with MSAA): never the hud's, never the merged ones
+    const uint2* history;                // the image the last resolve wrote (null: there is no history)
+    uint2* out;                          // the resolved image: the post pass's src, and the next frame's history
+    float reproject[16];                 // R, column-major: AwsmTaa.reproject
+    float jitter[2];                     // AwsmTaa.jitter_ndc
+    float feedback;
+    float* layer_xy;                     // k_taa_layers: per pixel (sx, sy)
+    uint8_t* layer_used;                 // ... and whether the history was usable
+    const uint32_t* poison;              // FrameDev.poison / frame_serial
+    uint32_t frame_serial;
+};
+
 #ifdef __HIPCC__
 // A hand-off gate that gave up (its signal never came within the time budget) has poisoned the frame it guarded: its kernels must not run on
 // buffers that are half written, or still being read.  Wave-uniform, one scalar load.

@@ -49,6 +49,9 @@ void awsm_launch_shadow_resolve(const awsm::ShadowArgs* args, uint32_t msaa, hip
 // kernels_selection.hip
 void awsm_launch_selection(const awsm::SelectionDev* args, hipStream_t s);
 void awsm_launch_selection_layers(const awsm::SelectionDev* args, hipStream_t s);
+// kernels_taa.hip
+void awsm_launch_taa(const awsm::TaaArgs* args, uint32_t msaa, hipStream_t s);
+void awsm_launch_taa_layers(const awsm::TaaArgs* args, uint32_t msaa, hipStream_t s);
 // kernels_env.hip
 void awsm_launch_env_write(const awsm::EnvWriteArgs* a, hipStream_t s);
 void awsm_launch_env_expand_rows(const uint32_t* rows, const uint16_t* tables, uint2* dst, uint32_t n, hipStream_t s);

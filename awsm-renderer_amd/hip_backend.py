@@ -43,7 +43,8 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid",
            "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao",
            "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow",
-           "awsm_hip_selection_defaults", "awsm_hip_set_selection", "awsm_hip_read_selection"]
+           "awsm_hip_selection_defaults", "awsm_hip_set_selection", "awsm_hip_read_selection",
+           "awsm_hip_taa_defaults", "awsm_hip_set_taa", "awsm_hip_read_taa"]
 
 
 class AwsmConfig(C.Structure):
@@ -90,6 +91,32 @@ class AwsmSsao(C.Structure):
             if k not in names or k == "struct_size":
                 raise TypeError("AwsmSsao has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
             setattr(self, k, float(v))
+        return self
+
+
+AWSM_TAA_RESET = 1
+
+
+class AwsmTaa(C.Structure):
+    """Temporal anti-aliasing (awsm_hip_set_taa): the weight of the current image, AWSM_TAA_RESET, the NDC offset the frame's projection was
+    translated by, and the column-major matrix from this frame's unjittered NDC to the previous frame's unjittered clip space."""
+    _fields_ = [("struct_size", C.c_uint32), ("feedback", C.c_float), ("flags", C.c_uint32), ("jitter_ndc", C.c_float * 2), ("reproject", C.c_float * 16)]
+
+    def override(self, **overrides):
+        """Set fields by name (a sequence for jitter_ndc and reproject); an unknown name is a TypeError."""
+        names = dict(self._fields_)
+        for k, v in overrides.items():
+            if k not in names or k == "struct_size":
+                raise TypeError("AwsmTaa has no field %r (fields: %s)" % (k, ", ".join(n for n, _ in self._fields_[1:])))
+            if k == "flags":
+                self.flags = int(v)
+            elif k == "feedback":
+                self.feedback = float(v)
+            else:
+                vals = [float(x) for x in np.asarray(v, dtype=np.float32).reshape(-1)]
+                if len(vals) != len(getattr(self, k)):
+                    raise ValueError("AwsmTaa.%s takes %d values" % (k, len(getattr(self, k))))
+                setattr(self, k, names[k](*vals))
         return self
 
 
@@ -315,6 +342,9 @@ def load_library():
     lib.awsm_hip_ssao_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_set_ssao.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_ssao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_taa_defaults.argtypes = [C.c_void_p]
+    lib.awsm_hip_set_taa.argtypes = [C.c_void_p, C.c_void_p]
+    lib.awsm_hip_read_taa.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.awsm_hip_shadow_defaults.argtypes = [C.c_void_p]
     lib.awsm_hip_shadow_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
     lib.awsm_hip_read_shadow_map.argtypes = [C.c_void_p, C.c_void_p]
@@ -833,6 +863,33 @@ class HipDevice:
         flags = (AWSM_POST_SMAA if smaa else 0) | (AWSM_POST_BLOOM if bloom else 0) | (AWSM_POST_DOF if dof else 0)
         p = AwsmPostParams(C.sizeof(AwsmPostParams) if struct_size is None else struct_size, tonemapping, flags, 0)
         self._chk(self.lib.awsm_hip_post_pass(self.ctx, C.byref(p)), "post_pass")
+
+    def taa_defaults(self) -> AwsmTaa:
+        t = AwsmTaa()
+        self._chk(self.lib.awsm_hip_taa_defaults(C.byref(t)), "taa_defaults")
+        return t
+
+    def set_taa(self, on=True, struct_size: Optional[int] = None, **overrides):
+        """Temporal anti-aliasing in every later post_pass: the defaults with `overrides` (feedback, flags, jitter_ndc, reproject — column-major,
+        16 values); set_taa(None) turns it off and drops the history.  struct_size: what the record claims as its size (tests)."""
+        if not on:
+            return self._chk(self.lib.awsm_hip_set_taa(self.ctx, None), "set_taa")
+        t = self.taa_defaults().override(**overrides)
+        if struct_size is not None:
+            t.struct_size = struct_size
+        self._chk(self.lib.awsm_hip_set_taa(self.ctx, C.byref(t)), "set_taa")
+
+    def read_taa(self, layers: bool = True):
+        """Of the last post pass -> (the resolved image, uint16 [H, W, 4] f16 bits; the history position (sx, sy) per pixel in texel-index
+        units, float32 [H, W, 2]; whether the history was used, bool [H, W]).  layers=False: the image alone (the layers cost a kernel)."""
+        resolved = np.zeros((self.height, self.width, 4), dtype=np.uint16)
+        if not layers:
+            self._chk(self.lib.awsm_hip_read_taa(self.ctx, resolved.ctypes.data, None, None), "read_taa")
+            return resolved
+        xy = np.zeros((self.height, self.width, 2), dtype=np.float32)
+        used = np.zeros((self.height, self.width), dtype=np.uint8)
+        self._chk(self.lib.awsm_hip_read_taa(self.ctx, resolved.ctypes.data, xy.ctypes.data, used.ctypes.data), "read_taa")
+        return resolved, xy, used.astype(bool)
 
     def read_display(self) -> np.ndarray:
         out = np.zeros((self.height, self.width, 4), dtype=np.uint8)

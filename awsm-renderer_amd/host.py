@@ -89,6 +89,11 @@ class HostShadow(C.Structure):
         return self
 
 
+class HostTaa(C.Structure):
+    """AwsmHostTaa (awsm_host_set_taa): the weight of the current frame and the jitter amplitudes for a still and a moving camera."""
+    _fields_ = [("struct_size", C.c_uint32), ("feedback", C.c_float), ("strength_still", C.c_float), ("strength_moving", C.c_float)]
+
+
 class AnimationClip(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("n_keys", C.c_uint32), ("width", C.c_uint32),
                 ("times", C.POINTER(C.c_double)), ("values", F32P), ("in_tangents", F32P), ("out_tangents", F32P), ("duration", C.c_double)]
@@ -158,6 +163,7 @@ def load_library():
         "awsm_host_editor_grid_defaults": (C.c_int, [vp, vp]), "awsm_host_set_editor_grid": (C.c_int, [vp, vp]),
         "awsm_host_selection_defaults": (C.c_int, [vp, vp]), "awsm_host_set_selection": (C.c_int, [vp, vp, vp, C.c_uint32]),
         "awsm_host_ssao_defaults": (C.c_int, [vp, vp]), "awsm_host_set_ssao": (C.c_int, [vp, vp]),
+        "awsm_host_set_taa": (C.c_int, [vp, vp]), "awsm_host_taa_jitter": (C.c_int, [vp, C.c_uint32, C.c_int, F32P]),
         "awsm_host_shadow_defaults": (C.c_int, [vp, vp]), "awsm_host_set_shadow": (C.c_int, [vp, vp]),
         "awsm_host_shadow_camera": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
@@ -638,6 +644,24 @@ class Host:
         keys = (C.c_uint64 * max(1, len(mesh_keys)))(*[int(k) for k in mesh_keys])
         self._chk(self.lib.awsm_host_set_selection(self.h, C.byref(s), keys, len(mesh_keys)), "set_selection")
 
+    def set_taa(self, on: bool = True, **overrides):
+        """Temporal anti-aliasing in every later render(): the projection is jittered per frame and the post pass (set_post_processing first)
+        begins with the history resolve.  overrides: feedback (0.1), strength_still (0.8), strength_moving (0.2).  on=False turns it off."""
+        if not on:
+            return self._chk(self.lib.awsm_host_set_taa(self.h, None), "set_taa")
+        t = HostTaa(C.sizeof(HostTaa), 0.1, 0.8, 0.2)
+        for k, v in overrides.items():
+            if k not in ("feedback", "strength_still", "strength_moving"):
+                raise TypeError("AwsmHostTaa has no field %r (fields: feedback, strength_still, strength_moving)" % k)
+            setattr(t, k, float(v))
+        self._chk(self.lib.awsm_host_set_taa(self.h, C.byref(t)), "set_taa")
+
+    def taa_jitter(self, frame_count: int, moved: bool = False):
+        """The NDC offset (x, y) a render with that frame count jitters the projection by, as float32 (no device work)."""
+        out = np.zeros(2, dtype=np.float32)
+        self._chk(self.lib.awsm_host_taa_jitter(self.h, frame_count, int(moved), out.ctypes.data_as(F32P)), "taa_jitter")
+        return out
+
     def set_ssao(self, on: bool = True, **overrides):
         """Screen-space ambient occlusion in the opaque pass of every later render(): the backend's defaults with `overrides`
         (hip_backend.AwsmSsao's field names: radius, intensity, bias, strength).  on=False turns it off."""
@@ -1063,6 +1087,9 @@ class Renderer:
 
     def set_ssao(self, on: bool = True, **overrides):
         self.host.set_ssao(on, **overrides)
+
+    def set_taa(self, on: bool = True, **overrides):
+        self.host.set_taa(on, **overrides)
 
     def set_selection(self, mesh_keys=(), on: bool = True, **overrides):
         """Outline and box the meshes `mesh_keys` (keys from pick()) in every later render(); on=False for off."""

@@ -72,6 +72,7 @@ struct Backend {
     int (*set_editor_grid)(AwsmHipCtx*, const AwsmEditorGrid*) = nullptr;
     int (*ssao_defaults)(AwsmSsao*) = nullptr;                          // optional: screen-space ambient occlusion (awsm_host_set_ssao)
     int (*set_ssao)(AwsmHipCtx*, const AwsmSsao*) = nullptr;
+    int (*set_taa)(AwsmHipCtx*, const AwsmTaa*) = nullptr;              // optional: temporal anti-aliasing (awsm_host_set_taa)
     int (*selection_defaults)(AwsmSelection*) = nullptr;                // optional: the editor's selection overlay (awsm_host_set_selection)
     int (*set_selection)(AwsmHipCtx*, const AwsmSelection*, const uint32_t*, uint32_t, const AwsmSelectionBox*, uint32_t) = nullptr;
     int (*shadow_defaults)(AwsmShadow*) = nullptr;                      // optional: shadows (awsm_host_set_shadow)
@@ -267,6 +268,13 @@ struct AwsmHost {
     uint8_t shadow_block[512] = {};
     std::vector<AwsmDraw> shadow_casters;
     Mat4 cam_view = mat4_identity(), cam_proj = mat4_identity();
+    // ---- temporal anti-aliasing (awsm_host_set_taa): the record; the jittered block of the frame (camera_raw stays the unjittered
+    // one awsm_host_camera_update packed); the unjittered matrices of the last render with TAA on, as camera.rs keeps last_matrices ----
+    bool taa_on = false, taa_reset = true, taa_have_last = false;
+    AwsmHostTaa taa{(uint32_t)sizeof(AwsmHostTaa), 0.1f, 0.8f, 0.2f};
+    uint8_t taa_block[512] = {};
+    Mat4 taa_last_view = mat4_identity(), taa_last_proj = mat4_identity();
+    AwsmTaa taa_sent{};                        // what the last render handed the backend
     uint32_t frame_count = 0;
     uint32_t width = 0, height = 0;
     uint32_t msaa_sample_count = 0;   // AntiAliasing::msaa_sample_count: 0 = None, 4 = Some(4)
@@ -709,6 +717,7 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.set_editor_grid = reinterpret_cast<decltype(b.set_editor_grid)>(dlsym(b.dl, "awsm_hip_set_editor_grid"));
     b.ssao_defaults = reinterpret_cast<decltype(b.ssao_defaults)>(dlsym(b.dl, "awsm_hip_ssao_defaults"));      // optional (awsm_host_set_ssao)
     b.set_ssao = reinterpret_cast<decltype(b.set_ssao)>(dlsym(b.dl, "awsm_hip_set_ssao"));
+    b.set_taa = reinterpret_cast<decltype(b.set_taa)>(dlsym(b.dl, "awsm_hip_set_taa"));      // optional (awsm_host_set_taa)
     b.selection_defaults = reinterpret_cast<decltype(b.selection_defaults)>(dlsym(b.dl, "awsm_hip_selection_defaults"));      // optional (awsm_host_set_selection)
     b.set_selection = reinterpret_cast<decltype(b.set_selection)>(dlsym(b.dl, "awsm_hip_set_selection"));
     b.shadow_defaults = reinterpret_cast<decltype(b.shadow_defaults)>(dlsym(b.dl, "awsm_hip_shadow_defaults"));      // optional (awsm_host_set_shadow)
@@ -1396,6 +1405,7 @@ int awsm_host_resize(AwsmHost* h, uint32_t w, uint32_t ht) {
     int rc = h->be.resize(h->ctx, w, ht, h->msaa_sample_count);
     if (rc) return dev_fail(h, rc, "resize");
     h->width = w; h->height = ht;
+    h->taa_reset = true;      // the backend dropped its history; said once more with the next record
     return AWSM_OK;
 }
 // AwsmRenderer::set_anti_aliasing (anti_alias.rs:42-45): {msaa_sample_count None (0) or Some(4), mipmap}; other counts are
@@ -1607,6 +1617,96 @@ int awsm_host_update_transforms(AwsmHost* h) {   // transforms.rs:29-39 + meshes
 
 static int render_shadow_pass(AwsmHost* h);
 static int send_selection(AwsmHost* h);
+
+// ---- temporal anti-aliasing ----
+// camera.rs:263-274, in f32 as it stands there
+static float taa_halton(uint32_t index, uint32_t base) {
+    float result = 0.0f, f = 1.0f;
+    while (index > 0) {
+        f /= (float)base;
+        result += f * (float)(index % base);
+        index /= base;
+    }
+    return result;
+}
+// camera.rs:137-143: Halton(2, 3) - 0.5 over the frame size, scaled by the strength
+static void taa_jitter_ndc(uint32_t frame_count, float strength, float width, float height, float out[2]) {
+    const float jx = taa_halton(frame_count, 2) - 0.5f, jy = taa_halton(frame_count, 3) - 0.5f;
+    out[0] = (jx / width) * strength;
+    out[1] = (jy / height) * strength;
+}
+// camera.rs:122-129
+static bool taa_matrices_equal(const Mat4& a, const Mat4& b, float epsilon) {
+    const float* pa = &a.c[0].x; const float* pb = &b.c[0].x;
+    for (int i = 0; i < 16; i++) if (std::fabs(pa[i] - pb[i]) > epsilon) return false;
+    return true;
+}
+// glam's mul_mat4 and inverse (glam.hpp) with every operation in f64, on column-major arrays
+static void taa_mul64(const double a[16], const double b[16], double r[16]) {
+    for (int c = 0; c < 4; c++)
+        for (int i = 0; i < 4; i++) r[c * 4 + i] = ((a[i] * b[c * 4] + a[4 + i] * b[c * 4 + 1]) + a[8 + i] * b[c * 4 + 2]) + a[12 + i] * b[c * 4 + 3];
+}
+static void taa_inverse64(const double m[16], double out[16]) {
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m03 = m[3], m10 = m[4], m11 = m[5], m12 = m[6], m13 = m[7];
+    const double m20 = m[8], m21 = m[9], m22 = m[10], m23 = m[11], m30 = m[12], m31 = m[13], m32 = m[14], m33 = m[15];
+    const double coef00 = m22 * m33 - m32 * m23, coef02 = m12 * m33 - m32 * m13, coef03 = m12 * m23 - m22 * m13;
+    const double coef04 = m21 * m33 - m31 * m23, coef06 = m11 * m33 - m31 * m13, coef07 = m11 * m23 - m21 * m13;
+    const double coef08 = m21 * m32 - m31 * m22, coef10 = m11 * m32 - m31 * m12, coef11 = m11 * m22 - m21 * m12;
+    const double coef12 = m20 * m33 - m30 * m23, coef14 = m10 * m33 - m30 * m13, coef15 = m10 * m23 - m20 * m13;
+    const double coef16 = m20 * m32 - m30 * m22, coef18 = m10 * m32 - m30 * m12, coef19 = m10 * m22 - m20 * m12;
+    const double coef20 = m20 * m31 - m30 * m21, coef22 = m10 * m31 - m30 * m11, coef23 = m10 * m21 - m20 * m11;
+    const double fac[6][4] = {{coef00, coef00, coef02, coef03}, {coef04, coef04, coef06, coef07}, {coef08, coef08, coef10, coef11},
+                              {coef12, coef12, coef14, coef15}, {coef16, coef16, coef18, coef19}, {coef20, coef20, coef22, coef23}};
+    const double vec[4][4] = {{m10, m00, m00, m00}, {m11, m01, m01, m01}, {m12, m02, m02, m02}, {m13, m03, m03, m03}};
+    static const double sign_a[4] = {1.0, -1.0, 1.0, -1.0}, sign_b[4] = {-1.0, 1.0, -1.0, 1.0};
+    for (int i = 0; i < 4; i++) {
+        out[i] = ((vec[1][i] * fac[0][i] - vec[2][i] * fac[1][i]) + vec[3][i] * fac[2][i]) * sign_a[i];
+        out[4 + i] = ((vec[0][i] * fac[0][i] - vec[2][i] * fac[3][i]) + vec[3][i] * fac[4][i]) * sign_b[i];
+        out[8 + i] = ((vec[0][i] * fac[1][i] - vec[1][i] * fac[3][i]) + vec[3][i] * fac[5][i]) * sign_a[i];
+        out[12 + i] = ((vec[0][i] * fac[2][i] - vec[1][i] * fac[4][i]) + vec[2][i] * fac[5][i]) * sign_b[i];
+    }
+    const double dot1 = ((m[0] * out[0] + m[1] * out[4]) + m[2] * out[8]) + m[3] * out[12];
+    const double rcp_det = 1.0 / dot1;
+    for (int i = 0; i < 16; i++) out[i] = out[i] * rcp_det;
+}
+// R = view_proj_prev * inverse(view_proj_cur), both unjittered: composed in f64 from the f32 matrices, rounded once to f32
+static void taa_reproject(const Mat4& view_prev, const Mat4& proj_prev, const Mat4& view, const Mat4& proj, float out[16]) {
+    double vp[16], pp[16], v[16], p[16], vp_prev[16], vp_cur[16], inv_cur[16], r[16];
+    for (int i = 0; i < 16; i++) { vp[i] = (&view_prev.c[0].x)[i]; pp[i] = (&proj_prev.c[0].x)[i]; v[i] = (&view.c[0].x)[i]; p[i] = (&proj.c[0].x)[i]; }
+    taa_mul64(pp, vp, vp_prev);
+    taa_mul64(p, v, vp_cur);
+    taa_inverse64(vp_cur, inv_cur);
+    taa_mul64(vp_prev, inv_cur, r);
+    for (int i = 0; i < 16; i++) out[i] = (float)r[i];
+}
+static int taa_prepare_frame(AwsmHost* h) {
+    if (!h->post_on) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: awsm_host_set_taa is on and resolves in the post pass; call awsm_host_set_post_processing first (or awsm_host_set_taa(NULL))");
+    const Mat4& v = h->cam_view; const Mat4& p = h->cam_proj;
+    const bool same_bits = h->taa_have_last && memcmp(&v, &h->taa_last_view, 64) == 0 && memcmp(&p, &h->taa_last_proj, 64) == 0;
+    const bool moved = !h->taa_have_last || !taa_matrices_equal(h->taa_last_view, v, 1e-6f) || !taa_matrices_equal(h->taa_last_proj, p, 1e-6f);      // the first frame counts as moved
+    AwsmTaa& t = h->taa_sent;
+    t = AwsmTaa{};
+    t.struct_size = (uint32_t)sizeof(AwsmTaa);
+    t.feedback = h->taa.feedback;
+    taa_jitter_ndc(h->frame_count, moved ? h->taa.strength_moving : h->taa.strength_still, (float)h->width, (float)h->height, t.jitter_ndc);
+    const Mat4 identity = mat4_identity();
+    memcpy(t.reproject, &identity, 64);
+    if (h->taa_have_last && !same_bits) taa_reproject(h->taa_last_view, h->taa_last_proj, v, p, t.reproject);
+    bool finite = true;
+    for (float f : t.reproject) finite = finite && std::isfinite(f);
+    if (!finite) { memcpy(t.reproject, &identity, 64); h->taa_reset = true; }      // a singular camera: nothing to reproject with, this frame starts over
+    if (!h->taa_have_last) h->taa_reset = true;
+    t.flags = h->taa_reset ? AWSM_TAA_RESET : 0u;
+    h->taa_reset = false;
+    // proj' = translation(jitter) * proj, glam's mul_mat4; the block from it as from any projection
+    Mat4 jitter = mat4_identity();
+    jitter.c[3] = {t.jitter_ndc[0], t.jitter_ndc[1], 0.0f, 1.0f};
+    float pos[3];
+    memcpy(pos, h->camera_raw + 384, sizeof pos);      // the position as awsm_host_camera_update was given it
+    pack_camera_block(h, v, mat4_mul(jitter, p), pos, (float)h->width, (float)h->height, h->taa_block);
+    h->taa_last_view = v; h->taa_last_proj = p; h->taa_have_last = true;
+    return AWSM_OK;
+}
 int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render.rs:53-383 (hot path only)
     if (!h->width) return fail(h, AWSM_ERR_NOT_READY, "render before resize");
     h->shadow_rendered = false;
@@ -1617,6 +1717,7 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     h->upload_bytes = 0;
     h->frame_count += 1;   // render_textures.next_frame()
     int rc;
+    if (h->taa_on && (rc = taa_prepare_frame(h))) return rc;      // the jittered camera block and the record of this frame
     // ---- write_gpu, in the reference's order (render.rs:73-97) ----
     if (h->transforms_gpu_dirty) {
         bool d1 = true, d2 = true;
@@ -1673,9 +1774,9 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     if ((rc = flush_buffer(h, h->tr_data, AWSM_BUF_TRANSPARENCY_GEOM_DATA, h->tr_data_dirty))) return rc;   // meshes.rs:1268: between the visibility and the attribute buffers
     if ((rc = flush_buffer(h, h->attr_data, AWSM_BUF_ATTR_DATA, h->attr_data_dirty))) return rc;
     if ((rc = flush_buffer(h, h->attr_index, AWSM_BUF_ATTR_INDEX, h->attr_index_dirty))) return rc;
-    if (h->camera_dirty) {   // camera.rs:232-251
+    if (h->camera_dirty || h->taa_on) {   // camera.rs:232-251; with TAA on the block is another one every frame
         if (!h->camera_created) { if ((rc = h->be.buffer_create(h->ctx, AWSM_BUF_CAMERA, 512))) return dev_fail(h, rc, "buffer_create(camera)"); h->camera_created = true; }
-        if ((rc = h->be.buffer_write(h->ctx, AWSM_BUF_CAMERA, 0, h->camera_raw, 512))) return dev_fail(h, rc, "buffer_write(camera)");
+        if ((rc = h->be.buffer_write(h->ctx, AWSM_BUF_CAMERA, 0, h->taa_on ? h->taa_block : h->camera_raw, 512))) return dev_fail(h, rc, "buffer_write(camera)");
         h->upload_bytes += 512;
         h->camera_dirty = false;
     }
@@ -1705,6 +1806,7 @@ int awsm_host_render(AwsmHost* h, int sync, AwsmFrameStats* stats) {   // render
     // ---- the HUD transparent pass over the composite (render.rs:301-312) ----
     if (h->has_hud_meshes && (rc = h->be.hud_transparent_pass(h->ctx, h->last_hud_transparent_draws.data(), (uint32_t)h->last_hud_transparent_draws.size()))) return dev_fail(h, rc, "hud_transparent_pass");
     // ---- the effects + display passes (render.rs:339-356), when post-processing was turned on ----
+    if (h->taa_on && (rc = h->be.set_taa(h->ctx, &h->taa_sent))) return dev_fail(h, rc, "set_taa");
     if (h->post_on && (rc = h->be.post_pass(h->ctx, &h->post))) return dev_fail(h, rc, "post_pass");
     if (sync) { if ((rc = h->be.frame_end(h->ctx, stats))) return dev_fail(h, rc, "frame_end"); }   // gpu.submit_commands (render.rs:370)
     return AWSM_OK;
@@ -1913,6 +2015,35 @@ static int render_shadow_pass(AwsmHost* h) {
     const int rc = h->be.shadow_pass(h->ctx, &s, h->shadow_block, 512, h->shadow_casters.data(), (uint32_t)h->shadow_casters.size());
     if (rc) return dev_fail(h, rc, "shadow_pass");
     h->shadow_rendered = true;
+    return AWSM_OK;
+}
+
+// Temporal anti-aliasing: the host jitters the projection, composes the reprojection matrix and hands the backend a record per frame.
+int awsm_host_set_taa(AwsmHost* h, const AwsmHostTaa* taa) {
+    if (!h) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.set_taa) return fail(h, AWSM_ERR_UNSUPPORTED, "set_taa: the backend library has no %s", "awsm_hip_set_taa");
+    if (!taa) {
+        const int rc = h->be.set_taa(h->ctx, nullptr);
+        if (rc) return dev_fail(h, rc, "set_taa");
+        if (h->taa_on) h->camera_dirty = true;      // the unjittered block goes up again
+        h->taa_on = false; h->taa_have_last = false; h->taa_reset = true;
+        return AWSM_OK;
+    }
+    if (taa->struct_size < 4u || taa->struct_size > 4096u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_taa: AwsmHostTaa.struct_size = %u (set it to sizeof(AwsmHostTaa))", taa->struct_size);
+    AwsmHostTaa full{(uint32_t)sizeof(AwsmHostTaa), 0.1f, 0.8f, 0.2f};
+    const size_t known = std::min<size_t>(taa->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
+    memcpy((uint8_t*)&full + 4, (const uint8_t*)taa + 4, known - 4);
+    if (!std::isfinite(full.feedback) || !(full.feedback > 0.0f && full.feedback <= 1.0f)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_taa: feedback = %g (0 < feedback <= 1)", (double)full.feedback);
+    if (!std::isfinite(full.strength_still) || !std::isfinite(full.strength_moving)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_taa: a jitter strength is not finite");
+    if (!h->taa_on) { h->taa_have_last = false; h->taa_reset = true; }
+    h->taa = full;
+    h->taa_on = true;
+    return AWSM_OK;
+}
+int awsm_host_taa_jitter(AwsmHost* h, uint32_t frame_count, int moved, float out_ndc[2]) {
+    if (!h || !out_ndc) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->width) return fail(h, AWSM_ERR_NOT_READY, "taa_jitter before resize");
+    taa_jitter_ndc(frame_count, moved ? h->taa.strength_moving : h->taa.strength_still, (float)h->width, (float)h->height, out_ndc);
     return AWSM_OK;
 }
 

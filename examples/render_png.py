@@ -14,6 +14,8 @@ vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl th
 --shadow [LIGHT] casts shadows from one directional or spot light of the scene (--shadow-size N, --shadow-strength X): a depth map from the light,
 looked up per pixel and multiplied into the opaque image.
 --ssao darkens creases and contact lines: ambient occlusion estimated from the geometry pass's depth (--ssao-radius R in world units, --ssao-intensity I).
+--taa N renders N frames of the still view with the projection jittered per frame and resolves each into a history (temporal anti-aliasing, in front of the
+post pass: it implies the post pass) and writes the last; with --select the N frames are the selected ones.
 --grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
 --select X,Y (may be repeated) picks the mesh under each pixel of a first frame and renders again with those meshes selected: an outline around their
 visible pixels and a wire box around each one's world bounding box, dimmed where other geometry hides it.
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--ssao", action="store_true", help="screen-space ambient occlusion from the visibility depth, multiplied into the opaque image")
     ap.add_argument("--ssao-radius", type=float, default=None, metavar="R", help="with --ssao: the sampling radius in world units (default 0.5)")
     ap.add_argument("--ssao-intensity", type=float, default=None, metavar="I", help="with --ssao: the estimator's scale (default 1.0)")
+    ap.add_argument("--taa", type=int, default=0, metavar="N", help="temporal anti-aliasing: render N jittered frames of the still view, write the last (implies the post pass)")
     ap.add_argument("--shadow", nargs="?", const=-1, type=int, default=None, metavar="LIGHT",
                     help="shadows from one directional or spot light: an index into the scene's lights (default: the first directional light); not with --via-glb, "
                          "whose lights are the file's and have no index here")
@@ -91,7 +94,7 @@ def main():
         print(f"{a.hdr}: {info['width']}x{info['height']}{' (+Y)' if info['flipped_y'] else ''}, exposure {info['exposure']:g} -> skybox {a.hdr_size}^2 with its chain")
     if a.bake_ibl:
         r.host.env_bake_ibl(128, 6, 32)                                           # 128 64 32 16 8 4; sets the IBL mip counts
-    post = a.tonemap is not None or a.bloom or a.dof or a.smaa
+    post = a.tonemap is not None or a.bloom or a.dof or a.smaa or a.taa > 0
     if post:
         from awsm_renderer_amd.hip_backend import TONEMAP
         r.set_post_processing(TONEMAP[a.tonemap or "khronos"], bloom=a.bloom, dof=a.dof, smaa=a.smaa)
@@ -105,6 +108,8 @@ def main():
         if a.via_glb:
             ap.error("--shadow names a light by its index in the scene description; a scene read from a .glb keeps no such index (Host.set_shadow takes a light's key)")
         r.set_shadow(True if a.shadow < 0 else a.shadow, **{k: v for k, v in (("map_size", a.shadow_size), ("strength", a.shadow_strength)) if v is not None})
+    if a.taa > 0:
+        r.set_taa(True)
     stats = r.render(sync=True)
     picked = []
     if a.select:
@@ -119,13 +124,15 @@ def main():
         if picked:
             r.set_selection(picked)
             stats = r.render(sync=True)
+    for _ in range(a.taa - 1):      # the first of the N frames is the one above (or the selected one)
+        stats = r.render(sync=True)
     dev = HipDevice.from_ctx(r.host.device_ctx, W, H)
     if post:
         rgba = dev.read_display()
         r.close()
         from PIL import Image
         Image.fromarray(rgba[..., :3]).save(a.out)
-        print(f"{a.out}: {W}x{H}, post pass {a.tonemap or 'khronos'} bloom={a.bloom} dof={a.dof} smaa={a.smaa}, the device's RGBA8 display image")
+        print(f"{a.out}: {W}x{H}, post pass {a.tonemap or 'khronos'} bloom={a.bloom} dof={a.dof} smaa={a.smaa}{f' taa={a.taa} frames' if a.taa else ''}, the device's RGBA8 display image")
         return
     final = dev.read_composite() if stats["forward_triangles"] or a.grid or picked else dev.read_opaque()      # the image after the transparent pass, when the scene has one
     img = final.view(np.float16).astype(np.float32)[..., :3]

@@ -702,6 +702,43 @@ int awsm_hip_set_selection(AwsmHipCtx* ctx, const AwsmSelection* selection /* NU
 int awsm_hip_read_selection(AwsmHipCtx* ctx, uint8_t* selected_out, uint8_t* ring_out, float* box_alpha_out /* width x height each */,
                             float* edges_out /* n_boxes x 12 x 8 floats */);
 
+/* ---- temporal anti-aliasing (the "TAA" box of the reference's docs/ROADMAP.md, whose camera still carries the jitter).  State of
+ * awsm_hip_post_pass, as SSAO is state of the opaque pass: with it on, the post pass begins with k_taa_resolve.  Per pixel the resolve takes the depth
+ * of the WORLD key (the least of the four samples with MSAA, 1.0 where nothing was hit; never hud_depth), forms the pixel's unjittered NDC position
+ * n = pixel centre - jitter_ndc, q = reproject * (n, depth, 1) and the history position pixel + (q.xy / q.w - n) in texels, samples the last
+ * resolved image there bilinearly (taps clamped to the edge), clamps the sample per channel to the min / max of the current image's 3x3
+ * neighbourhood and writes history * (1 - feedback) + current * feedback, alpha from the current image.  "Current image" is what the post pass
+ * reads anyway: the composite when the frame had a transparent pass, else the opaque image.  The history is usable when there is one, q.w > 0 and
+ * the position lies within half a texel of the image; elsewhere the current texel is copied.  The resolved image is the next frame's history AND
+ * the source of everything behind it in the post pass (SMAA, bloom, DoF, tone map, display): two RGBA16F images per context, in ping-pong, the
+ * index advancing once per frame — a post pass awsm_hip_frame_end enqueues again for a replayed frame reads the same history and rewrites the same
+ * image.  The caller jitters its projection by jitter_ndc (proj' = translation(jitter_ndc, 0) * proj) and hands over
+ * reproject = view_proj_previous * inverse(view_proj_current), both unjittered; the host layer does both (awsm_host_set_taa).
+ *   defaults  feedback 0.1, flags 0, jitter_ndc (0, 0), reproject = identity; struct_size = sizeof(AwsmTaa).
+ *   set_taa   NULL turns it off and drops the history.  struct_size as for awsm_hip_set_ssao (at least its own four bytes, at most 4096; nothing
+ *             beyond it is read, fields it does not reach keep their defaults).  A non-finite value, feedback outside (0, 1] or an unknown flag:
+ *             AWSM_ERR_INVALID_ARGUMENT, and the state stays as it was.  Takes effect from the next awsm_hip_post_pass; a pass already enqueued
+ *             (AWSM_CFG_OVERLAP_FRAMES) and a replay keep the record they were given.  AWSM_TAA_RESET drops the history in front of the next
+ *             post pass and is cleared by it.
+ *   read_taa  of the last post pass: the resolved image (width x height x 4 f16), the history position (sx, sy) per pixel in texel-index units
+ *             (width x height x 2 f32) and whether the history was used (width x height bytes) — the last two computed once more from the frame's
+ *             keys and the record.  Any pointer may be NULL.  Synchronous.  AWSM_ERR_NOT_READY unless the last post pass resolved.
+ * The history is also dropped by awsm_hip_resize (a new size or MSAA mode) and by a frame a hand-off gate dropped.
+ * Limits: no per-object motion vectors — a moving or animated mesh is reprojected as if it stood still, and only the neighbourhood clamp bounds its
+ * ghost; transparent and HUD pixels are reprojected with the world depth behind them; no depth-based disocclusion test (the history's depth is not
+ * kept); no luma weighting; unsharded contexts only (the post pass refuses shards). ---- */
+#define AWSM_TAA_RESET 1u
+typedef struct AwsmTaa {
+    uint32_t struct_size;
+    float    feedback;        /* weight of the current image, 0 < feedback <= 1 */
+    uint32_t flags;           /* AWSM_TAA_RESET */
+    float    jitter_ndc[2];   /* what the frame's projection was translated by */
+    float    reproject[16];   /* column-major: unjittered NDC of this frame -> unjittered clip space of the previous one */
+} AwsmTaa;
+int awsm_hip_taa_defaults(AwsmTaa* out);
+int awsm_hip_set_taa(AwsmHipCtx* ctx, const AwsmTaa* taa /* NULL = off, history dropped */);
+int awsm_hip_read_taa(AwsmHipCtx* ctx, uint16_t* resolved_rgba16f_out, float* lookup_xy_out, uint8_t* used_out);
+
 #ifdef __cplusplus
 }
 #endif

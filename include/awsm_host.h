@@ -268,6 +268,31 @@ int awsm_host_set_selection(AwsmHost* h, const AwsmSelection* selection /* NULL 
  * so does its AWSM_ERR_UNSUPPORTED from the render of a sharded host. */
 int awsm_host_ssao_defaults(AwsmHost* h, AwsmSsao* out);
 int awsm_host_set_ssao(AwsmHost* h, const AwsmSsao* ssao /* NULL = off */);
+/* Temporal anti-aliasing (awsm_hip_set_taa in awsm_hip.h has the resolve's rules): with it on, every awsm_host_render
+ *   - jitters the projection as the reference's camera.rs does (Halton(2, 3) - 0.5 of the frame count the block carries, divided by the frame size
+ *     and scaled by strength_still when view and projection equal the last render's within 1e-6 per element, else by strength_moving; the first
+ *     frame counts as moved): proj' = translation(jitter_ndc) * proj, and uploads the 512-byte camera block packed from proj' — inv_proj,
+ *     view_proj, inv_view_proj and the frustum rays are the jittered ones — in place of the block awsm_host_camera_update packed, which the host
+ *     keeps: with TAA off again that block goes up as it was;
+ *   - composes reproject = view_proj_previous * inverse(view_proj_current) from the unjittered f32 matrices, every operation in f64, rounded once
+ *     to f32 — the exact identity when both matrices have the bits they had in the last render;
+ *   - hands the backend that record (awsm_hip_set_taa) in front of its post pass, with AWSM_TAA_RESET in the first record after this call, after
+ *     awsm_host_resize / awsm_host_set_anti_aliasing, and when the reprojection matrix is not finite.
+ * It resolves in the post pass: while TAA is on and awsm_host_set_post_processing is not, awsm_host_render returns AWSM_ERR_INVALID_ARGUMENT and
+ * says so.  NULL turns it off (the backend drops its history).  struct_size as for the backend's records: at least its own four bytes, at most
+ * 4096, fields it does not reach keep their defaults (feedback 0.1, strength_still 0.8, strength_moving 0.2 — the reference's amplitudes).
+ * AWSM_ERR_INVALID_ARGUMENT, the state unchanged, for a non-finite field or feedback outside (0, 1]; AWSM_ERR_UNSUPPORTED, naming the symbol, when
+ * the backend library lacks awsm_hip_set_taa.  The limits are the backend's: no motion vectors for moved or animated meshes, unsharded hosts only.
+ * awsm_host_taa_jitter returns the NDC offset a render with that frame count would use at the host's current size (moved != 0: the moving
+ * strength); no device work. */
+typedef struct AwsmHostTaa {
+    uint32_t struct_size;
+    float    feedback;          /* weight of the current frame, 0 < feedback <= 1 */
+    float    strength_still;    /* jitter amplitude in pixels (full range) for an unchanged camera */
+    float    strength_moving;   /* ... and for a camera that moved */
+} AwsmHostTaa;
+int awsm_host_set_taa(AwsmHost* h, const AwsmHostTaa* taa /* NULL = off */);
+int awsm_host_taa_jitter(AwsmHost* h, uint32_t frame_count, int moved, float out_ndc[2]);
 
 /* Shadows from one directional or spot light (awsm_hip_shadow_pass in awsm_hip.h has the device's rules).  While it is on,
  * awsm_host_render calls the backend's shadow pass after the geometry pass, every frame, with a camera it fits to the light and the casters it
