@@ -25,7 +25,17 @@ namespace {
 
 constexpr int kLeanWgsPerCu = 0;   // measured: the one-wavefront-per-strip grid wins once the geometry kernels fit beside it
 
-inline FrameBufs& FB(AwsmHipCtx* c) { return c->fb[c->slot]; }
+// A pass's device state, per frame slot / in the current slot.  The kind is the one way a pass is named: its FrameBufs carry it (FrameBufs::kind),
+// its draw list is c->lists[kind].
+inline FrameBufs* pass_slots(AwsmHipCtx* c, PassKind kind) {
+    FrameBufs* const sets[kPassKinds] = {c->fb, c->tr, c->hud, c->htr, c->shadow};      // in PassKind's order
+    return sets[kind];
+}
+inline FrameBufs& pass_bufs(AwsmHipCtx* c, PassKind kind) { return pass_slots(c, kind)[c->slot]; }
+inline FrameBufs& FB(AwsmHipCtx* c) { return c->fb[c->slot]; }      // = pass_bufs(c, kPassWorld)
+inline uint32_t samples_of(const AwsmHipCtx* c) { return c->msaa == 4 ? 4u : 1u; }
+// the context renders a part of the frame: a row range (awsm_hip_set_shard_rows) or every n-th tile row (awsm_hip_set_shard_bands)
+inline bool is_sharded(const AwsmHipCtx* c) { return c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height)); }
 inline hipStream_t shade_stream_of(AwsmHipCtx* c) { return c->overlap ? c->shade_streams[c->slot] : c->stream; }
 inline int n_slots(const AwsmHipCtx* c) { return c->overlap ? kSlots : 1; }
 inline int prev_slot(const AwsmHipCtx* c) { return (c->slot + kSlots - 1) % kSlots; }
@@ -227,8 +237,36 @@ int sync_scene(AwsmHipCtx* c) {
     return AWSM_OK;
 }
 
-void fill_frame(AwsmHipCtx* c, FrameDev* f) {
+// The per-pass members of a frame — whose draw list, transformed vertices, setup records, tile tables, lists, counters and keys the kernels of a
+// pass work on — from that pass's FrameBufs.  The ONE place they are set: a new per-pass buffer is added here.
+void bind_pass(FrameDev& f, const FrameBufs& b) {
+    f.bin_capacity = b.bin_capacity;
+    f.draws = (const DrawDev*)b.draws_dev.ptr;
+    f.clip = (float4*)b.clip.ptr; f.nrm = (float4*)b.nrm.ptr; f.tan = (float4*)b.tan.ptr;
+    f.tri_info = (uint32_t*)b.tri_flags.ptr;
+    f.tri_rec = (TriRec*)b.tri_rec.ptr;
+    f.tile_count = (uint32_t*)b.tile_count.ptr; f.tile_offset = (uint32_t*)b.tile_offset.ptr;
+    f.tile_cursor = (uint32_t*)b.tile_cursor.ptr; f.bin_list = (uint32_t*)b.bin_list.ptr;
+    f.tile_order = (uint32_t*)b.tile_order.ptr;
+    f.scan_tmp = (uint32_t*)b.scan_tmp.ptr;
+    f.tile_split = (uint32_t*)b.tile_split.ptr; f.raster_scratch = (unsigned long long*)b.raster_scratch.ptr;
+    f.raster_extra_cap = b.raster_extra_cap; f.raster_slot_cap = b.raster_slot_cap;
+    f.big_list = (uint32_t*)b.big_list.ptr;
+    f.counters = (uint32_t*)b.counters.ptr;
+    f.vis = (unsigned long long*)b.vis.ptr;
+}
+
+// Which frame a FrameDev describes.  hud_keys: the frame has hud geometry and the pass looks at its keys (the opaque pass leaves those pixels
+// cleared); merged: the hud draws follow the world's in one rank space (AwsmHipCtx::hud_merged) — with hud_keys the pass sees the merged keys
+// and the combined list, and in any case the lean route's 32-bit offsets must hold for both passes' triangles.
+struct FrameView { bool hud_keys, merged; };
+inline FrameView world_view() { return {false, false}; }      // the world pass's own: no merged hud keys, no hud ranks
+inline FrameView frame_view(const AwsmHipCtx* c) { return {c->hud_geometry_done, c->hud_merged}; }      // the frame as the passes behind the HUD geometry pass see it
+
+void fill_frame(AwsmHipCtx* c, FrameDev* f, FrameView view) {
     memset(f, 0, sizeof *f);
+    const PassList& world = c->lists[kPassWorld];
+    const PassList& hud = c->lists[kPassHud];
     uint32_t y0, y1;
     shard(c, &y0, &y1);
     f->width = c->width; f->height = c->height; f->y0 = y0; f->y1 = y1; f->sy0 = y0; f->sy1 = y1;
@@ -245,17 +283,14 @@ void fill_frame(AwsmHipCtx* c, FrameDev* f) {
         f->tile_row0 = c->band_r;
         f->tiles_y = c->band_r < rows_full ? (rows_full - c->band_r + c->band_n - 1) / c->band_n : 0;
     }
-    f->n_draws = (uint32_t)c->draws_host.size();
-    f->total_tris = c->total_tris; f->total_verts = c->total_verts;
-    f->bin_capacity = FB(c).bin_capacity;
-    f->draws = (const DrawDev*)FB(c).draws_dev.ptr;
+    f->n_draws = (uint32_t)world.draws.size();
+    f->total_tris = world.total_tris; f->total_verts = 3u * world.total_tris;
+    bind_pass(*f, FB(c));
     f->draw_shade = (DrawShadeDev*)FB(c).draw_shade.ptr;
     f->tex_slots = (TexSlotDev*)FB(c).tex_slots.ptr;
     f->draw_mat = (DrawMatDev*)FB(c).draw_mat.ptr;
-    f->clip = (float4*)FB(c).clip.ptr; f->nrm = (float4*)FB(c).nrm.ptr; f->tan = (float4*)FB(c).tan.ptr;
-    f->tri_info = (uint32_t*)FB(c).tri_flags.ptr;
     // The lean opaque route (k_shade_lean): frames whose per-pixel key / per-triangle / per-vertex / attribute byte offsets fit 32 bits
-    const bool lean_ok = !(c->flags & AWSM_CFG_GENERAL_SHADE_ONLY) && (uint64_t)c->width * c->height * (c->msaa == 4 ? 32u : 8u) < (1ull << 32) && (c->msaa == 0 || (c->msaa_edge_bits[c->slot].ptr && c->msaa_cells[c->slot].ptr)) && FB(c).tri_shade.ptr && FB(c).draw_lean.ptr && c->shade_todo[c->slot].ptr && ((uint64_t)c->total_tris + (c->hud_merged ? c->hud_total_tris : 0u)) * kTriRecBytes < (1ull << 32) &&
+    const bool lean_ok = !(c->flags & AWSM_CFG_GENERAL_SHADE_ONLY) && (uint64_t)c->width * c->height * (c->msaa == 4 ? 32u : 8u) < (1ull << 32) && (c->msaa == 0 || (c->msaa_edge_bits[c->slot].ptr && c->msaa_cells[c->slot].ptr)) && FB(c).tri_shade.ptr && FB(c).draw_lean.ptr && c->shade_todo[c->slot].ptr && ((uint64_t)world.total_tris + (view.merged ? hud.total_tris : 0u)) * kTriRecBytes < (1ull << 32) &&
                          c->bufs[AWSM_BUF_ATTR_DATA].size < (1ull << 32) - 64;
     f->tri_shade = lean_ok ? (uint4*)FB(c).tri_shade.ptr : nullptr;
     f->attr_data_bytes = (uint32_t)std::min<size_t>(c->bufs[AWSM_BUF_ATTR_DATA].size, 0xFFFFFFFFu);
@@ -264,15 +299,6 @@ void fill_frame(AwsmHipCtx* c, FrameDev* f) {
     f->shade_todo_cap = f->shade_todo ? (uint32_t)(c->shade_todo[c->slot].size / 4 - 4 - 1024) : 0u;
     f->lean_next = f->shade_todo ? f->shade_todo + 4 + f->shade_todo_cap : nullptr;
     f->lean_grid = c->lean_grid;
-    f->tri_rec = (TriRec*)FB(c).tri_rec.ptr;
-    f->tile_count = (uint32_t*)FB(c).tile_count.ptr; f->tile_offset = (uint32_t*)FB(c).tile_offset.ptr;
-    f->tile_cursor = (uint32_t*)FB(c).tile_cursor.ptr; f->bin_list = (uint32_t*)FB(c).bin_list.ptr;
-    f->tile_order = (uint32_t*)FB(c).tile_order.ptr;
-    f->scan_tmp = (uint32_t*)FB(c).scan_tmp.ptr;
-    f->tile_split = (uint32_t*)FB(c).tile_split.ptr; f->raster_scratch = (unsigned long long*)FB(c).raster_scratch.ptr;
-    f->raster_extra_cap = FB(c).raster_extra_cap; f->raster_slot_cap = FB(c).raster_slot_cap;
-    f->big_list = (uint32_t*)FB(c).big_list.ptr;
-    f->counters = (uint32_t*)FB(c).counters.ptr;
 #ifdef AWSM_STAMP
     {
         static unsigned long long* stamps = nullptr;
@@ -285,7 +311,6 @@ void fill_frame(AwsmHipCtx* c, FrameDev* f) {
     f->poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
     f->host_bin_status = c->counters_host + 16 + 2 * c->slot;
     f->frame_serial = c->frame_serial;
-    f->vis = (unsigned long long*)FB(c).vis.ptr;
     f->camera = (const uint8_t*)FB(c).camera.ptr;      // the snapshot the geometry pass took: every kernel of a frame, lean or general, sees the camera the frame was submitted with
     f->camera_snap = nullptr; f->camera_snap_words = 0;
     memcpy(f->pix2view, FB(c).pix2view, sizeof f->pix2view); memcpy(f->view_rot, FB(c).view_rot, sizeof f->view_rot); memcpy(f->cam_pos, FB(c).cam_pos, sizeof f->cam_pos);
@@ -295,11 +320,11 @@ void fill_frame(AwsmHipCtx* c, FrameDev* f) {
     f->msaa_edges = (uint32_t*)c->msaa_edges[c->slot].ptr;
     f->msaa_edge_bits = (lean_ok && c->msaa == 4) ? (unsigned long long*)c->msaa_edge_bits[c->slot].ptr : nullptr;
     f->msaa_cells = (uint2*)c->msaa_cells[c->slot].ptr;
-    f->hud_vis = c->hud_geometry_done ? (const unsigned long long*)c->hud[c->slot].vis.ptr : nullptr;
+    f->hud_vis = view.hud_keys ? (const unsigned long long*)c->hud[c->slot].vis.ptr : nullptr;
     f->hud_draws = (const DrawDev*)c->hud[c->slot].draws_dev.ptr; f->hud_tri_info = (const uint32_t*)c->hud[c->slot].tri_flags.ptr;
-    if (c->hud_geometry_done && c->hud_merged) {      // one rank space: the hud draws behind the world's; the opaque pass sees the merged keys
+    if (view.hud_keys && view.merged) {      // one rank space: the hud draws behind the world's; the opaque pass sees the merged keys
         f->n_draws = (uint32_t)c->hud_combined.size();
-        f->total_tris = c->total_tris + c->hud_total_tris; f->total_verts = 3u * f->total_tris;
+        f->total_tris = world.total_tris + hud.total_tris; f->total_verts = 3u * f->total_tris;
         f->vis = (unsigned long long*)c->merged_vis[c->slot].ptr;
         f->hud_draws = f->draws; f->hud_tri_info = f->tri_info;      // (the picker: hud keys name global ranks)
     }
@@ -372,16 +397,32 @@ void fill_geometry_cache(AwsmHipCtx* c, FrameDev* f, bool replay) {
 }
 
 
+// The binning chain of a pass: count -> big(0) -> scan -> fill -> big(1).  A pass without triangles only scans (k_bin_scan clears tile_cursor and
+// orders the tiles for the raster / forward kernels).  Whether the chain runs at all, and what stands around it, is the caller's business.
+inline void enqueue_binning(const FrameDev& f, bool has_tris, hipStream_t s) {
+    if (has_tris) { awsm_launch_bin_count(&f, s); awsm_launch_bin_big(&f, 0, s); }
+    awsm_launch_bin_scan(&f, s);
+    if (has_tris) { awsm_launch_bin_fill(&f, s); awsm_launch_bin_big(&f, 1, s); }
+}
+// A pass without triangles launches no k_deform_transform, which otherwise clears counters + tile_count (k_bin_scan clears tile_cursor)
+int clear_empty_pass(AwsmHipCtx* c, const FrameBufs& b, uint32_t n_tiles, hipStream_t s) {
+    HIPCHK(c, hipMemsetAsync(b.counters.ptr, 0, kCtrWords * sizeof(uint32_t), s));
+    HIPCHK(c, hipMemsetAsync((uint32_t*)b.counters.ptr + 12, 0, 2 * sizeof(uint32_t), s));
+    if (n_tiles) HIPCHK(c, hipMemsetAsync(b.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), s));
+    return AWSM_OK;
+}
+
 // replay: the frame's geometry pass is enqueued again (a bin list that overflowed, world arrays that moved under the hud pass): the camera snapshot the first
 // enqueue took stays — pix2view / cam_pos were composed from that camera at awsm_hip_geometry_pass — and the geometry cache is not consulted.
 int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
     HostTrace ht(c->frame_serial);
+    const PassList& world = c->lists[kPassWorld];
     FrameDev f;
-    { const bool hd = c->hud_geometry_done, hm = c->hud_merged; c->hud_geometry_done = false; c->hud_merged = false; fill_frame(c, &f); c->hud_geometry_done = hd; c->hud_merged = hm; }      // the world pass's own view (no merged hud keys, no hud ranks)
+    fill_frame(c, &f, world_view());
     fill_geometry_cache(c, &f, replay);
     f.block_draw = FB(c).block_map_valid ? (const uint32_t*)FB(c).block_map.ptr : nullptr;
     // AwsmFrameStats.geometry_cache_blocks: marked only when stage times are asked for too (a plain store per workgroup, counted by frame_end on the host)
-    f.cache_mark = (c->stage_timers && FB(c).cache_mark.size >= (size_t)c->n_blocks * 4) ? (uint32_t*)FB(c).cache_mark.ptr : nullptr;
+    f.cache_mark = (c->stage_timers && FB(c).cache_mark.size >= (size_t)world.n_blocks * 4) ? (uint32_t*)FB(c).cache_mark.ptr : nullptr;
     const uint32_t n_tiles = f.tiles_x * f.tiles_y;
     int rc = sync_scene(c);
     if (rc) return rc;
@@ -394,7 +435,7 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
     // (copied by k_deform_transform when the frame has geometry: a 512-byte hipMemcpyAsync costs the stream 18 us of gap + copy)
     if (c->bufs[AWSM_BUF_CAMERA].ptr && !replay) {
         const size_t cam_bytes = std::min<size_t>(512, c->bufs[AWSM_BUF_CAMERA].size);
-        if (c->total_tris && n_tiles) { f.camera_snap = (uint32_t*)FB(c).camera.ptr; f.camera_snap_words = (uint32_t)(cam_bytes / 4); }
+        if (world.total_tris && n_tiles) { f.camera_snap = (uint32_t*)FB(c).camera.ptr; f.camera_snap_words = (uint32_t)(cam_bytes / 4); }
         else HIPCHK(c, hipMemcpyAsync(FB(c).camera.ptr, c->bufs[AWSM_BUF_CAMERA].ptr, cam_bytes, hipMemcpyDeviceToDevice, c->stream));
     }
     if (c->overlap) {
@@ -405,12 +446,8 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
         c->geom_write_seq[c->slot] = c->write_seq;
     }
     ht.mark("geometry: slot wait + upload event");
-    const bool has_geometry = c->total_tris && n_tiles;
-    if (!has_geometry) {   // otherwise k_deform_transform clears counters + tile_count and k_bin_scan clears tile_cursor
-        HIPCHK(c, hipMemsetAsync(FB(c).counters.ptr, 0, 8 * sizeof(uint32_t), c->stream));
-        HIPCHK(c, hipMemsetAsync((uint32_t*)FB(c).counters.ptr + 12, 0, 2 * sizeof(uint32_t), c->stream));
-        if (n_tiles) HIPCHK(c, hipMemsetAsync(FB(c).tile_count.ptr, 0, n_tiles * sizeof(uint32_t), c->stream));
-    }
+    const bool has_geometry = world.total_tris && n_tiles;
+    if (!has_geometry && (rc = clear_empty_pass(c, FB(c), n_tiles, c->stream))) return rc;
     if (c->trace_dev) awsm_launch_handoff_signal(nullptr, 0u, trace_slot(c, 0), c->stream);
     if ((rc = record(c, EV_START))) return rc;
     // Measurement aid (tools/knockout.sh; static camera only): from the ninth frame on leave out the raster (4), the binning launches as well (6) or
@@ -422,14 +459,10 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
 #else
     const int knockout = 0;
 #endif
-    if (c->total_tris && n_tiles && !(knockout & 1)) awsm_launch_transform(c->scene_dev, &f, c->n_blocks, c->stream);
+    if (has_geometry && !(knockout & 1)) awsm_launch_transform(c->scene_dev, &f, world.n_blocks, c->stream);
     if ((rc = record(c, EV_TRANSFORM))) return rc;
     ht.mark("geometry: transform launch");
-    if (n_tiles && !(knockout & 2)) {
-        if (c->total_tris) { awsm_launch_bin_count(&f, c->stream); awsm_launch_bin_big(&f, 0, c->stream); }
-        awsm_launch_bin_scan(&f, c->stream);
-        if (c->total_tris) { awsm_launch_bin_fill(&f, c->stream); awsm_launch_bin_big(&f, 1, c->stream); }
-    }
+    if (n_tiles && !(knockout & 2)) enqueue_binning(f, world.total_tris != 0, c->stream);
     if ((rc = record(c, EV_BIN))) return rc;
     ht.mark("geometry: bin launches");
     if (n_tiles && !(knockout & 4)) awsm_launch_raster(&f, c->stream);
@@ -439,7 +472,7 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
     {   // the slot's arrays now hold this list's world positions / N / T / per-triangle words (all of them: hits kept theirs, misses were recomputed)
         FrameBufs& b = FB(c);
         b.cache_valid = has_geometry && !(knockout & 1) && b.wcache.ptr != nullptr;
-        b.cached_n_draws = (uint32_t)c->draws_host.size(); b.cached_is_prev = false;
+        b.cached_n_draws = (uint32_t)world.draws.size(); b.cached_is_prev = false;
         b.cache_had_tri_shade = f.tri_shade != nullptr;
         b.cache_seq = c->write_seq; b.cache_serial = c->frame_serial;
         // entries every slot has seen are of no further use
@@ -453,7 +486,7 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
 int enqueue_opaque(AwsmHipCtx* c) {
     HostTrace ht(c->frame_serial);
     FrameDev f;
-    fill_frame(c, &f);
+    fill_frame(c, &f, frame_view(c));
     f.has_opaque = c->last_opaque.has_opaque;
     f.mipmap = c->last_opaque.mipmap;
     f.aniso = (c->flags & AWSM_CFG_ANISOTROPIC) ? 1u : 0u;
@@ -542,7 +575,7 @@ int enqueue_opaque(AwsmHipCtx* c) {
         a.visibility = (float*)c->shadow_layers[c->slot].ptr; a.multiplier = a.visibility + px;
         a.out16 = (uint2*)f.out_rgba16f; a.out32 = (float4*)f.out_rgba32f;
         a.poison = f.poison; a.frame_serial = f.frame_serial;
-        awsm_launch_shadow_resolve(&a, c->msaa == 4 ? 4u : 1u, ss);
+        awsm_launch_shadow_resolve(&a, samples_of(c), ss);
     }
     // screen-space ambient occlusion, with the record this pass was submitted with: behind the shading kernels — it modulates their image in place —
     // and in front of the shade-done signal below: it reads the slot's keys, which the slot's next geometry pass overwrites.  A replay
@@ -558,7 +591,7 @@ int enqueue_opaque(AwsmHipCtx* c) {
         sa.ao_raw = (float*)c->ssao_layers[c->slot].ptr; sa.ao_smoothed = sa.ao_raw + px; sa.view_z = sa.ao_raw + 2 * px;
         sa.out16 = (uint2*)f.out_rgba16f; sa.out32 = (float4*)f.out_rgba32f;
         sa.poison = f.poison; sa.frame_serial = f.frame_serial;
-        awsm_launch_ssao(&sa, c->msaa == 4 ? 4u : 1u, ss);
+        awsm_launch_ssao(&sa, samples_of(c), ss);
     }
     if ((rc = record(c, EV_SHADE, ss))) return rc;      // behind the SSAO kernels: with SSAO on AwsmFrameStats.ms_shade is the shading kernels and the occlusion
     ht.mark("opaque: shade launches");
@@ -569,34 +602,23 @@ int enqueue_opaque(AwsmHipCtx* c) {
     return AWSM_OK;
 }
 
-inline FrameBufs& TR(AwsmHipCtx* c) { return (c->hud_transparent ? c->htr : c->tr)[c->slot]; }
-
-// The transparent pass's frame: its own draws / vertices / setup records / bins; the geometry pass's visibility keys for the depth
-// test; the opaque image as blit source and transmission background; the composite image as target.
-void fill_frame_forward(AwsmHipCtx* c, FrameDev* f) {
-    fill_frame(c, f);
-    FrameBufs& t = TR(c);
-    const int which = c->hud_transparent ? 1 : 0;
+// The frame of a transparent pass (kind: the world's or the HUD's): its own draws / vertices / setup records / bins; the geometry pass's
+// visibility keys for the depth test; the opaque image as blit source and transmission background; the composite image as target.
+void fill_frame_forward(AwsmHipCtx* c, FrameDev* f, PassKind kind) {
+    fill_frame(c, f, frame_view(c));
+    const FrameBufs& t = pass_bufs(c, kind);
+    const PassList& list = c->lists[kind];
+    bind_pass(*f, t);
     f->vis = (unsigned long long*)FB(c).vis.ptr;      // the WORLD's depth (render.rs:224-297), whatever the opaque pass read
-    f->n_draws = (uint32_t)c->tr_draws_host[which].size();
-    f->total_tris = c->tr_total_tris[which]; f->total_verts = 3u * c->tr_total_tris[which];
-    f->bin_capacity = t.bin_capacity;
-    f->draws = (const DrawDev*)t.draws_dev.ptr;
+    f->n_draws = (uint32_t)list.draws.size();
+    f->total_tris = list.total_tris; f->total_verts = 3u * list.total_tris;
     f->draw_shade = (DrawShadeDev*)t.draw_shade.ptr;
     f->tex_slots = (TexSlotDev*)t.tex_slots.ptr;
     f->draw_mat = (DrawMatDev*)t.draw_mat.ptr;
-    f->clip = (float4*)t.clip.ptr; f->nrm = (float4*)t.nrm.ptr; f->tan = (float4*)t.tan.ptr; f->wpos = (float4*)t.wpos.ptr;
-    f->tri_info = (uint32_t*)t.tri_flags.ptr;
+    f->wpos = (float4*)t.wpos.ptr;
     f->tri_shade = nullptr; f->draw_lean = nullptr; f->shade_todo = nullptr; f->shade_todo_cap = 0; f->lean_next = nullptr; f->lean_grid = 0;     // the opaque pass's lean route only
-    f->tri_rec = (TriRec*)t.tri_rec.ptr;
-    f->tile_count = (uint32_t*)t.tile_count.ptr; f->tile_offset = (uint32_t*)t.tile_offset.ptr;
-    f->tile_cursor = (uint32_t*)t.tile_cursor.ptr; f->bin_list = (uint32_t*)t.bin_list.ptr;
-    f->tile_order = (uint32_t*)t.tile_order.ptr;
-    f->scan_tmp = (uint32_t*)t.scan_tmp.ptr;
-    f->tile_split = (uint32_t*)t.tile_split.ptr; f->raster_scratch = nullptr;      // the transparent pass has its own tile kernel: nothing is split
+    f->raster_scratch = nullptr;      // the transparent pass has its own tile kernel: nothing is split
     f->raster_extra_cap = 0; f->raster_slot_cap = 0;
-    f->big_list = (uint32_t*)t.big_list.ptr;
-    f->counters = (uint32_t*)t.counters.ptr;
     f->opaque_rgba16f = c->opaque_src ? (const uint16_t*)c->opaque_src : f->out_rgba16f;
     f->out_compact = 0;                    // the composite is addressed by absolute row
     f->frag_rec = (uint4*)t.frag_rec.ptr; f->frag_color = (float4*)t.frag_color.ptr; f->frag_first = (uint32_t*)t.frag_first.ptr; f->frag_cap = t.frag_cap;
@@ -605,7 +627,7 @@ void fill_frame_forward(AwsmHipCtx* c, FrameDev* f) {
     f->has_opaque = c->last_opaque.has_opaque;
     f->mipmap = c->last_opaque.mipmap;
     f->aniso = (c->flags & AWSM_CFG_ANISOTROPIC) ? 1u : 0u;
-    if (c->hud_transparent) {      // the HUD pass: depth starts cleared, the colours it blends over are the composite's own (in place, a pixel per thread)
+    if (kind == kPassHudTransparent) {      // the HUD pass: depth starts cleared, the colours it blends over are the composite's own (in place, a pixel per thread)
         f->hud_pass = 1;
         f->opaque_rgba16f = f->out_rgba16f;
     }
@@ -615,8 +637,8 @@ void fill_frame_forward(AwsmHipCtx* c, FrameDev* f) {
 // hud draws share the world's rank space the world's draws come first), the camera snapshot, the slot's tables.
 void fill_selection(AwsmHipCtx* c, const AwsmHipCtx::SelectionState& st, SelectionDev* a) {
     memset(a, 0, sizeof *a);
-    a->width = c->width; a->height = c->height; a->msaa = c->msaa == 4 ? 4u : 1u;
-    a->n_draws = (uint32_t)c->draws_host.size(); a->total_tris = c->total_tris;
+    a->width = c->width; a->height = c->height; a->msaa = samples_of(c);
+    a->n_draws = (uint32_t)c->lists[kPassWorld].draws.size(); a->total_tris = c->lists[kPassWorld].total_tris;
     a->n_keys = (uint32_t)(st.keys.size() / 2); a->n_boxes = (uint32_t)(st.boxes.size() / 6);
     a->flags = st.flags; a->radius = st.radius;
     memcpy(a->outline_color, st.outline_color, sizeof a->outline_color); memcpy(a->box_color, st.box_color, sizeof a->box_color);
@@ -633,9 +655,10 @@ void fill_selection(AwsmHipCtx* c, const AwsmHipCtx::SelectionState& st, Selecti
     if (a->n_boxes) memcpy(a->boxes, st.boxes.data(), st.boxes.size() * 4);
 }
 
-int enqueue_transparent(AwsmHipCtx* c) {
+int enqueue_transparent(AwsmHipCtx* c, PassKind kind) {
+    const bool hud = kind == kPassHudTransparent;
     FrameDev f;
-    fill_frame_forward(c, &f);
+    fill_frame_forward(c, &f, kind);
     const uint32_t n_tiles = f.tiles_x * f.tiles_y;
     int rc = sync_scene(c);
     if (rc) return rc;
@@ -645,21 +668,17 @@ int enqueue_transparent(AwsmHipCtx* c) {
     if ((rc = record(c, EV_FWD_BEGIN, ss))) return rc;
     const bool has_geometry = f.total_tris && n_tiles;
     if (!has_geometry) {
-        HIPCHK(c, hipMemsetAsync(TR(c).counters.ptr, 0, 8 * sizeof(uint32_t), ss));
-        HIPCHK(c, hipMemsetAsync((uint32_t*)TR(c).counters.ptr + 12, 0, 2 * sizeof(uint32_t), ss));
-        if (n_tiles) HIPCHK(c, hipMemsetAsync(TR(c).tile_count.ptr, 0, n_tiles * sizeof(uint32_t), ss));
+        if ((rc = clear_empty_pass(c, pass_bufs(c, kind), n_tiles, ss))) return rc;
     } else {
         awsm_launch_resolve_draws(c->scene_dev, &f, ss);      // first: the transform tags each triangle with its draw's alpha mode
-        awsm_launch_transform_forward(c->scene_dev, &f, c->tr_n_blocks[c->hud_transparent ? 1 : 0], ss);
+        awsm_launch_transform_forward(c->scene_dev, &f, c->lists[kind].n_blocks, ss);
     }
     if (n_tiles) {
-        if (f.total_tris) { awsm_launch_bin_count(&f, ss); awsm_launch_bin_big(&f, 0, ss); }
-        awsm_launch_bin_scan(&f, ss);
-        if (f.total_tris) { awsm_launch_bin_fill(&f, ss); awsm_launch_bin_big(&f, 1, ss); }
+        enqueue_binning(f, f.total_tris != 0, ss);
         // the editor's ground grid: the world pass only, with the record this pass was submitted with and the frame's camera snapshot
         EditorGridDev grid;
         const AwsmHipCtx::GridState& gs = c->grid_pass[c->slot];
-        const bool with_grid = gs.on && !c->hud_transparent;
+        const bool with_grid = gs.on && !hud;
         if (with_grid) { grid.camera = f.camera; memcpy(grid.p, gs.p, sizeof grid.p); }
         awsm_launch_forward(c->scene_dev, &f, with_grid ? &grid : nullptr, ss);
         // the editor's selection overlay, with the record this pass was submitted with: the world pass only, behind the kernels that leave the
@@ -667,7 +686,7 @@ int enqueue_transparent(AwsmHipCtx* c) {
         // which the slot's next geometry pass overwrites (the ordering argument of the occlusion kernels in enqueue_opaque).  A replay
         // (awsm_hip_frame_end) comes through here again behind a blit that wrote every pixel anew, so the overlay is blended once.
         const AwsmHipCtx::SelectionState& sl = c->sel_pass[c->slot];
-        if (sl.on && !c->hud_transparent) {
+        if (sl.on && !hud) {
             SelectionDev sd;
             fill_selection(c, sl, &sd);
             sd.out16 = (uint2*)f.out_rgba16f; sd.out32 = (float4*)f.out_rgba32f;
@@ -743,7 +762,7 @@ int build_draw_list(AwsmHipCtx* c, const char* pass, const AwsmDraw* draws, uint
 struct PassDims { uint32_t w, h, samples; };
 inline PassDims dims_of(const AwsmHipCtx* c, const FrameBufs& b) {
     if (b.kind == kPassShadow) { const uint32_t S = c->shadow_pass[b.slot].p.map_size; return {S, S, 1u}; }
-    return {c->width, c->height, c->msaa == 4u ? 4u : 1u};
+    return {c->width, c->height, samples_of(c)};
 }
 
 int reserve_raster_items(AwsmHipCtx* c, FrameBufs& b, bool forward, PassDims dm) {
@@ -809,8 +828,7 @@ int ensure_pass_capacity(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>
         const size_t tri_cap = std::max<size_t>(std::min<size_t>((size_t)total_tris + total_tris / 4 + 4096, std::max<size_t>(tri_bound, total_tris)), b.tri_cap);
         const size_t draw_cap = std::max<size_t>(draws_host.size() + draws_host.size() / 4 + 64, b.draw_cap);
         const bool shadow = b.kind == kPassShadow;      // (the light's pass: this slot's alone — the other slot's map may have another size)
-        FrameBufs* const sets[] = {c->fb, c->tr, c->hud, c->htr, c->shadow};      // in PassKind's order
-        FrameBufs* set = sets[b.kind];
+        FrameBufs* const set = pass_slots(c, b.kind);
         for (int sl = 0; sl < (shadow ? 1 : n_slots(c)); sl++) {
             // (the slot in use first: if memory runs out half-way the current frame still has its buffers)
             FrameBufs& t = set[(c->slot + sl) % kSlots];
@@ -870,7 +888,27 @@ int reserve_pass_buffers(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>
     return upload_draw_list(c, b, draws_host, b.kind == kPassWorld);
 }
 
-int ensure_bin_capacity(AwsmHipCtx* c, uint32_t entries) { return ensure_bin_capacity_of(c, FB(c), entries); }
+// A list that overflowed grows to what its pass measured, with headroom: entries + 25 % + 1024.
+inline uint32_t with_headroom(uint32_t need) { return need + need / 4 + 1024; }
+// ... a geometry-type pass's bin list (counters: the pass's own, read back), and the raster items that are sized with it
+int grow_after_overflow(AwsmHipCtx* c, FrameBufs& b, const uint32_t* counters) {
+    const int rc = ensure_bin_capacity_of(c, b, with_headroom(counters[kCtrEntries]));
+    return rc ? rc : reserve_raster_items(c, b, false, dims_of(c, b));
+}
+
+// A versioned record of the C ABI (first word: struct_size) over the defaults `dst` already holds: the caller's fields as far as it knows them.
+int merge_record(AwsmHipCtx* c, const char* entry, const char* type, const void* src, void* dst, size_t size) {
+    const uint32_t given = *(const uint32_t*)src;
+    if (given < 4u || given > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: %s.struct_size = %u (set it to sizeof(%s))", entry, type, given, type);
+    memcpy((uint8_t*)dst + 4, (const uint8_t*)src + 4, (std::min<size_t>(given, size) & ~(size_t)3) - 4);      // whole fields only; the rest keeps its defaults
+    return AWSM_OK;
+}
+// ... and its first n floats are finite
+int check_finite(AwsmHipCtx* c, const char* entry, const float* p, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: value %zu of the record is not finite", entry, i);
+    return AWSM_OK;
+}
 
 }  // namespace
 
@@ -890,10 +928,8 @@ int awsm_hip_create(const AwsmConfig* cfg, AwsmHipCtx** out) {
     if (!c) return AWSM_ERR_OUT_OF_MEMORY;
     c->device = cfg->device;
     c->flags = cfg->flags;
-    for (int s = 0; s < kSlots; s++) {
-        FrameBufs* const of_kind[] = {&c->fb[s], &c->tr[s], &c->hud[s], &c->htr[s], &c->shadow[s]};      // in PassKind's order
-        for (int k = 0; k < 5; k++) { of_kind[k]->kind = (PassKind)k; of_kind[k]->slot = (uint8_t)s; }
-    }
+    for (int k = 0; k < kPassKinds; k++)
+        for (int s = 0; s < kSlots; s++) { FrameBufs& b = pass_slots(c, (PassKind)k)[s]; b.kind = (PassKind)k; b.slot = (uint8_t)s; }
     auto bail = [&](int code) { awsm_hip_destroy(c); return code; };
     if (hipSetDevice(c->device) != hipSuccess) return bail(AWSM_ERR_DEVICE);
     hipDeviceProp_t prop;
@@ -915,14 +951,11 @@ int awsm_hip_create(const AwsmConfig* cfg, AwsmHipCtx** out) {
         c->lean_grid = per_cu > 0 ? (uint32_t)(per_cu * prop.multiProcessorCount) & ~7u : 0u;
     }
     for (int s = 0; s < n_slots(c); s++) {
-        if (hipMalloc(&c->fb[s].counters.ptr, 16 * sizeof(uint32_t)) != hipSuccess || hipMemset(c->fb[s].counters.ptr, 0, 16 * sizeof(uint32_t)) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);   // 8 frame counters + 4 pick words + k_bin_scan's arrival counter [12] and ready flag [13]
-        c->fb[s].counters.size = 16 * sizeof(uint32_t);
-        if (hipMalloc(&c->tr[s].counters.ptr, 16 * sizeof(uint32_t)) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);
-        c->tr[s].counters.size = 16 * sizeof(uint32_t);
-        if (hipMalloc(&c->htr[s].counters.ptr, 16 * sizeof(uint32_t)) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);
-        c->htr[s].counters.size = 16 * sizeof(uint32_t);
-        if (hipMalloc(&c->hud[s].counters.ptr, 16 * sizeof(uint32_t)) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);
-        c->hud[s].counters.size = 16 * sizeof(uint32_t);
+        for (PassKind k : {kPassWorld, kPassTransparent, kPassHudTransparent, kPassHud}) {      // (the shadow pass's: at its first use)
+            DevBuf& ctr = pass_slots(c, k)[s].counters;   // 8 frame counters + 4 pick words + k_bin_scan's arrival counter [12] and ready flag [13]
+            if (hipMalloc(&ctr.ptr, 16 * sizeof(uint32_t)) != hipSuccess || (k == kPassWorld && hipMemset(ctr.ptr, 0, 16 * sizeof(uint32_t)) != hipSuccess)) return bail(AWSM_ERR_OUT_OF_MEMORY);
+            ctr.size = 16 * sizeof(uint32_t);
+        }
         if (hipMalloc(&c->fb[s].camera.ptr, 512) != hipSuccess || hipMemset(c->fb[s].camera.ptr, 0, 512) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);      // per-frame camera snapshot (every mode)
         c->fb[s].camera.size = 512;
     }
@@ -998,8 +1031,8 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     fr(c->sel_layers);
     for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
-    for (int k = 0; k < 5 * kSlots; k++) {
-        FrameBufs& b = k < kSlots ? c->fb[k] : (k < 2 * kSlots ? c->tr[k - kSlots] : (k < 3 * kSlots ? c->hud[k - 2 * kSlots] : (k < 4 * kSlots ? c->htr[k - 3 * kSlots] : c->shadow[k - 4 * kSlots])));
+    for (int k = 0; k < kPassKinds * kSlots; k++) {
+        FrameBufs& b = pass_slots(c, (PassKind)(k / kSlots))[k % kSlots];
         fr(b.vis); fr(b.wpos); fr(b.frag_rec); fr(b.frag_color); fr(b.frag_first); fr(b.tex_slots); fr(b.draw_mat); fr(b.clip); fr(b.nrm); fr(b.tan); fr(b.tri_rec); fr(b.tri_flags); fr(b.tri_shade); fr(b.draw_lean); fr(b.draws_dev); fr(b.draw_shade); fr(b.tile_count); fr(b.tile_offset);
         fr(b.wcache); fr(b.draws_prev); fr(b.cache_mark); fr(b.block_map); fr(b.tile_cursor); fr(b.tile_order); fr(b.scan_tmp); fr(b.tile_split); fr(b.raster_scratch); fr(b.bin_list); fr(b.big_list); fr(b.counters); fr(b.camera);
     }
@@ -1204,7 +1237,7 @@ int awsm_hip_msaa_halo_export(AwsmHipCtx* c, void* dst, size_t bytes) {
     if (bytes < (size_t)bands * 2 * c->width * 8) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "msaa_halo_export: %zu bytes, %zu needed (%u bands x 2 rows x %u keys)", bytes, (size_t)bands * 2 * c->width * 8, bands, c->width);
     HIPCHK(c, hipSetDevice(c->device));
     FrameDev f;
-    fill_frame(c, &f);
+    fill_frame(c, &f, frame_view(c));
     awsm_launch_msaa_halo_export(&f, (unsigned long long*)dst, bands, c->stream);
     HIPCHK(c, hipGetLastError());
     return AWSM_OK;
@@ -1259,7 +1292,8 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
     ht.mark("geometry_pass: slot-free wait");
     c->shadow_done = false; c->shadow_pass[c->slot].on = false; c->shadow_px[c->slot] = 0;      // no shadow pass in a frame: no shadow in that frame
     c->draws_api.assign(draws, draws + n);
-    c->draws_host.swap(new_draws);
+    PassList& world = c->lists[kPassWorld];
+    world.draws.swap(new_draws);
     {   // What earlier frames needed in their (triangle, tile) lists, as far as the GPU has reported it (pinned words written by k_bin_scan;
         // no wait).  A frame rendered without frame_end cannot be replayed: size the list ahead of the need instead, and count the
         // frames that did overflow (AwsmFrameStats.frames_with_dropped_bin_entries).
@@ -1278,10 +1312,10 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
                 if ((rc = reserve_raster_items(c, c->fb[s], false, dims_of(c, c->fb[s])))) return rc;
             }
     }
-    c->total_tris = (uint32_t)tris; c->total_verts = (uint32_t)(3 * tris); c->n_blocks = (uint32_t)blocks;
+    world.total_tris = (uint32_t)tris; world.n_blocks = (uint32_t)blocks;
     ht.mark("geometry_pass: bin capacity");
     compose_pixel_to_view(c, FB(c));
-    if ((rc = reserve_pass_buffers(c, FB(c), c->draws_host, c->total_tris, false))) return rc;
+    if ((rc = reserve_pass_buffers(c, FB(c), world.draws, world.total_tris, false))) return rc;
     ht.mark("geometry_pass: reserve + draw-list upload");
     if ((rc = enqueue_geometry(c))) return rc;
     c->camera_written_since_snapshot = false;
@@ -1294,49 +1328,42 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
 // themselves.  Here: the same kernels into the slot's hud key buffer; the world's keys and depth stay as they are (the world transparent pass tests
 // against them), and the opaque pass, the picker and the HUD transparent pass look at the hud keys.
 static int enqueue_hud_geometry(AwsmHipCtx* c) {
-    FrameBufs& hb = c->hud[c->slot];
+    const FrameBufs& hb = pass_bufs(c, kPassHud);
+    const PassList& world = c->lists[kPassWorld];
+    const PassList& hud = c->lists[kPassHud];
     FrameDev f;
-    { const bool hd = c->hud_geometry_done; c->hud_geometry_done = false; fill_frame(c, &f); c->hud_geometry_done = hd; }
-    f.bin_capacity = hb.bin_capacity;
+    fill_frame(c, &f, FrameView{false, c->hud_merged});      // no hud keys yet; merged: the lean route's offsets must hold for both passes' triangles
+    bind_pass(f, hb);      // the tile tables, the lists, the counters and the keys are this pass's own in either mode
     f.shade_todo = nullptr; f.shade_todo_cap = 0; f.lean_next = nullptr; f.lean_grid = 0;      // (k_deform_transform's per-frame resets of the opaque pass's lists: the world pass's)
     if (c->hud_merged) {
         // MSAA: the hud draws in the world pass's rank space — vertices, setup records and per-triangle words go behind the world's in the SAME arrays
-        // (f keeps the world's pointers), only the tile tables, the lists and the keys are this pass's own
+        // (f keeps the world's list and arrays, and its lean records), only the tile tables, the lists and the keys are this pass's own
+        const FrameBufs& wb = FB(c);
+        f.draws = (const DrawDev*)wb.draws_dev.ptr;
+        f.clip = (float4*)wb.clip.ptr; f.nrm = (float4*)wb.nrm.ptr; f.tan = (float4*)wb.tan.ptr;
+        f.tri_info = (uint32_t*)wb.tri_flags.ptr;
+        f.tri_rec = (TriRec*)wb.tri_rec.ptr;
         f.n_draws = (uint32_t)c->hud_combined.size();
-        f.total_tris = c->total_tris + c->hud_total_tris; f.total_verts = 3u * f.total_tris;
-        f.rank0 = c->total_tris; f.block0 = c->n_blocks;
+        f.total_tris = world.total_tris + hud.total_tris; f.total_verts = 3u * f.total_tris;
+        f.rank0 = world.total_tris; f.block0 = world.n_blocks;
     } else {
-    f.n_draws = (uint32_t)c->hud_draws_host.size();
-    f.total_tris = c->hud_total_tris; f.total_verts = 3u * c->hud_total_tris;
-    f.draws = (const DrawDev*)hb.draws_dev.ptr;
-    f.clip = (float4*)hb.clip.ptr; f.nrm = (float4*)hb.nrm.ptr; f.tan = (float4*)hb.tan.ptr;
-    f.tri_info = (uint32_t*)hb.tri_flags.ptr;
-    f.tri_shade = nullptr; f.draw_lean = nullptr;
-    f.tri_rec = (TriRec*)hb.tri_rec.ptr;
+        f.n_draws = (uint32_t)hud.draws.size();
+        f.total_tris = hud.total_tris; f.total_verts = 3u * hud.total_tris;
+        f.tri_shade = nullptr; f.draw_lean = nullptr;
     }
-    f.tile_count = (uint32_t*)hb.tile_count.ptr; f.tile_offset = (uint32_t*)hb.tile_offset.ptr;
-    f.tile_cursor = (uint32_t*)hb.tile_cursor.ptr; f.bin_list = (uint32_t*)hb.bin_list.ptr;
-    f.tile_order = (uint32_t*)hb.tile_order.ptr; f.scan_tmp = (uint32_t*)hb.scan_tmp.ptr;
-    f.tile_split = (uint32_t*)hb.tile_split.ptr; f.raster_scratch = (unsigned long long*)hb.raster_scratch.ptr;
-    f.raster_extra_cap = hb.raster_extra_cap; f.raster_slot_cap = hb.raster_slot_cap;
-    f.big_list = (uint32_t*)hb.big_list.ptr;
-    f.counters = (uint32_t*)hb.counters.ptr;
     f.host_bin_status = nullptr;                 // the world pass's status words are not this pass's to write
     f.camera_snap = nullptr; f.camera_snap_words = 0;
-    f.vis = (unsigned long long*)hb.vis.ptr;     // every tile of the frame is written: a tile without hud triangles becomes "no hit"
-    f.hud_vis = nullptr;
+    // (f.vis, this pass's keys: every tile of the frame is written — a tile without hud triangles becomes "no hit")
     int rc;
     if ((rc = sync_scene(c))) return rc;
     const uint32_t n_tiles = f.tiles_x * f.tiles_y;
-    awsm_launch_transform(c->scene_dev, &f, c->hud_n_blocks, c->stream);
+    awsm_launch_transform(c->scene_dev, &f, hud.n_blocks, c->stream);      // (unconditionally, and no memsets: this pass is enqueued only with triangles)
     if (n_tiles) {
-        awsm_launch_bin_count(&f, c->stream); awsm_launch_bin_big(&f, 0, c->stream);
-        awsm_launch_bin_scan(&f, c->stream);
-        awsm_launch_bin_fill(&f, c->stream); awsm_launch_bin_big(&f, 1, c->stream);
+        enqueue_binning(f, true, c->stream);
         awsm_launch_raster(&f, c->stream);
     }
     if (c->hud_merged) {      // what the opaque pass reads: per sample the hud triangle (where one was drawn) under the world's depth
-        const size_t spp = c->msaa == 4 ? 4 : 1, first = (size_t)f.y0 * c->width * spp, n = (size_t)(f.y1 - f.y0) * c->width * spp;
+        const size_t spp = samples_of(c), first = (size_t)f.y0 * c->width * spp, n = (size_t)(f.y1 - f.y0) * c->width * spp;
         awsm_launch_hud_merge((const unsigned long long*)FB(c).vis.ptr, (const unsigned long long*)hb.vis.ptr, (unsigned long long*)c->merged_vis[c->slot].ptr, first, n, c->stream);
     }
     HIPCHK(c, hipGetLastError());
@@ -1348,30 +1375,32 @@ int awsm_hip_hud_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n)
     if (!c->geometry_done || c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "hud_geometry_pass goes between the geometry pass and the opaque pass of a frame");
     HIPCHK(c, hipSetDevice(c->device));
     uint64_t tris = 0, blocks = 0;
-    int rc = build_draw_list(c, "hud_geometry_pass", draws, n, AWSM_BUF_VIS_GEOM_DATA, 168u, c->hud_draws_host, &tris, &blocks);
+    PassList& hud = c->lists[kPassHud];
+    const PassList& world = c->lists[kPassWorld];
+    int rc = build_draw_list(c, "hud_geometry_pass", draws, n, AWSM_BUF_VIS_GEOM_DATA, 168u, hud.draws, &tris, &blocks);
     if (rc) return rc;
-    c->hud_total_tris = (uint32_t)tris; c->hud_n_blocks = (uint32_t)blocks;
+    hud.total_tris = (uint32_t)tris; hud.n_blocks = (uint32_t)blocks;
     c->hud_merged = false;
     if (!tris) { c->hud_geometry_done = false; return AWSM_OK; }
-    FrameBufs& hb = c->hud[c->slot];
-    const size_t px = (size_t)c->width * c->height, spp = c->msaa == 4 ? 4 : 1;
+    FrameBufs& hb = pass_bufs(c, kPassHud);
+    const size_t px = (size_t)c->width * c->height, spp = samples_of(c);
     if ((rc = dev_reserve(c, hb.vis, px * 8 * spp))) return rc;
-    if ((rc = reserve_pass_buffers(c, hb, c->hud_draws_host, c->hud_total_tris, false))) return rc;      // tile tables, lists (and, single-sampled, the pass's own vertex arrays)
+    if ((rc = reserve_pass_buffers(c, hb, hud.draws, hud.total_tris, false))) return rc;      // tile tables, lists (and, single-sampled, the pass's own vertex arrays)
     if (c->msaa == 4) {
         // one rank space with the world pass (see AwsmHipCtx::hud_merged)
-        if ((uint64_t)c->total_tris + tris > 0x55555555ull) return fail(c, AWSM_ERR_UNSUPPORTED, "hud_geometry_pass: more than 2^32/3 triangles in the frame");
-        c->hud_combined = c->draws_host;
-        for (DrawDev d : c->hud_draws_host) { d.first_tri += c->total_tris; d.first_block += c->n_blocks; c->hud_combined.push_back(d); }
+        if ((uint64_t)world.total_tris + tris > 0x55555555ull) return fail(c, AWSM_ERR_UNSUPPORTED, "hud_geometry_pass: more than 2^32/3 triangles in the frame");
+        c->hud_combined = world.draws;
+        for (DrawDev d : hud.draws) { d.first_tri += world.total_tris; d.first_block += world.n_blocks; c->hud_combined.push_back(d); }
         if (c->hud_combined.size() >= (1u << 24)) return fail(c, AWSM_ERR_UNSUPPORTED, "hud_geometry_pass: more than 2^24 draws in the frame");
         FrameBufs& wb = FB(c);
         const void* before[3] = {wb.clip.ptr, wb.tri_rec.ptr, wb.tri_flags.ptr};
-        if ((rc = ensure_pass_capacity(c, wb, c->hud_combined, c->total_tris + c->hud_total_tris, false))) return rc;      // room for the hud draws behind the world's
+        if ((rc = ensure_pass_capacity(c, wb, c->hud_combined, world.total_tris + hud.total_tris, false))) return rc;      // room for the hud draws behind the world's
         // The world's list stays cached as the world pass uploaded it (re-uploaded only if the list buffer just moved); the hud draws go behind it with a
         // cache of their own — a static scene with a hud mesh uploads nothing per frame and keeps its per-draw records (the combined list used to
         // replace the world list's cache, so both were uploaded every frame and k_resolve_draws never rested).
-        if ((rc = upload_draw_list(c, wb, c->draws_host, true))) return rc;
+        if ((rc = upload_draw_list(c, wb, world.draws, true))) return rc;
         {
-            const size_t at = c->draws_host.size();
+            const size_t at = world.draws.size();
             const std::vector<DrawDev> tail(c->hud_combined.begin() + (long)at, c->hud_combined.end());
             const bool same = wb.tail_uploaded_valid && wb.tail_uploaded_ptr == wb.draws_dev.ptr && wb.tail_uploaded_at == at && wb.tail_uploaded.size() == tail.size() &&
                               memcmp(wb.tail_uploaded.data(), tail.data(), tail.size() * sizeof(DrawDev)) == 0;
@@ -1401,32 +1430,21 @@ int awsm_hip_hud_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n)
 // camera snapshot, no status words, the opaque pass's lists nulled, no geometry cache — nothing the world pass left is reset.  k_deform_transform
 // reads view_proj through the scene table: it is given the slot's second copy of the table, whose camera entry is the slot's copy of the light block.
 static int enqueue_shadow(AwsmHipCtx* c) {
-    FrameBufs& sb = c->shadow[c->slot];
+    const FrameBufs& sb = pass_bufs(c, kPassShadow);
+    const PassList& casters = c->lists[kPassShadow];
     const uint32_t S = c->shadow_pass[c->slot].p.map_size;
     FrameDev f;
     memset(&f, 0, sizeof f);
     f.width = S; f.height = S; f.y0 = 0; f.y1 = S; f.sy0 = 0; f.sy1 = S;
     f.tiles_x = (S + kTile - 1) / kTile; f.tiles_y = f.tiles_x; f.tile_row0 = 0;
     f.band_n = 1; f.band_r = 0; f.out_compact = 0;
-    f.n_draws = (uint32_t)c->shadow_draws_host.size();
-    f.total_tris = c->shadow_total_tris; f.total_verts = 3u * c->shadow_total_tris;
-    f.bin_capacity = sb.bin_capacity;
+    f.n_draws = (uint32_t)casters.draws.size();
+    f.total_tris = casters.total_tris; f.total_verts = 3u * casters.total_tris;
     f.msaa = 0;                                  // single-sampled, whatever the frame is
     f.camera = (const uint8_t*)c->shadow_cam[c->slot].ptr;
-    f.draws = (const DrawDev*)sb.draws_dev.ptr;
-    f.clip = (float4*)sb.clip.ptr; f.nrm = (float4*)sb.nrm.ptr; f.tan = (float4*)sb.tan.ptr;
-    f.tri_info = (uint32_t*)sb.tri_flags.ptr;
-    f.tri_rec = (TriRec*)sb.tri_rec.ptr;
-    f.tile_count = (uint32_t*)sb.tile_count.ptr; f.tile_offset = (uint32_t*)sb.tile_offset.ptr;
-    f.tile_cursor = (uint32_t*)sb.tile_cursor.ptr; f.bin_list = (uint32_t*)sb.bin_list.ptr;
-    f.tile_order = (uint32_t*)sb.tile_order.ptr; f.scan_tmp = (uint32_t*)sb.scan_tmp.ptr;
-    f.tile_split = (uint32_t*)sb.tile_split.ptr; f.raster_scratch = (unsigned long long*)sb.raster_scratch.ptr;
-    f.raster_extra_cap = sb.raster_extra_cap; f.raster_slot_cap = sb.raster_slot_cap;
-    f.big_list = (uint32_t*)sb.big_list.ptr;
-    f.counters = (uint32_t*)sb.counters.ptr;
+    bind_pass(f, sb);                            // (vis = the map: every tile of it is written, a tile without casters becomes "no hit")
     f.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
     f.frame_serial = c->frame_serial;
-    f.vis = (unsigned long long*)sb.vis.ptr;     // every tile of the map is written: a tile without casters becomes "no hit"
     int rc;
     if ((rc = sync_scene(c))) return rc;
     if (c->shadow_scene_seq[c->slot] != c->scene_uploads) {      // the scene table was uploaded since the copy was made
@@ -1435,17 +1453,10 @@ static int enqueue_shadow(AwsmHipCtx* c) {
         if ((rc = upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc))) return rc;
         c->shadow_scene_seq[c->slot] = c->scene_uploads;
     }
-    const uint32_t n_tiles = f.tiles_x * f.tiles_y;
-    if (!f.total_tris) {      // otherwise k_deform_transform clears counters + tile_count (enqueue_geometry)
-        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, 8 * sizeof(uint32_t), c->stream));
-        HIPCHK(c, hipMemsetAsync((uint32_t*)sb.counters.ptr + 12, 0, 2 * sizeof(uint32_t), c->stream));
-        HIPCHK(c, hipMemsetAsync(sb.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), c->stream));
-    } else {
-        awsm_launch_transform(c->shadow_scene[c->slot], &f, c->shadow_n_blocks, c->stream);
-        awsm_launch_bin_count(&f, c->stream); awsm_launch_bin_big(&f, 0, c->stream);
-    }
-    awsm_launch_bin_scan(&f, c->stream);
-    if (f.total_tris) { awsm_launch_bin_fill(&f, c->stream); awsm_launch_bin_big(&f, 1, c->stream); }
+    const uint32_t n_tiles = f.tiles_x * f.tiles_y;      // (S >= 1: never 0 — the map is always scanned and rasterised)
+    if (!f.total_tris) { if ((rc = clear_empty_pass(c, sb, n_tiles, c->stream))) return rc; }
+    else awsm_launch_transform(c->shadow_scene[c->slot], &f, casters.n_blocks, c->stream);      // through the slot's second scene table
+    enqueue_binning(f, f.total_tris != 0, c->stream);
     awsm_launch_raster(&f, c->stream);
     HIPCHK(c, hipGetLastError());
     return AWSM_OK;
@@ -1461,16 +1472,13 @@ int awsm_hip_shadow_defaults(AwsmShadow* out) {
 int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_camera, size_t camera_bytes, const AwsmDraw* casters, uint32_t n) {
     if (!c || !s || (!casters && n)) return AWSM_ERR_INVALID_ARGUMENT;
     if (!c->geometry_done || c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass goes between the geometry pass and the opaque pass of a frame");
-    if (c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height)))
+    if (is_sharded(c))
         return fail(c, AWSM_ERR_UNSUPPORTED, "shadow_pass on a sharded context: the resolve's neighbours need rows the shard never rasterised (no halo exchange)");
     AwsmShadow full;
     awsm_hip_shadow_defaults(&full);
-    if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: AwsmShadow.struct_size = %u (set it to sizeof(AwsmShadow))", s->struct_size);
-    memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, (std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3) - 4);      // whole fields only; the rest keeps its defaults
+    { const int rcm = merge_record(c, "shadow_pass", "AwsmShadow", s, &full, sizeof full); if (rcm) return rcm; }
     if (!light_camera || camera_bytes != 512) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", camera_bytes);
-    const float* v = full.light;
-    for (size_t i = 0; i < 9; i++)      // light[4] and the five parameters are contiguous
-        if (!std::isfinite(v[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: value %zu of the record is not finite", i);
+    { const int rcf = check_finite(c, "shadow_pass", full.light, 9); if (rcf) return rcf; }      // light[4] and the five parameters are contiguous
     static_assert(offsetof(AwsmShadow, facing_fade) == offsetof(AwsmShadow, light) + 8 * sizeof(float) && sizeof(AwsmShadow) == 48, "AwsmShadow: light[4] and five floats behind three words");
     float lvp[16];
     memcpy(lvp, (const uint8_t*)light_camera + 128, sizeof lvp);
@@ -1489,12 +1497,13 @@ int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_c
     int rc = build_draw_list(c, "shadow_pass", casters, n, AWSM_BUF_VIS_GEOM_DATA, 168u, list, &tris, &blocks);
     if (rc) return rc;
     // nothing refused from here on but for memory: the slot's state is this pass's
-    FrameBufs& sb = c->shadow[c->slot];
+    FrameBufs& sb = pass_bufs(c, kPassShadow);
+    PassList& cast = c->lists[kPassShadow];
     AwsmHipCtx::ShadowState& st = c->shadow_pass[c->slot];
     c->shadow_done = false; st.on = false;
     st.p = full; memcpy(st.light_view_proj, lvp, sizeof lvp);
-    c->shadow_draws_host.swap(list);
-    c->shadow_total_tris = (uint32_t)tris; c->shadow_n_blocks = (uint32_t)blocks;
+    cast.draws.swap(list);
+    cast.total_tris = (uint32_t)tris; cast.n_blocks = (uint32_t)blocks;
     if (!sb.counters.ptr) {
         HIPCHK(c, hipMalloc(&sb.counters.ptr, 16 * sizeof(uint32_t)));
         sb.counters.size = 16 * sizeof(uint32_t);
@@ -1503,7 +1512,7 @@ int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_c
     if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
     if ((rc = dev_reserve(c, c->shadow_cam[c->slot], 512))) return rc;
     if ((rc = dev_reserve(c, sb.vis, (size_t)full.map_size * full.map_size * 8))) return rc;
-    if ((rc = reserve_pass_buffers(c, sb, c->shadow_draws_host, c->shadow_total_tris, false))) return rc;
+    if ((rc = reserve_pass_buffers(c, sb, cast.draws, cast.total_tris, false))) return rc;
     if ((rc = upload_small(c, c->shadow_cam[c->slot].ptr, light_camera, 512))) return rc;      // through the pinned ring, as small writes are
     if ((rc = enqueue_shadow(c))) return rc;
     st.on = true; c->shadow_done = true;
@@ -1551,7 +1560,7 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     }
     // screen-space ambient occlusion (awsm_hip_set_ssao): this pass carries the record as it stands now, into a replay too
     const bool ssao_on = c->ssao.on && p->has_opaque;
-    if (ssao_on && (c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height))))
+    if (ssao_on && is_sharded(c))
         return fail(c, AWSM_ERR_UNSUPPORTED, "opaque_pass with SSAO on a sharded context: its taps and its smoothing read depth in rows the shard never rasterised (no halo exchange)");
     HIPCHK(c, hipSetDevice(c->device));
     if (ssao_on) { const int rcs = dev_reserve(c, c->ssao_layers[c->slot], (size_t)c->width * c->height * 12); if (rcs) return rcs; }
@@ -1578,23 +1587,18 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     return AWSM_OK;
 }
 
-static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n, bool hud);
-static int transparent_pass_impl(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n, bool hud) {
-    const int rc = transparent_pass_body(c, draws, n, hud);
-    if (c) c->hud_transparent = false;      // (whatever the outcome: TR(c) names the world pass's buffers outside a HUD pass's own enqueue)
-    return rc;
-}
-static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n, bool hud) {
+// kind: the world transparent pass or the HUD one
+static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n, PassKind kind) {
+    const bool hud = kind == kPassHudTransparent;
     if (!c || (!draws && n)) return AWSM_ERR_INVALID_ARGUMENT;
     if (!c->geometry_done || !c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "transparent_pass needs the geometry and opaque passes of the same frame first");
     if (hud && !c->transparent_done) return fail(c, AWSM_ERR_NOT_READY, "hud_transparent_pass draws over the composite: call transparent_pass first (n_draws = 0 is valid)");
-    c->hud_transparent = hud;
-    const bool sharded = c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height));
+    const bool sharded = is_sharded(c);
     if (sharded && !c->opaque_src)
         return fail(c, AWSM_ERR_UNSUPPORTED, "transparent_pass on a sharded context: screen-space transmission reads the whole opaque image — gather it and bind it with awsm_hip_bind_opaque_source first");
     if (!hud && c->sel.on && sharded)
         return fail(c, AWSM_ERR_UNSUPPORTED, "transparent_pass with a selection on a sharded context: the outline's ring reads keys in rows the shard never rasterised (no halo exchange)");
-    if (!hud && c->sel.on && !c->draws_host.empty() && (!c->bufs[AWSM_BUF_GEOM_META].ptr || !c->bufs[AWSM_BUF_MATERIAL_META].ptr))
+    if (!hud && c->sel.on && !c->lists[kPassWorld].draws.empty() && (!c->bufs[AWSM_BUF_GEOM_META].ptr || !c->bufs[AWSM_BUF_MATERIAL_META].ptr))
         return fail(c, AWSM_ERR_NOT_READY, "transparent_pass with a selection: the geometry or material meta buffer is missing");
     if (c->opaque_src && c->opaque_src_bytes < (size_t)c->width * c->height * 8)
         return fail(c, AWSM_ERR_INVALID_ARGUMENT, "transparent_pass: the bound opaque source holds %zu bytes, the frame needs %zu", c->opaque_src_bytes, (size_t)c->width * c->height * 8);
@@ -1606,34 +1610,35 @@ static int transparent_pass_body(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t 
     }
     HIPCHK(c, hipSetDevice(c->device));
     uint64_t tris = 0, blocks = 0;
-    const int which = hud ? 1 : 0;
-    int rc = build_draw_list(c, hud ? "hud_transparent_pass" : "transparent_pass", draws, n, AWSM_BUF_TRANSPARENCY_GEOM_DATA, 0u, c->tr_draws_host[which], &tris, &blocks);
+    PassList& list = c->lists[kind];
+    FrameBufs& t = pass_bufs(c, kind);
+    int rc = build_draw_list(c, hud ? "hud_transparent_pass" : "transparent_pass", draws, n, AWSM_BUF_TRANSPARENCY_GEOM_DATA, 0u, list.draws, &tris, &blocks);
     if (rc) return rc;
-    c->tr_total_tris[which] = (uint32_t)tris; c->tr_n_blocks[which] = (uint32_t)blocks;
+    list.total_tris = (uint32_t)tris; list.n_blocks = (uint32_t)blocks;
     const size_t px = (size_t)c->width * c->height;
     if (!c->bound_comp && (rc = dev_reserve(c, c->comp16, px * 8))) return rc;
     if (c->bound_comp && c->bound_comp_bytes < px * 8) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "transparent_pass: bound composite holds %zu bytes, the frame needs %zu", c->bound_comp_bytes, px * 8);
     if ((c->flags & AWSM_CFG_PARITY_TAP) && (rc = dev_reserve(c, c->comp32, px * 16))) return rc;
-    if ((rc = reserve_pass_buffers(c, TR(c), c->tr_draws_host[which], c->tr_total_tris[which], true))) return rc;
-    if ((rc = dev_reserve(c, TR(c).frag_first, px * 4))) return rc;
-    if ((rc = ensure_fragment_capacity(c, TR(c), (c->flags & AWSM_CFG_SMALL_BIN_LIST) ? 4096u : (uint32_t)std::max<size_t>(px / 2, 1u << 20)))) return rc;
+    if ((rc = reserve_pass_buffers(c, t, list.draws, list.total_tris, true))) return rc;
+    if ((rc = dev_reserve(c, t.frag_first, px * 4))) return rc;
+    if ((rc = ensure_fragment_capacity(c, t, (c->flags & AWSM_CFG_SMALL_BIN_LIST) ? 4096u : (uint32_t)std::max<size_t>(px / 2, 1u << 20)))) return rc;
     if (c->overlap) {   // the draw-list upload went to the caller's stream; the pass runs on the shade stream
         HIPCHK(c, hipEventRecord(c->ev_geom_done[c->slot], c->stream));
         HIPCHK(c, hipStreamWaitEvent(shade_stream_of(c), c->ev_geom_done[c->slot], 0));
     }
     if (!hud) c->grid_pass[c->slot] = c->grid;
     if (!hud) {      // the selection overlay: this pass carries the record as it stands now, into a replay too
-        if (c->sel.on && (rc = dev_reserve(c, c->sel_tables[c->slot], (size_t)selection::kMaxEdges * selection::kEdgeFloats * 4 + std::max<size_t>(c->draws_host.size(), 1)))) return rc;
+        if (c->sel.on && (rc = dev_reserve(c, c->sel_tables[c->slot], (size_t)selection::kMaxEdges * selection::kEdgeFloats * 4 + std::max<size_t>(c->lists[kPassWorld].draws.size(), 1)))) return rc;
         c->sel_pass[c->slot] = c->sel;
     }
-    if ((rc = enqueue_transparent(c))) return rc;
+    if ((rc = enqueue_transparent(c, kind))) return rc;
     if (hud) c->hud_transparent_done = true; else { c->transparent_done = true; c->hud_transparent_done = false; }
     return AWSM_OK;
 }
-int awsm_hip_transparent_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) { return transparent_pass_impl(c, draws, n, false); }
+int awsm_hip_transparent_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) { return transparent_pass_body(c, draws, n, kPassTransparent); }
 // MaterialTransparentRenderPass::render(ctx, renderables.hud, true) (render.rs:301-312, begin_hud_transparent_pass :490-521): the hud meshes drawn
 // forward over what the frame holds so far (colours LoadOp::Load -> the composite, in place), depth-tested among themselves against hud_depth, cleared.
-int awsm_hip_hud_transparent_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) { return transparent_pass_impl(c, draws, n, true); }
+int awsm_hip_hud_transparent_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) { return transparent_pass_body(c, draws, n, kPassHudTransparent); }
 
 int awsm_hip_set_stage_timers(AwsmHipCtx* c, int enabled) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
@@ -1687,34 +1692,38 @@ static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& p);
 int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
     HIPCHK(c, hipSetDevice(c->device));
+    const PassList& world_list = c->lists[kPassWorld];
+    // the passes' counter words as read back (CounterWord): the world geometry pass's and the world transparent pass's in the pinned block
+    const uint32_t* const world = c->counters_host;
+    const uint32_t* const fwd = c->counters_host + 8;
     bool still_over = false;
     for (int attempt = 0;; attempt++) {
         if (out && c->geometry_done && c->has_opaque_for_stats()) {   // stats only: count covered pixels from the visibility buffer
             FrameDev f;
-            fill_frame(c, &f);
-            HIPCHK(c, hipMemsetAsync((uint32_t*)FB(c).counters.ptr + 3, 0, sizeof(uint32_t), c->stream));
+            fill_frame(c, &f, frame_view(c));
+            HIPCHK(c, hipMemsetAsync((uint32_t*)FB(c).counters.ptr + kCtrCovered, 0, sizeof(uint32_t), c->stream));
             awsm_launch_count_covered(&f, c->stream);
         }
         HIPCHK(c, hipMemcpyAsync(c->counters_host, FB(c).counters.ptr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->cache_blocks_last = 0;
-        if (out && c->geometry_done && c->stage_timers && c->n_blocks && FB(c).cache_mark.size >= (size_t)c->n_blocks * 4) {
-            std::vector<uint32_t> marks(c->n_blocks);
+        if (out && c->geometry_done && c->stage_timers && world_list.n_blocks && FB(c).cache_mark.size >= (size_t)world_list.n_blocks * 4) {
+            std::vector<uint32_t> marks(world_list.n_blocks);
             HIPCHK(c, hipMemcpy(marks.data(), FB(c).cache_mark.ptr, marks.size() * 4, hipMemcpyDeviceToHost));
             for (uint32_t m : marks) c->cache_blocks_last += m == c->frame_serial ? 1u : 0u;
         }
         if (c->overlap) { HIPCHK(c, sync_shade_streams(c)); for (bool& b : c->shade_pending) b = false; }
         { int rch = handoff_check(c); if (rch) return rch; }      // a gate ended unopened: the frame it guarded was dropped
         memset(c->counters_host + 8, 0, 8 * sizeof(uint32_t));
-        uint32_t hud_fwd[8] = {}, hud_geo[8] = {}, shadow_geo[8] = {};      // the HUD transparent pass's, the HUD geometry pass's and the shadow pass's own counters (same layout)
-        if (c->shadow_done) HIPCHK(c, hipMemcpy(shadow_geo, c->shadow[c->slot].counters.ptr, sizeof shadow_geo, hipMemcpyDeviceToHost));
-        if (c->transparent_done) HIPCHK(c, hipMemcpy(c->counters_host + 8, c->tr[c->slot].counters.ptr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (c->hud_transparent_done) HIPCHK(c, hipMemcpy(hud_fwd, c->htr[c->slot].counters.ptr, sizeof hud_fwd, hipMemcpyDeviceToHost));
-        if (c->hud_geometry_done) HIPCHK(c, hipMemcpy(hud_geo, c->hud[c->slot].counters.ptr, sizeof hud_geo, hipMemcpyDeviceToHost));
-        const bool geom_over = c->geometry_done && c->counters_host[2] != 0, fwd_over = c->transparent_done && c->counters_host[10] != 0;
-        const bool frag_over = c->transparent_done && c->counters_host[14] != 0;      // a pixel's fragment list did not fit
-        const bool hud_geo_over = c->hud_geometry_done && hud_geo[2] != 0, hud_fwd_over = c->hud_transparent_done && hud_fwd[2] != 0, hud_frag_over = c->hud_transparent_done && hud_fwd[6] != 0;
-        const bool shadow_over = c->shadow_done && shadow_geo[2] != 0;
+        uint32_t hud_fwd[kCtrWords] = {}, hud_geo[kCtrWords] = {}, shadow_geo[kCtrWords] = {};      // the HUD transparent pass's, the HUD geometry pass's and the shadow pass's own counters (same layout)
+        if (c->shadow_done) HIPCHK(c, hipMemcpy(shadow_geo, pass_bufs(c, kPassShadow).counters.ptr, sizeof shadow_geo, hipMemcpyDeviceToHost));
+        if (c->transparent_done) HIPCHK(c, hipMemcpy(c->counters_host + 8, pass_bufs(c, kPassTransparent).counters.ptr, kCtrWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (c->hud_transparent_done) HIPCHK(c, hipMemcpy(hud_fwd, pass_bufs(c, kPassHudTransparent).counters.ptr, sizeof hud_fwd, hipMemcpyDeviceToHost));
+        if (c->hud_geometry_done) HIPCHK(c, hipMemcpy(hud_geo, pass_bufs(c, kPassHud).counters.ptr, sizeof hud_geo, hipMemcpyDeviceToHost));
+        const bool geom_over = c->geometry_done && world[kCtrOverflow] != 0, fwd_over = c->transparent_done && fwd[kCtrOverflow] != 0;
+        const bool frag_over = c->transparent_done && fwd[kCtrFragOverflow] != 0;      // a pixel's fragment list did not fit
+        const bool hud_geo_over = c->hud_geometry_done && hud_geo[kCtrOverflow] != 0, hud_fwd_over = c->hud_transparent_done && hud_fwd[kCtrOverflow] != 0, hud_frag_over = c->hud_transparent_done && hud_fwd[kCtrFragOverflow] != 0;
+        const bool shadow_over = c->shadow_done && shadow_geo[kCtrOverflow] != 0;
         still_over = geom_over || fwd_over || frag_over || hud_geo_over || hud_fwd_over || hud_frag_over || shadow_over;
         if (!still_over || attempt >= 4) break;
         // a list overflowed: grow it to the measured need and replay from the first pass that lost entries.  The passes of a frame are replayed in their
@@ -1723,36 +1732,26 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         int rc;
         c->overflow_retries++;
         if (geom_over) {
-            if ((rc = ensure_bin_capacity(c, c->counters_host[1] + c->counters_host[1] / 4 + 1024))) return rc;
-            if ((rc = reserve_raster_items(c, FB(c), false, dims_of(c, FB(c))))) return rc;
+            if ((rc = grow_after_overflow(c, FB(c), world))) return rc;
             if ((rc = enqueue_geometry(c, true))) return rc;
         }
         if (hud_geo_over || (geom_over && c->hud_geometry_done && c->hud_merged)) {      // (merged keys: a new world pass needs a new merge)
-            FrameBufs& hb = c->hud[c->slot];
-            if (hud_geo_over && (rc = ensure_bin_capacity_of(c, hb, hud_geo[1] + hud_geo[1] / 4 + 1024))) return rc;
-            if (hud_geo_over && (rc = reserve_raster_items(c, hb, false, dims_of(c, hb)))) return rc;
+            if (hud_geo_over && (rc = grow_after_overflow(c, pass_bufs(c, kPassHud), hud_geo))) return rc;
             if ((rc = enqueue_hud_geometry(c))) return rc;
         }
         if (shadow_over) {      // the light's pass, in its place between the geometry passes and the opaque pass; the light block is still in the slot's copy
-            FrameBufs& sb = c->shadow[c->slot];
-            if ((rc = ensure_bin_capacity_of(c, sb, shadow_geo[1] + shadow_geo[1] / 4 + 1024))) return rc;
-            if ((rc = reserve_raster_items(c, sb, false, dims_of(c, sb)))) return rc;
+            if ((rc = grow_after_overflow(c, pass_bufs(c, kPassShadow), shadow_geo))) return rc;
             if ((rc = enqueue_shadow(c))) return rc;
         }
         if ((geom_over || hud_geo_over || shadow_over) && c->opaque_done && (rc = enqueue_opaque(c))) return rc;
-        if (fwd_over && (rc = ensure_bin_capacity_of(c, c->tr[c->slot], c->counters_host[9] + c->counters_host[9] / 4 + 1024))) return rc;
-        if (frag_over && (rc = ensure_fragment_capacity(c, c->tr[c->slot], c->counters_host[13] + c->counters_host[13] / 4 + 1024))) return rc;
-        if (hud_fwd_over && (rc = ensure_bin_capacity_of(c, c->htr[c->slot], hud_fwd[1] + hud_fwd[1] / 4 + 1024))) return rc;
-        if (hud_frag_over && (rc = ensure_fragment_capacity(c, c->htr[c->slot], hud_fwd[5] + hud_fwd[5] / 4 + 1024))) return rc;
+        // (the transparent passes have a tile kernel of their own: no raster items to size with their lists)
+        if (fwd_over && (rc = ensure_bin_capacity_of(c, pass_bufs(c, kPassTransparent), with_headroom(fwd[kCtrEntries])))) return rc;
+        if (frag_over && (rc = ensure_fragment_capacity(c, pass_bufs(c, kPassTransparent), with_headroom(fwd[kCtrFragments])))) return rc;
+        if (hud_fwd_over && (rc = ensure_bin_capacity_of(c, pass_bufs(c, kPassHudTransparent), with_headroom(hud_fwd[kCtrEntries])))) return rc;
+        if (hud_frag_over && (rc = ensure_fragment_capacity(c, pass_bufs(c, kPassHudTransparent), with_headroom(hud_fwd[kCtrFragments])))) return rc;
         if (c->transparent_done) {
-            c->hud_transparent = false;
-            if ((rc = enqueue_transparent(c))) return rc;
-            if (c->hud_transparent_done) {
-                c->hud_transparent = true;
-                rc = enqueue_transparent(c);
-                c->hud_transparent = false;
-                if (rc) return rc;
-            }
+            if ((rc = enqueue_transparent(c, kPassTransparent))) return rc;
+            if (c->hud_transparent_done && (rc = enqueue_transparent(c, kPassHudTransparent))) return rc;
         }
         if (c->post_done && (rc = enqueue_post(c, c->post_params))) return rc;     // the effects + display of the replayed images (and fragment lists)
     }
@@ -1772,18 +1771,18 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
             out->ms_raster = ms(EV_BIN, EV_RASTER);
         }
         if (c->opaque_done) { out->ms_shade = ms(EV_SHADE_BEGIN, EV_SHADE); out->ms_shade_lean = ms(EV_SHADE_BEGIN, EV_SHADE_LEAN); }
-        if (c->transparent_done) { out->ms_forward = ms(EV_FWD_BEGIN, EV_FWD); out->forward_triangles = c->tr_total_tris[0] + (c->hud_transparent_done ? c->tr_total_tris[1] : 0u); out->forward_fragment_slots = c->counters_host[13]; }
+        if (c->transparent_done) { out->ms_forward = ms(EV_FWD_BEGIN, EV_FWD); out->forward_triangles = c->lists[kPassTransparent].total_tris + (c->hud_transparent_done ? c->lists[kPassHudTransparent].total_tris : 0u); out->forward_fragment_slots = fwd[kCtrFragments]; }
         out->ms_total = (c->geometry_done ? ms(EV_START, EV_RASTER) : 0.0f) + out->ms_shade + out->ms_forward;   // the two passes may run on different streams
-        out->triangles_in = c->total_tris;
-        out->triangles_binned = c->counters_host[0];
-        out->bin_entries = c->counters_host[1];
-        out->covered_pixels = c->counters_host[3];
+        out->triangles_in = world_list.total_tris;
+        out->triangles_binned = world[kCtrBinned];
+        out->bin_entries = world[kCtrEntries];
+        out->covered_pixels = world[kCtrCovered];
         out->bin_overflow_retries = c->overflow_retries;
         out->frames_with_dropped_bin_entries = c->dropped_frames;
         out->handoff_gate_timeouts = c->handoff_dropped_frames;
         out->geometry_cache_blocks = (c->geometry_done && c->stage_timers) ? c->cache_blocks_last : 0u;
-        out->geometry_blocks = c->geometry_done ? c->n_blocks : 0u;
-        if (c->opaque_done && c->shade_todo[c->slot].ptr && c->last_opaque.has_opaque && !(c->flags & AWSM_CFG_GENERAL_SHADE_ONLY) && !c->draws_host.empty())
+        out->geometry_blocks = c->geometry_done ? world_list.n_blocks : 0u;
+        if (c->opaque_done && c->shade_todo[c->slot].ptr && c->last_opaque.has_opaque && !(c->flags & AWSM_CFG_GENERAL_SHADE_ONLY) && !world_list.draws.empty())
             HIPCHK(c, hipMemcpy(&out->shade_general_wavefronts, c->shade_todo[c->slot].ptr, 4, hipMemcpyDeviceToHost));
         out->struct_size = (uint32_t)std::min<size_t>(caller_size, sizeof(AwsmFrameStats));
         memcpy(caller_out, out, out->struct_size);
@@ -1812,7 +1811,7 @@ int awsm_hip_read_visibility(AwsmHipCtx* c, uint64_t* keys_out) {
     if (!FB(c).vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_visibility before resize");
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
-    HIPCHK(c, hipMemcpy(keys_out, FB(c).vis.ptr, (size_t)c->width * c->height * (c->msaa == 4 ? 4 : 1) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(keys_out, FB(c).vis.ptr, (size_t)c->width * c->height * samples_of(c) * 8, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 
@@ -1820,7 +1819,7 @@ int awsm_hip_read_visibility(AwsmHipCtx* c, uint64_t* keys_out) {
 // diagnostic builds only: the geometry kernels' stamps of the last frame, [4 kernels][16384 workgroups][8] u64
 extern "C" int awsm_hip_debug_read_stamps(AwsmHipCtx* c, unsigned long long* out) {
     FrameDev f;
-    fill_frame(c, &f);
+    fill_frame(c, &f, frame_view(c));
     if (sync_all(c)) return AWSM_ERR_DEVICE;
     return hipMemcpy(out, f.stamps, 4ull * 16384 * 8 * 8, hipMemcpyDeviceToHost) == hipSuccess ? AWSM_OK : AWSM_ERR_DEVICE;
 }
@@ -1833,7 +1832,7 @@ int awsm_hip_read_gbuffer(AwsmHipCtx* c, float* out6) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
     FrameDev f;
-    fill_frame(c, &f);
+    fill_frame(c, &f, frame_view(c));
     const size_t bytes = (size_t)c->width * c->height * 6 * sizeof(float);
     float* dev = nullptr;
     HIPCHK(c, hipMalloc((void**)&dev, bytes));
@@ -1857,7 +1856,7 @@ int awsm_hip_visibility_digest(AwsmHipCtx* c, uint64_t* out2) {
     int rc = dev_reserve(c, c->digest, 16);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->digest.ptr, 0, 16, c->stream));
-    awsm_launch_vis_digest((const unsigned long long*)FB(c).vis.ptr, (size_t)c->width * c->height * (c->msaa == 4 ? 4 : 1), (unsigned long long*)c->digest.ptr, c->stream);
+    awsm_launch_vis_digest((const unsigned long long*)FB(c).vis.ptr, (size_t)c->width * c->height * samples_of(c), (unsigned long long*)c->digest.ptr, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out2, c->digest.ptr, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1867,13 +1866,14 @@ int awsm_hip_visibility_digest(AwsmHipCtx* c, uint64_t* out2) {
 int awsm_hip_read_visibility_unpacked(AwsmHipCtx* c, uint32_t* tri_id, uint32_t* meta_off, float* depth) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
     if (!FB(c).vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_visibility before resize");
-    const size_t n = (size_t)c->width * c->height * (c->msaa == 4 ? 4 : 1);
+    const size_t n = (size_t)c->width * c->height * samples_of(c);
     std::vector<uint64_t> keys(n);
     int rc = awsm_hip_read_visibility(c, keys.data());
     if (rc) return rc;
-    std::vector<uint32_t> meta(c->draws_host.size());
-    for (size_t d = 0; d < c->draws_host.size(); d++)
-        HIPCHK(c, hipMemcpy(&meta[d], (const uint8_t*)c->bufs[AWSM_BUF_GEOM_META].ptr + c->draws_host[d].geom_meta_off + 36, 4, hipMemcpyDeviceToHost));
+    const std::vector<DrawDev>& world_draws = c->lists[kPassWorld].draws;
+    std::vector<uint32_t> meta(world_draws.size());
+    for (size_t d = 0; d < world_draws.size(); d++)
+        HIPCHK(c, hipMemcpy(&meta[d], (const uint8_t*)c->bufs[AWSM_BUF_GEOM_META].ptr + world_draws[d].geom_meta_off + 36, 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) {
         if (keys[i] == ~0ull) {   // cleared texel: 0xFFFF per channel -> join32 == U32_MAX (geometry/render_pass.rs:22-30)
             if (tri_id) tri_id[i] = 0xFFFFFFFFu;
@@ -1882,9 +1882,9 @@ int awsm_hip_read_visibility_unpacked(AwsmHipCtx* c, uint32_t* tri_id, uint32_t*
             continue;
         }
         const uint32_t rank = 0xFFFFFFFFu - (uint32_t)(keys[i] & 0xFFFFFFFFull);
-        size_t lo = 0, hi = c->draws_host.size();
-        while (hi - lo > 1) { size_t mid = (lo + hi) / 2; if (c->draws_host[mid].first_tri <= rank) lo = mid; else hi = mid; }
-        if (tri_id) tri_id[i] = rank - c->draws_host[lo].first_tri;
+        size_t lo = 0, hi = world_draws.size();
+        while (hi - lo > 1) { size_t mid = (lo + hi) / 2; if (world_draws[mid].first_tri <= rank) lo = mid; else hi = mid; }
+        if (tri_id) tri_id[i] = rank - world_draws[lo].first_tri;
         if (meta_off) meta_off[i] = meta[lo];
         if (depth) { uint32_t b = (uint32_t)(keys[i] >> 32); memcpy(&depth[i], &b, 4); }
     }
@@ -1897,7 +1897,7 @@ int awsm_hip_pick(AwsmHipCtx* c, int32_t x, int32_t y, AwsmPick* out) {
     if (!c->bufs[AWSM_BUF_MATERIAL_META].ptr || !c->bufs[AWSM_BUF_GEOM_META].ptr) return fail(c, AWSM_ERR_NOT_READY, "pick: meta buffers missing");
     HIPCHK(c, hipSetDevice(c->device));
     FrameDev f;
-    fill_frame(c, &f);
+    fill_frame(c, &f, frame_view(c));
     int rc = sync_scene(c);
     if (rc) return rc;
     uint32_t* dev_out = (uint32_t*)FB(c).counters.ptr + 8;          // 4 words after the frame counters
@@ -1976,12 +1976,9 @@ int awsm_hip_set_editor_grid(AwsmHipCtx* c, const AwsmEditorGrid* g) {
     AwsmEditorGrid full;
     awsm_hip_editor_grid_defaults(&full);
     if (g) {
-        if (g->struct_size < 4u || g->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_editor_grid: AwsmEditorGrid.struct_size = %u (set it to sizeof(AwsmEditorGrid))", g->struct_size);
-        const size_t known = std::min<size_t>(g->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
-        memcpy((uint8_t*)&full + 4, (const uint8_t*)g + 4, known - 4);
-        const float* p = full.color_background;
-        for (size_t i = 0; i < sizeof(EditorGridDev::p) / 4; i++)
-            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_editor_grid: value %zu of the record is not finite", i);
+        int rc = merge_record(c, "set_editor_grid", "AwsmEditorGrid", g, &full, sizeof full);
+        if (!rc) rc = check_finite(c, "set_editor_grid", full.color_background, sizeof(EditorGridDev::p) / 4);
+        if (rc) return rc;
     }
     { int rcb = scene_write_barrier(c); if (rcb) return rcb; }      // scene state like any other; the pass itself carries the record it was enqueued with
     c->grid.on = g != nullptr;
@@ -2023,12 +2020,9 @@ int awsm_hip_set_ssao(AwsmHipCtx* c, const AwsmSsao* s) {
     AwsmSsao full;
     awsm_hip_ssao_defaults(&full);
     if (s) {
-        if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: AwsmSsao.struct_size = %u (set it to sizeof(AwsmSsao))", s->struct_size);
-        const size_t known = std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
-        memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, known - 4);
-        const float* p = &full.radius;
-        for (size_t i = 0; i < 4; i++)
-            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: value %zu of the record is not finite", i);
+        int rc = merge_record(c, "set_ssao", "AwsmSsao", s, &full, sizeof full);
+        if (!rc) rc = check_finite(c, "set_ssao", &full.radius, 4);
+        if (rc) return rc;
         if (!(full.radius > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: radius = %g (world units, > 0)", (double)full.radius);
         if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_ssao: strength = %g (0 .. 1)", (double)full.strength);
     }
@@ -2065,12 +2059,9 @@ int awsm_hip_set_selection(AwsmHipCtx* c, const AwsmSelection* s, const uint32_t
     AwsmSelection full;
     awsm_hip_selection_defaults(&full);
     if (s) {
-        if (s->struct_size < 4u || s->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: AwsmSelection.struct_size = %u (set it to sizeof(AwsmSelection))", s->struct_size);
-        const size_t known = std::min<size_t>(s->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
-        memcpy((uint8_t*)&full + 4, (const uint8_t*)s + 4, known - 4);
-        const float* p = full.outline_color;
-        for (size_t i = 0; i < 11; i++)
-            if (!std::isfinite(p[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: value %zu of the record is not finite", i);
+        int rc = merge_record(c, "set_selection", "AwsmSelection", s, &full, sizeof full);
+        if (!rc) rc = check_finite(c, "set_selection", full.outline_color, 11);      // two colours and three parameters, contiguous
+        if (rc) return rc;
         if (full.flags & ~(AWSM_SELECTION_OUTLINE | AWSM_SELECTION_BOXES)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: unknown flags 0x%x", full.flags);
         if (full.outline_radius < 1u || full.outline_radius > (uint32_t)selection::kMaxRadius) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: outline_radius = %u (1 .. %d pixels)", full.outline_radius, selection::kMaxRadius);
         if (!(full.box_half_width > 0.0f && full.box_half_width <= selection::kMaxHalfWidth)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_selection: box_half_width = %g (pixels, above 0, at most %g)", (double)full.box_half_width, (double)selection::kMaxHalfWidth);
@@ -2138,9 +2129,7 @@ int awsm_hip_set_taa(AwsmHipCtx* c, const AwsmTaa* t) {
     }
     AwsmTaa full;
     awsm_hip_taa_defaults(&full);
-    if (t->struct_size < 4u || t->struct_size > 4096u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: AwsmTaa.struct_size = %u (set it to sizeof(AwsmTaa))", t->struct_size);
-    const size_t known = std::min<size_t>(t->struct_size, sizeof full) & ~(size_t)3;      // whole fields only
-    memcpy((uint8_t*)&full + 4, (const uint8_t*)t + 4, known - 4);
+    { const int rcm = merge_record(c, "set_taa", "AwsmTaa", t, &full, sizeof full); if (rcm) return rcm; }
     if (!std::isfinite(full.feedback) || !(full.feedback > 0.0f && full.feedback <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: feedback = %g (0 < feedback <= 1)", (double)full.feedback);
     if (full.flags & ~AWSM_TAA_RESET) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: unknown flags 0x%x", full.flags);
     for (int i = 0; i < 2; i++) if (!std::isfinite(full.jitter_ndc[i])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "set_taa: jitter_ndc[%d] is not finite", i);
@@ -2167,7 +2156,7 @@ int awsm_hip_read_taa(AwsmHipCtx* c, uint16_t* resolved, float* lookup_xy, uint8
         TaaArgs t = c->taa_args;
         t.layer_xy = (float*)c->taa_layers.ptr; t.layer_used = (uint8_t*)(t.layer_xy + 2 * px);
         t.poison = nullptr;
-        awsm_launch_taa_layers(&t, c->msaa == 4 ? 4u : 1u, c->stream);
+        awsm_launch_taa_layers(&t, samples_of(c), c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (lookup_xy) HIPCHK(c, hipMemcpy(lookup_xy, t.layer_xy, px * 8, hipMemcpyDeviceToHost));
@@ -2182,8 +2171,7 @@ int awsm_hip_post_pass(AwsmHipCtx* c, const AwsmPostParams* p) {
     if (p->struct_size != sizeof(AwsmPostParams)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: struct_size %u, this library's AwsmPostParams is %zu bytes", p->struct_size, sizeof(AwsmPostParams));
     if (p->tonemapping > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: tonemapping %u (0 None, 1 KhronosNeutralPbr, 2 Aces)", p->tonemapping);
     if (p->flags & ~(AWSM_POST_SMAA | AWSM_POST_BLOOM | AWSM_POST_DOF)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "post_pass: unknown flags 0x%x", p->flags);
-    const bool sharded = c->band_n > 1 || (c->y1 != 0 && !(c->y0 == 0 && c->y1 >= c->height));
-    if (sharded) return fail(c, AWSM_ERR_UNSUPPORTED, "post_pass on a sharded context: the SMAA / bloom / DoF stencils read neighbouring rows (no halo exchange)");
+    if (is_sharded(c)) return fail(c, AWSM_ERR_UNSUPPORTED, "post_pass on a sharded context: the SMAA / bloom / DoF stencils read neighbouring rows (no halo exchange)");
     if (c->width == 0 || !c->geometry_done || !c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "post_pass needs the frame's opaque pass first");
     // temporal anti-aliasing (awsm_hip_set_taa): this pass carries the record as it stands now, into a replay too
     if (c->taa.on && (c->taa.flags & AWSM_TAA_RESET)) { c->taa_have = false; c->taa_serial = 0; c->taa.flags &= ~AWSM_TAA_RESET; }      // one pass, then cleared
@@ -2209,8 +2197,8 @@ static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& pp) {
     if (c->transparent_done) a.src = (const uint2*)(c->bound_comp ? c->bound_comp : c->comp16.ptr);
     else a.src = (const uint2*)(c->bound_out ? (const uint8_t*)c->bound_out - (size_t)c->out_first_row * c->width * 8 : (const uint8_t*)c->out16[c->slot].ptr);
     a.vis = (const unsigned long long*)FB(c).vis.ptr;       // the world's keys (not the merged hud ones): hud_depth plays no part
-    const FrameBufs& t = c->tr[c->slot];
-    if (dof && c->transparent_done && c->tr_total_tris[0] && t.frag_first.ptr) {
+    const FrameBufs& t = pass_bufs(c, kPassTransparent);
+    if (dof && c->transparent_done && c->lists[kPassTransparent].total_tris && t.frag_first.ptr) {
         a.frag_first = (const uint32_t*)t.frag_first.ptr; a.frag_rec = (const uint4*)t.frag_rec.ptr; a.frag_cap = t.frag_cap; a.tri_rec = (const TriRec*)t.tri_rec.ptr;
     }
     a.camera = (const float*)FB(c).camera.ptr;
@@ -2240,11 +2228,11 @@ static int enqueue_post(AwsmHipCtx* c, const AwsmPostParams& pp) {
         t.out = (uint2*)c->taa_img[c->taa_cur].ptr;
         memcpy(t.reproject, ts.reproject, sizeof t.reproject); t.jitter[0] = ts.jitter[0]; t.jitter[1] = ts.jitter[1]; t.feedback = ts.feedback;
         t.poison = a.poison; t.frame_serial = a.frame_serial;
-        awsm_launch_taa(&t, c->msaa == 4 ? 4u : 1u, ss);
+        awsm_launch_taa(&t, samples_of(c), ss);
         a.src = t.out;
         c->taa_args = t; c->taa_have = true; c->taa_resolved = true;
     }
-    awsm_launch_post(&a, p->flags, c->msaa == 4 ? 4u : 1u, c->bloom_a.ptr, c->bloom_b.ptr, ss);
+    awsm_launch_post(&a, p->flags, samples_of(c), c->bloom_a.ptr, c->bloom_b.ptr, ss);
     HIPCHK(c, hipGetLastError());
     if (c->overlap) HIPCHK(c, mark_shade_done(c, ss));       // the slot's next geometry pass waits for this too
     c->last_display = a.display;
@@ -2280,39 +2268,32 @@ int awsm_hip_bind_display(AwsmHipCtx* c, void* device_ptr, size_t bytes) {
 
 void* awsm_hip_display_device_ptr(AwsmHipCtx* c) { return c ? c->last_display : nullptr; }
 
-int awsm_hip_read_transformed_forward(AwsmHipCtx* c, float* clip_out, float* nt_out, float* wpos_out, uint32_t max_vertices) {
-    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
-    if (!c->transparent_done) return fail(c, AWSM_ERR_NOT_READY, "read_transformed_forward before transparent_pass");
-    const uint32_t n = std::min(max_vertices, 3u * c->tr_total_tris[0]);
+// the first n transformed vertices of a pass: clip positions, world N and T interleaved, world positions (the transparent passes keep them)
+static int read_pass_vertices(AwsmHipCtx* c, const FrameBufs& b, uint32_t n, float* clip_out, float* nt_out, float* wpos_out) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
     if (n == 0) return AWSM_OK;
-    if (clip_out) HIPCHK(c, hipMemcpy(clip_out, TR(c).clip.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (wpos_out) HIPCHK(c, hipMemcpy(wpos_out, TR(c).wpos.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (clip_out) HIPCHK(c, hipMemcpy(clip_out, b.clip.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (wpos_out) HIPCHK(c, hipMemcpy(wpos_out, b.wpos.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
     if (nt_out) {
         std::vector<float> nn((size_t)n * 4), tt((size_t)n * 4);
-        HIPCHK(c, hipMemcpy(nn.data(), TR(c).nrm.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(tt.data(), TR(c).tan.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(nn.data(), b.nrm.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(tt.data(), b.tan.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) { memcpy(nt_out + i * 8, &nn[i * 4], 16); memcpy(nt_out + i * 8 + 4, &tt[i * 4], 16); }
     }
     return AWSM_OK;
 }
 
+int awsm_hip_read_transformed_forward(AwsmHipCtx* c, float* clip_out, float* nt_out, float* wpos_out, uint32_t max_vertices) {
+    if (!c) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!c->transparent_done) return fail(c, AWSM_ERR_NOT_READY, "read_transformed_forward before transparent_pass");
+    return read_pass_vertices(c, pass_bufs(c, kPassTransparent), std::min(max_vertices, 3u * c->lists[kPassTransparent].total_tris), clip_out, nt_out, wpos_out);
+}
+
 int awsm_hip_read_transformed(AwsmHipCtx* c, float* clip_out, float* nt_out, uint32_t max_vertices) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
     if (!c->geometry_done) return fail(c, AWSM_ERR_NOT_READY, "read_transformed before geometry_pass");
-    const uint32_t n = std::min(max_vertices, c->total_verts);
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rcs = sync_all(c); if (rcs) return rcs; }
-    if (n == 0) return AWSM_OK;
-    if (clip_out) HIPCHK(c, hipMemcpy(clip_out, FB(c).clip.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (nt_out) {
-        std::vector<float> nn((size_t)n * 4), tt((size_t)n * 4);
-        HIPCHK(c, hipMemcpy(nn.data(), FB(c).nrm.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(tt.data(), FB(c).tan.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++) { memcpy(nt_out + i * 8, &nn[i * 4], 16); memcpy(nt_out + i * 8 + 4, &tt[i * 4], 16); }
-    }
-    return AWSM_OK;
+    return read_pass_vertices(c, FB(c), std::min(max_vertices, 3u * c->lists[kPassWorld].total_tris), clip_out, nt_out, nullptr);
 }
 
 }  // extern "C"

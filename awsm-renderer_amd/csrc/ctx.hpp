@@ -26,7 +26,16 @@ struct DevBuf {
 enum { EV_START = 0, EV_TRANSFORM, EV_BIN, EV_RASTER, EV_SHADE_BEGIN, EV_SHADE_LEAN, EV_SHADE, EV_FWD_BEGIN, EV_FWD, EV_COUNT };
 
 // Which pass a FrameBufs serves: AwsmHipCtx::fb, tr, hud, htr, shadow in that order (set once by awsm_hip_create).
+// A pass is named by its kind everywhere on the host: pass_bufs(c, kind) is its device state in the current frame slot, AwsmHipCtx::lists[kind] its draw list.
 enum PassKind : uint8_t { kPassWorld = 0, kPassTransparent, kPassHud, kPassHudTransparent, kPassShadow };
+constexpr int kPassKinds = 5;
+
+// What the host knows of a pass's draws in the current frame: one DrawDev per (draw, instance) with the running triangle / block prefix sums
+// (build_draw_list), their totals (vertices: 3 * total_tris), and the k_deform_transform workgroups they take.
+struct PassList {
+    std::vector<DrawDev> draws;
+    uint32_t total_tris = 0, n_blocks = 0;
+};
 
 // Everything the geometry pass produces for one frame and the opaque pass consumes.
 struct FrameBufs {
@@ -162,8 +171,6 @@ struct AwsmHipCtx {
     FrameBufs fb[kSlots];             // per-frame device state; two slots when frames overlap (AWSM_CFG_OVERLAP_FRAMES), else slot 0 only
     FrameBufs tr[kSlots];             // the same for the transparent pass's own draws (vertices, setup records, bins); no visibility buffer
     FrameBufs hud[kSlots];            // ... and for the HUD geometry pass (render.rs:169-178): its own vertices, bins and visibility keys (= hud_depth + the hud triangles)
-    std::vector<DrawDev> hud_draws_host;
-    uint32_t hud_total_tris = 0, hud_n_blocks = 0;
     bool hud_geometry_done = false;   // this frame has hud geometry: the opaque pass leaves its pixels cleared
     // MSAA frames: the hud draws follow the world's in ONE rank space (transformed into the world pass's vertex / setup arrays behind the world's, binned and
     // rasterised by themselves into hud[slot].vis), and the opaque pass reads the merged keys (k_hud_merge: hud rank under world depth) — what the
@@ -171,11 +178,8 @@ struct AwsmHipCtx {
     bool hud_merged = false;
     DevBuf merged_vis[kSlots];
     std::vector<DrawDev> hud_combined;   // world draws, then the hud draws with first_tri / first_block continued
-    bool hud_transparent = false;     // the transparent pass being enqueued is the HUD one (depth cleared, colours loaded from the composite)
-    // [0] the world transparent pass, [1] the HUD transparent pass: each with its own per-slot device state (tr / htr) — the HUD pass of a frame is enqueued
-    // while the world pass of the same frame may not have started on the shade stream, so they share neither a draw list nor counters
-    std::vector<DrawDev> tr_draws_host[2];
-    uint32_t tr_total_tris[2] = {0, 0}, tr_n_blocks[2] = {0, 0};
+    // the world transparent pass and the HUD transparent pass: each with its own per-slot device state (tr / htr) and its own list — the HUD pass of a
+    // frame is enqueued while the world pass of the same frame may not have started on the shade stream, so they share neither a draw list nor counters
     bool transparent_done = false, hud_transparent_done = false;
     FrameBufs htr[kSlots];
     // the editor's ground grid (awsm_hip_set_editor_grid): what the caller last set, and per frame slot what the slot's world transparent pass was
@@ -210,9 +214,8 @@ struct AwsmHipCtx {
     const void* opaque_src = nullptr;      // awsm_hip_bind_opaque_source: the gathered full-frame opaque image (sharded transparent pass)
     size_t opaque_src_bytes = 0;
     int slot = 0;
-    std::vector<DrawDev> draws_host;
+    PassList lists[kPassKinds];       // by PassKind: the draws each pass of the current frame was given
     std::vector<AwsmDraw> draws_api;
-    uint32_t total_tris = 0, total_verts = 0, n_blocks = 0;
     bool geometry_done = false, opaque_done = false;
     AwsmOpaqueParams last_opaque{};
     uint32_t overflow_retries = 0;
@@ -250,8 +253,6 @@ struct AwsmHipCtx {
     DevScene* shadow_scene[kSlots] = {};
     uint64_t shadow_scene_seq[kSlots] = {}, scene_uploads = 0;
     DevBuf shadow_cam[kSlots];
-    std::vector<DrawDev> shadow_draws_host;
-    uint32_t shadow_total_tris = 0, shadow_n_blocks = 0;
     bool shadow_done = false;        // this frame had a shadow pass
     struct ShadowState { bool on = false; AwsmShadow p{}; float light_view_proj[16] = {}; } shadow_pass[kSlots];
     DevBuf shadow_layers[kSlots];    // per slot [2][px] f32: V, m

@@ -139,6 +139,10 @@ struct TriRec;                                   // raster_setup.hpp (device sid
 constexpr size_t kTriRecBytes = 80;
 constexpr uint32_t kMaxDirtyRanges = 12;
 
+// The words of FrameDev::counters, one set per pass and frame slot (the host reads them by these names: awsm_hip_frame_end).  Words 8..11 of the
+// world pass's set are the picker's, 12 and 13 k_bin_scan's arrival counter and ready flag.
+enum CounterWord : uint32_t { kCtrBinned = 0, kCtrEntries, kCtrOverflow, kCtrCovered, kCtrBig, kCtrFragments, kCtrFragOverflow, kCtrExtraItems, kCtrWords };
+
 struct FrameDev {
     uint32_t width, height;
     uint32_t y0, y1;              // rows the geometry pass rasterises: the shard's rows [sy0, sy1), plus one halo row on each side with MSAA
