@@ -565,7 +565,11 @@ int enqueue_opaque(AwsmHipCtx* c) {
     const AwsmHipCtx::ShadowState& sh = c->shadow_pass[c->slot];
     if (sh.on && c->shadow_px[c->slot] && f.has_opaque && f.sy1 > f.sy0) {
         const size_t px = (size_t)c->width * c->height;
-        ShadowArgs a{};
+        ShadowViewsArgs av{};      // (the launch wrapper is handed the leading member: frame_params.hpp)
+        ShadowArgs& a = av.base;
+        const AwsmHipCtx::ShadowViews& views = c->shadow_views[c->slot];
+        av.n_views = views.n; av.view = (unsigned char*)c->shadow_view_layers[c->slot].ptr;
+        memcpy(av.view_proj, views.view_proj, sizeof av.view_proj);
         a.width = c->width; a.height = c->height;
         a.vis = (const unsigned long long*)FB(c).vis.ptr;       // the WORLD's keys (see below)
         a.camera = (const float*)f.camera;
@@ -1029,7 +1033,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->taa_img) fr(b); fr(c->taa_layers);
     for (auto& b : c->sel_tables) fr(b);
     fr(c->sel_layers);
-    for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
+    for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (auto& b : c->shadow_view_ctr) fr(b); for (auto& b : c->shadow_view_layers) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < kPassKinds * kSlots; k++) {
         FrameBufs& b = pass_slots(c, (PassKind)(k / kSlots))[k % kSlots];
@@ -1291,6 +1295,7 @@ int awsm_hip_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n) {
     }
     ht.mark("geometry_pass: slot-free wait");
     c->shadow_done = false; c->shadow_pass[c->slot].on = false; c->shadow_px[c->slot] = 0;      // no shadow pass in a frame: no shadow in that frame
+    c->shadow_views[c->slot].n = 0;
     c->draws_api.assign(draws, draws + n);
     PassList& world = c->lists[kPassWorld];
     world.draws.swap(new_draws);
@@ -1514,8 +1519,152 @@ int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_c
     if ((rc = dev_reserve(c, sb.vis, (size_t)full.map_size * full.map_size * 8))) return rc;
     if ((rc = reserve_pass_buffers(c, sb, cast.draws, cast.total_tris, false))) return rc;
     if ((rc = upload_small(c, c->shadow_cam[c->slot].ptr, light_camera, 512))) return rc;      // through the pinned ring, as small writes are
+    c->shadow_views[c->slot].n = 0;      // (one map, k_shadow_resolve: not a pass of views)
     if ((rc = enqueue_shadow(c))) return rc;
     st.on = true; c->shadow_done = true;
+    return AWSM_OK;
+}
+
+// ---- several views of one light ----
+// enqueue_shadow's chain once per view, in the views' order on the caller's stream, into layer i of the slot's stack of maps.  The views share the
+// shadow pass's vertex arrays, setup records, tile tables and lists; in front of each view's kernels its draw list goes into the pass's list buffer
+// and a scene table whose camera entry is the view's block into the slot's second table.  Each view counts its overflow in words of its own.
+static int enqueue_shadow_views(AwsmHipCtx* c) {
+    FrameBufs& sb = pass_bufs(c, kPassShadow);
+    const AwsmHipCtx::ShadowViews& views = c->shadow_views[c->slot];
+    const uint32_t S = c->shadow_pass[c->slot].p.map_size;
+    int rc;
+    if ((rc = sync_scene(c))) return rc;
+    c->shadow_scene_seq[c->slot] = ~0ull;      // the slot's second table is rewritten per view: awsm_hip_shadow_pass makes its own copy anew
+    for (uint32_t i = 0; i < views.n; i++) {
+        const PassList& casters = views.lists[i];
+        const uint8_t* const block = (const uint8_t*)c->shadow_cam[c->slot].ptr + (size_t)i * 512;
+        uint32_t* const counters = (uint32_t*)c->shadow_view_ctr[c->slot].ptr + (size_t)i * 16;
+        if ((rc = upload_draw_list(c, sb, casters.draws, false))) return rc;
+        FrameDev f;
+        memset(&f, 0, sizeof f);
+        f.width = S; f.height = S; f.y0 = 0; f.y1 = S; f.sy0 = 0; f.sy1 = S;
+        f.tiles_x = (S + kTile - 1) / kTile; f.tiles_y = f.tiles_x; f.tile_row0 = 0;
+        f.band_n = 1; f.band_r = 0; f.out_compact = 0;
+        f.n_draws = (uint32_t)casters.draws.size();
+        f.total_tris = casters.total_tris; f.total_verts = 3u * casters.total_tris;
+        f.msaa = 0;
+        f.camera = block;
+        bind_pass(f, sb);
+        f.counters = counters;
+        f.vis = (unsigned long long*)sb.vis.ptr + (size_t)i * S * S;
+        f.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
+        f.frame_serial = c->frame_serial;
+        DevScene sc = c->scene;
+        sc.buf[AWSM_BUF_CAMERA] = block;
+        if ((rc = upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc))) return rc;
+        const uint32_t n_tiles = f.tiles_x * f.tiles_y;
+        if (!f.total_tris) {      // clear_empty_pass, on the view's own counters
+            HIPCHK(c, hipMemsetAsync(counters, 0, kCtrWords * sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(counters + 12, 0, 2 * sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(sb.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), c->stream));
+        } else awsm_launch_transform(c->shadow_scene[c->slot], &f, casters.n_blocks, c->stream);
+        enqueue_binning(f, f.total_tris != 0, c->stream);
+        awsm_launch_raster(&f, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    return AWSM_OK;
+}
+
+int awsm_hip_shadow_pass_views(AwsmHipCtx* c, const AwsmShadow* s, const AwsmShadowView* views, uint32_t n_views) {
+    if (!c || !s) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!views || n_views < 1u || n_views > (uint32_t)AWSM_SHADOW_MAX_VIEWS)
+        return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: %u views at %p (1 .. %d views)", n_views, (const void*)views, AWSM_SHADOW_MAX_VIEWS);
+    if (!c->geometry_done || c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass_views goes between the geometry pass and the opaque pass of a frame");
+    if (is_sharded(c))
+        return fail(c, AWSM_ERR_UNSUPPORTED, "shadow_pass_views on a sharded context: the resolve's neighbours need rows the shard never rasterised (no halo exchange)");
+    AwsmShadow full;
+    awsm_hip_shadow_defaults(&full);
+    { const int rcm = merge_record(c, "shadow_pass_views", "AwsmShadow", s, &full, sizeof full); if (rcm) return rcm; }
+    { const int rcf = check_finite(c, "shadow_pass_views", full.light, 9); if (rcf) return rcf; }
+    if (full.map_size < 1u || full.map_size > 8192u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: map_size = %u (1 .. 8192)", full.map_size);
+    if (full.pcf_radius > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: pcf_radius = %u (0, 1 or 2)", full.pcf_radius);
+    if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: strength = %g (0 .. 1)", (double)full.strength);
+    if (!(full.facing_fade > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: facing_fade = %g (> 0)", (double)full.facing_fade);
+    if (!(full.max_slope >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: max_slope = %g (>= 0)", (double)full.max_slope);
+    if (full.light[3] != 0.0f && full.light[3] != 1.0f) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: light[3] = %g (0: directional, 1: positional)", (double)full.light[3]);
+    float lvp[AWSM_SHADOW_MAX_VIEWS][16];
+    uint8_t blocks_host[AWSM_SHADOW_MAX_VIEWS * 512];
+    bool any_casters = false;
+    for (uint32_t i = 0; i < n_views; i++) {
+        const AwsmShadowView& v = views[i];
+        if (!v.casters && v.n_casters) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u has %u casters at a null pointer", i, v.n_casters);
+        if (!v.light_camera || v.camera_bytes != 512)
+            return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", i, v.camera_bytes);
+        memcpy(blocks_host + (size_t)i * 512, v.light_camera, 512);
+        memcpy(lvp[i], (const uint8_t*)v.light_camera + 128, sizeof lvp[i]);
+        for (float m : lvp[i]) if (!std::isfinite(m)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u: the light camera's view_proj is not finite", i);
+        any_casters |= v.n_casters != 0;
+    }
+    static const AwsmBuf need[] = {AWSM_BUF_TRANSFORMS, AWSM_BUF_GEOM_META, AWSM_BUF_VIS_GEOM_DATA};
+    if (any_casters) for (AwsmBuf b : need) if (!c->bufs[b].ptr) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass_views: buffer %d missing", (int)b);
+    HIPCHK(c, hipSetDevice(c->device));
+    PassList lists[AWSM_SHADOW_MAX_VIEWS];
+    for (uint32_t i = 0; i < n_views; i++) {
+        char name[40];
+        snprintf(name, sizeof name, "shadow_pass_views: view %u", i);
+        uint64_t tris = 0, blocks = 0;
+        const int rcl = build_draw_list(c, name, views[i].casters, views[i].n_casters, AWSM_BUF_VIS_GEOM_DATA, 168u, lists[i].draws, &tris, &blocks);
+        if (rcl) return rcl;
+        lists[i].total_tris = (uint32_t)tris; lists[i].n_blocks = (uint32_t)blocks;
+    }
+    // nothing refused from here on but for memory: the slot's state is this pass's
+    FrameBufs& sb = pass_bufs(c, kPassShadow);
+    AwsmHipCtx::ShadowState& st = c->shadow_pass[c->slot];
+    AwsmHipCtx::ShadowViews& vs = c->shadow_views[c->slot];
+    c->shadow_done = false; st.on = false;
+    st.p = full; memcpy(st.light_view_proj, lvp[0], sizeof st.light_view_proj);
+    vs.n = n_views; memcpy(vs.view_proj, lvp, sizeof vs.view_proj);
+    for (uint32_t i = 0; i < n_views; i++) { vs.lists[i].draws.swap(lists[i].draws); vs.lists[i].total_tris = lists[i].total_tris; vs.lists[i].n_blocks = lists[i].n_blocks; }
+    c->lists[kPassShadow] = PassList();
+    int rc;
+    if (!sb.counters.ptr) {      // (the pass's own words, as awsm_hip_shadow_pass makes them: a later pass through it finds them)
+        HIPCHK(c, hipMalloc(&sb.counters.ptr, 16 * sizeof(uint32_t)));
+        sb.counters.size = 16 * sizeof(uint32_t);
+        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, sb.counters.size, c->stream));
+    }
+    DevBuf& ctr = c->shadow_view_ctr[c->slot];
+    if (!ctr.ptr) {
+        HIPCHK(c, hipMalloc(&ctr.ptr, AWSM_SHADOW_MAX_VIEWS * 16 * sizeof(uint32_t)));
+        ctr.size = AWSM_SHADOW_MAX_VIEWS * 16 * sizeof(uint32_t);
+        HIPCHK(c, hipMemsetAsync(ctr.ptr, 0, ctr.size, c->stream));
+    }
+    if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
+    if ((rc = dev_reserve(c, c->shadow_cam[c->slot], (size_t)AWSM_SHADOW_MAX_VIEWS * 512))) return rc;
+    if ((rc = dev_reserve(c, sb.vis, (size_t)n_views * full.map_size * full.map_size * 8))) return rc;
+    for (uint32_t i = 0; i < n_views; i++)      // grow-only: the arrays end up sized for the largest view
+        if ((rc = ensure_pass_capacity(c, sb, vs.lists[i].draws, vs.lists[i].total_tris, false))) return rc;
+    if ((rc = upload_small(c, c->shadow_cam[c->slot].ptr, blocks_host, (size_t)n_views * 512))) return rc;
+    if ((rc = enqueue_shadow_views(c))) return rc;
+    st.on = true; c->shadow_done = true;
+    return AWSM_OK;
+}
+
+int awsm_hip_read_shadow_map_view(AwsmHipCtx* c, uint32_t view, uint64_t* keys) {
+    if (!c || !keys) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!c->shadow_done || !c->shadow[c->slot].vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_shadow_map_view: the last submitted frame had no shadow pass");
+    const uint32_t n = std::max(c->shadow_views[c->slot].n, 1u);
+    if (view >= n) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "read_shadow_map_view: view %u of a pass with %u", view, n);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    const size_t S = c->shadow_pass[c->slot].p.map_size;
+    HIPCHK(c, hipMemcpy(keys, (const uint64_t*)c->shadow[c->slot].vis.ptr + (size_t)view * S * S, S * S * 8, hipMemcpyDeviceToHost));
+    return AWSM_OK;
+}
+
+int awsm_hip_read_shadow_view(AwsmHipCtx* c, uint8_t* view_out) {
+    if (!c || !view_out) return AWSM_ERR_INVALID_ARGUMENT;
+    const size_t px = (size_t)c->width * c->height;
+    if (!px || !c->shadow_done || !c->opaque_done || c->shadow_px[c->slot] != px || !c->shadow_views[c->slot].n || c->shadow_view_layers[c->slot].size < px)
+        return fail(c, AWSM_ERR_NOT_READY, "read_shadow_view: the last submitted frame had no shadow_pass_views with an opaque pass (has_opaque) behind it");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcs = sync_all(c); if (rcs) return rcs; }
+    HIPCHK(c, hipMemcpy(view_out, c->shadow_view_layers[c->slot].ptr, px, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 
@@ -1570,6 +1719,7 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     // shadows: the frame had a shadow pass (awsm_hip_shadow_pass) — its resolve goes behind this pass's shading kernels; V and m per frame slot, allocated at the first use
     const bool shadow_on = c->shadow_done && c->shadow_pass[c->slot].on && p->has_opaque;
     if (shadow_on) { const int rcs = dev_reserve(c, c->shadow_layers[c->slot], (size_t)c->width * c->height * 8); if (rcs) return rcs; }
+    if (shadow_on && c->shadow_views[c->slot].n) { const int rcs = dev_reserve(c, c->shadow_view_layers[c->slot], (size_t)c->width * c->height); if (rcs) return rcs; }
     c->shadow_px[c->slot] = shadow_on ? (size_t)c->width * c->height : 0;
     c->last_opaque = *p;
     if (!p->has_opaque && c->camera_written_since_snapshot && c->bufs[AWSM_BUF_CAMERA].ptr) {
@@ -1716,6 +1866,15 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         { int rch = handoff_check(c); if (rch) return rch; }      // a gate ended unopened: the frame it guarded was dropped
         memset(c->counters_host + 8, 0, 8 * sizeof(uint32_t));
         uint32_t hud_fwd[kCtrWords] = {}, hud_geo[kCtrWords] = {}, shadow_geo[kCtrWords] = {};      // the HUD transparent pass's, the HUD geometry pass's and the shadow pass's own counters (same layout)
+        const uint32_t shadow_n_views = c->shadow_done ? c->shadow_views[c->slot].n : 0u;
+        if (shadow_n_views) {      // a pass of views: the largest need of any view, and whether any view lost entries
+            uint32_t per_view[AWSM_SHADOW_MAX_VIEWS][16];
+            HIPCHK(c, hipMemcpy(per_view, c->shadow_view_ctr[c->slot].ptr, (size_t)shadow_n_views * sizeof per_view[0], hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < shadow_n_views; i++) {
+                shadow_geo[kCtrEntries] = std::max(shadow_geo[kCtrEntries], per_view[i][kCtrEntries]);
+                shadow_geo[kCtrOverflow] |= per_view[i][kCtrOverflow];
+            }
+        } else
         if (c->shadow_done) HIPCHK(c, hipMemcpy(shadow_geo, pass_bufs(c, kPassShadow).counters.ptr, sizeof shadow_geo, hipMemcpyDeviceToHost));
         if (c->transparent_done) HIPCHK(c, hipMemcpy(c->counters_host + 8, pass_bufs(c, kPassTransparent).counters.ptr, kCtrWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (c->hud_transparent_done) HIPCHK(c, hipMemcpy(hud_fwd, pass_bufs(c, kPassHudTransparent).counters.ptr, sizeof hud_fwd, hipMemcpyDeviceToHost));
@@ -1741,7 +1900,7 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         }
         if (shadow_over) {      // the light's pass, in its place between the geometry passes and the opaque pass; the light block is still in the slot's copy
             if ((rc = grow_after_overflow(c, pass_bufs(c, kPassShadow), shadow_geo))) return rc;
-            if ((rc = enqueue_shadow(c))) return rc;
+            if ((rc = shadow_n_views ? enqueue_shadow_views(c) : enqueue_shadow(c))) return rc;      // (every view again, in order)
         }
         if ((geom_over || hud_geo_over || shadow_over) && c->opaque_done && (rc = enqueue_opaque(c))) return rc;
         // (the transparent passes have a tile kernel of their own: no raster items to size with their lists)

@@ -276,6 +276,18 @@ struct AwsmHipCtx {
     uint32_t taa_serial = 0;
     bool taa_resolved = false;       // the last post pass resolved (awsm_hip_read_taa)
     TaaArgs taa_args{};              // ... with these arguments
+
+    // shadows from several views (awsm_hip_shadow_pass_views).  shadow_views[slot].n: the views of the slot's pass, 0 when it came
+    // through awsm_hip_shadow_pass.  With views, shadow[slot].vis is a stack of n layers of S x S keys, and the views share shadow[slot]'s vertex
+    // arrays, setup records, tile tables and lists — they run one after another on the caller's stream; what each view has of its own: its draw list
+    // (uploaded in front of its kernels, again in a replay), its block (shadow_cam[slot] holds n of them), and its 16 counter words in
+    // shadow_view_ctr[slot].  shadow_view_layers[slot]: one byte per pixel, the view k_shadow_resolve_views took.
+    struct ShadowViews {
+        uint32_t n = 0;
+        float view_proj[AWSM_SHADOW_MAX_VIEWS][16] = {};
+        PassList lists[AWSM_SHADOW_MAX_VIEWS];
+    } shadow_views[kSlots];
+    DevBuf shadow_view_ctr[kSlots], shadow_view_layers[kSlots];
 };
 
 #define HIPCHK(c, call)                                                                            \

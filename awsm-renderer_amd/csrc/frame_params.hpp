@@ -322,6 +322,17 @@ struct ShadowArgs {
     uint32_t frame_serial;
 };
 
+// Shadows from several views of one light (awsm_hip_shadow_pass_views).  awsm_launch_shadow_resolve is always handed the address of
+// this record's leading member.  n_views == 0: the frame's pass came through awsm_hip_shadow_pass and k_shadow_resolve receives `base` alone, the
+// bytes it always received.  Otherwise k_shadow_resolve_views receives the whole record: base.map is then a stack of n_views layers of S x S keys,
+// view_proj[i] is bytes 128..191 of view i's block, and base.light_view_proj is not read.
+struct ShadowViewsArgs {
+    ShadowArgs base;
+    uint32_t n_views;                    // 0, or 1 .. shadow::kMaxViews
+    unsigned char* view;                 // per pixel, per frame slot: the view the pixel was resolved in, shadow::kNoView = none
+    float view_proj[AWSM_SHADOW_MAX_VIEWS][16];
+};
+
 // Temporal anti-aliasing (kernels_taa.hip, awsm_hip_set_taa): what k_taa_resolve, enqueued in front of a post pass, and k_taa_layers, run by
 // awsm_hip_read_taa, read and write.
 struct TaaArgs {

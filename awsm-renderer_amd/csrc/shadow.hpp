@@ -10,6 +10,8 @@ constexpr int kWin = kTile + 2;       // 18: the tile and a one-pixel apron, sta
 constexpr int kMaxRadius = 2;         // R <= 2: at most 5x5 taps
 constexpr float kDetMin = 1e-12f;     // |det| of the receiver plane's 2x2 system below which the plane counts as flat
 constexpr unsigned kHit = 1u, kInside = 2u;      // a staged cell's flags
+constexpr int kMaxViews = 6;          // views of one light in a frame (AWSM_SHADOW_MAX_VIEWS): a cube's faces, or up to that many cascades
+constexpr unsigned kNoView = 255u;    // the view layer's byte of a pixel that lies in no view
 
 }  // namespace shadow
 }  // namespace awsm

@@ -43,6 +43,7 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_editor_grid_defaults", "awsm_hip_set_editor_grid", "awsm_hip_read_editor_grid",
            "awsm_hip_ssao_defaults", "awsm_hip_set_ssao", "awsm_hip_read_ssao",
            "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow",
+           "awsm_hip_shadow_pass_views", "awsm_hip_read_shadow_map_view", "awsm_hip_read_shadow_view",
            "awsm_hip_selection_defaults", "awsm_hip_set_selection", "awsm_hip_read_selection",
            "awsm_hip_taa_defaults", "awsm_hip_set_taa", "awsm_hip_read_taa"]
 
@@ -137,6 +138,15 @@ class AwsmShadow(C.Structure):
             else:
                 setattr(self, k, int(v) if k in ("map_size", "pcf_radius") else float(v))
         return self
+
+
+AWSM_SHADOW_MAX_VIEWS = 6
+SHADOW_NO_VIEW = 255      # read_shadow_view's byte of a pixel that lies in no view
+
+
+class AwsmShadowView(C.Structure):
+    """One view of awsm_hip_shadow_pass_views: a 512-byte light block and the draws that cast in it."""
+    _fields_ = [("light_camera", C.c_void_p), ("camera_bytes", C.c_size_t), ("casters", C.c_void_p), ("n_casters", C.c_uint32)]
 
 
 AWSM_SELECTION_OUTLINE, AWSM_SELECTION_BOXES = 1, 2
@@ -349,6 +359,9 @@ def load_library():
     lib.awsm_hip_shadow_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
     lib.awsm_hip_read_shadow_map.argtypes = [C.c_void_p, C.c_void_p]
     lib.awsm_hip_read_shadow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.awsm_hip_shadow_pass_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.awsm_hip_read_shadow_map_view.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.awsm_hip_read_shadow_view.argtypes = [C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -725,15 +738,44 @@ class HipDevice:
         self._chk(self.lib.awsm_hip_shadow_pass(self.ctx, C.byref(s), block.ctypes.data if block.size else None, block.size, arr, len(casters)), "shadow_pass")
         self._shadow_size = int(s.map_size)
 
-    def read_shadow_map(self, size: Optional[int] = None) -> np.ndarray:
+    def shadow_pass_views(self, views, struct_size: Optional[int] = None, n_views: Optional[int] = None, **overrides):
+        """The shadow maps of this frame from several views of one light, in shadow_pass's place: views = [(light_camera, casters), ...], 1 .. 6 of
+        them, each a 512-byte block and the draws that cast in it (none is legal).  The frame's opaque pass resolves every pixel in the first view
+        that holds it.  n_views: what the call claims as the count (tests)."""
+        s = self.shadow_defaults().override(**overrides)
+        if struct_size is not None:
+            s.struct_size = struct_size
+        views = list(views)
+        arr = (AwsmShadowView * max(1, len(views)))()
+        keep = []      # what the records point to
+        for i, (light_camera, casters) in enumerate(views):
+            block = np.frombuffer(bytes(light_camera), dtype=np.uint8)
+            draws = self.make_draws(casters)
+            keep.append((block, draws))
+            arr[i] = AwsmShadowView(block.ctypes.data if block.size else None, block.size, C.cast(draws, C.c_void_p), len(casters))
+        n = len(views) if n_views is None else n_views
+        self._chk(self.lib.awsm_hip_shadow_pass_views(self.ctx, C.byref(s), arr if views else None, n), "shadow_pass_views")
+        self._shadow_size = int(s.map_size)
+
+    def read_shadow_map(self, size: Optional[int] = None, view: Optional[int] = None) -> np.ndarray:
         """The last submitted frame's shadow map -> (S, S) uint64 keys (no hit = all ones).  size: the map's S; it may be left out when the pass was
-        made through this object's shadow_pass (a host's pass was not: give the size Host.set_shadow was given)."""
+        made through this object's shadow_pass (a host's pass was not: give the size Host.set_shadow was given).  view: the layer of a pass of
+        several views (shadow_pass_views); left out, layer 0 through awsm_hip_read_shadow_map."""
         if size is None and self._shadow_size is None:
             raise ValueError("read_shadow_map: no shadow_pass was made through this object; give the map's size")
         S = int(size if size is not None else self._shadow_size)
         keys = np.empty((S, S), np.uint64)
-        self._chk(self.lib.awsm_hip_read_shadow_map(self.ctx, keys.ctypes.data), "read_shadow_map")
+        if view is None:
+            self._chk(self.lib.awsm_hip_read_shadow_map(self.ctx, keys.ctypes.data), "read_shadow_map")
+        else:
+            self._chk(self.lib.awsm_hip_read_shadow_map_view(self.ctx, int(view), keys.ctypes.data), "read_shadow_map_view")
         return keys
+
+    def read_shadow_view(self) -> np.ndarray:
+        """The last submitted frame's view layer -> uint8 [H, W]: the view each pixel was resolved in, 255 = none (shadow_pass_views only)."""
+        view = np.empty((self.height, self.width), np.uint8)
+        self._chk(self.lib.awsm_hip_read_shadow_view(self.ctx, view.ctypes.data), "read_shadow_view")
+        return view
 
     def read_shadow(self):
         """The last submitted frame's layers -> (V, m), float32 [H, W] each: the light's visibility and the multiplier the opaque image received."""

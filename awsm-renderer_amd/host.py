@@ -89,6 +89,12 @@ class HostShadow(C.Structure):
         return self
 
 
+class HostShadowCascades(C.Structure):
+    """AwsmHostShadowCascades (awsm_host_set_shadow_cascades): how many nested windows a shadowed directional light gets along the camera's depth, the
+    blend of the logarithmic and the uniform split, and the depth the last one ends at (0: the camera's far)."""
+    _fields_ = [("struct_size", C.c_uint32), ("count", C.c_uint32), ("lambda_", C.c_float), ("max_distance", C.c_float)]
+
+
 class HostTaa(C.Structure):
     """AwsmHostTaa (awsm_host_set_taa): the weight of the current frame and the jitter amplitudes for a still and a moving camera."""
     _fields_ = [("struct_size", C.c_uint32), ("feedback", C.c_float), ("strength_still", C.c_float), ("strength_moving", C.c_float)]
@@ -166,6 +172,8 @@ def load_library():
         "awsm_host_set_taa": (C.c_int, [vp, vp]), "awsm_host_taa_jitter": (C.c_int, [vp, C.c_uint32, C.c_int, F32P]),
         "awsm_host_shadow_defaults": (C.c_int, [vp, vp]), "awsm_host_set_shadow": (C.c_int, [vp, vp]),
         "awsm_host_shadow_camera": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "awsm_host_shadow_cascades_defaults": (C.c_int, [vp]), "awsm_host_set_shadow_cascades": (C.c_int, [vp, vp]),
+        "awsm_host_shadow_view_count": (C.c_int, [vp, vp]), "awsm_host_shadow_view": (C.c_int, [vp, C.c_uint32, vp, vp, C.c_uint32, vp]),
         "awsm_host_mesh_set_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]), "awsm_host_mesh_append_instances": (C.c_int, [vp, u64, F32P, C.c_uint32]),
         "awsm_host_texture_insert_kind": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_update_transforms": (C.c_int, [vp]),
         "awsm_host_render": (C.c_int, [vp, C.c_int, vp]), "awsm_host_mirror": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
@@ -685,6 +693,31 @@ class Host:
             s.struct_size = struct_size
         self._chk(self.lib.awsm_host_set_shadow(self.h, C.byref(s)), "set_shadow")
 
+    def set_shadow_cascades(self, count: int = 1, lambda_: float = 0.5, max_distance: float = 0.0, struct_size: Optional[int] = None):
+        """Cascades for a shadowed directional light in every later render(): `count` (1 .. 4) nested windows along the camera's depth, tightest
+        first; count = 1 is the single map.  Spot and point lights ignore it."""
+        c = HostShadowCascades()
+        self._chk(self.lib.awsm_host_shadow_cascades_defaults(C.byref(c)), "shadow_cascades_defaults")
+        c.count, c.lambda_, c.max_distance = int(count), float(lambda_), float(max_distance)
+        if struct_size is not None:
+            c.struct_size = struct_size
+        self._chk(self.lib.awsm_host_set_shadow_cascades(self.h, C.byref(c)), "set_shadow_cascades")
+
+    def shadow_views(self, cap: int = 65536):
+        """What the last render() handed the backend's shadow pass -> [(the 512-byte light block, the caster draws as dicts), ...], one per view."""
+        n_views = C.c_uint32(0)
+        self._chk(self.lib.awsm_host_shadow_view_count(self.h, C.byref(n_views)), "shadow_view_count")
+        fields = [f for f, _ in hip_backend.AwsmDraw._fields_]
+        out = []
+        for view in range(n_views.value):
+            block = (C.c_uint8 * 512)()
+            n = C.c_uint32(0)
+            self._chk(self.lib.awsm_host_shadow_view(self.h, view, block, None, 0, C.byref(n)), "shadow_view")
+            draws = (hip_backend.AwsmDraw * max(1, n.value))()
+            self._chk(self.lib.awsm_host_shadow_view(self.h, view, None, draws, n.value, None), "shadow_view")
+            out.append((bytes(block), [{f: int(getattr(draws[i], f)) for f in fields} for i in range(n.value)]))
+        return out
+
     def shadow_camera(self, cap: int = 65536):
         """What the last render() handed the backend's shadow pass -> (the 512-byte light block, the caster draws as dicts)."""
         block = (C.c_uint8 * 512)()
@@ -1095,11 +1128,14 @@ class Renderer:
         """Outline and box the meshes `mesh_keys` (keys from pick()) in every later render(); on=False for off."""
         self.host.set_selection(mesh_keys, on, **overrides)
 
-    def set_shadow(self, light=True, **overrides):
-        """Shadows from one of the scene's lights: an index into scene.lights, True for the first directional light (the first spot light if
-        there is none), False / None for off."""
+    def set_shadow(self, light=True, cascades: Optional[int] = None, cascade_lambda: float = 0.5, cascade_distance: float = 0.0, **overrides):
+        """Shadows from one of the scene's lights: an index into scene.lights (directional, spot or point), True for the first directional light
+        (the first spot light if there is none), False / None for off.  cascades = N: a directional light's N nested windows along the camera's
+        depth (Host.set_shadow_cascades), with cascade_lambda and cascade_distance."""
         if light is None or light is False:
             return self.host.set_shadow(None)
+        if cascades is not None:
+            self.host.set_shadow_cascades(cascades, cascade_lambda, cascade_distance)
         if light is True:
             kinds = [l.get("kind", "directional") for l in self.scene.lights]
             light = kinds.index("directional") if "directional" in kinds else (kinds.index("spot") if "spot" in kinds else None)

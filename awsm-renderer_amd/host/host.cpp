@@ -77,6 +77,7 @@ struct Backend {
     int (*set_selection)(AwsmHipCtx*, const AwsmSelection*, const uint32_t*, uint32_t, const AwsmSelectionBox*, uint32_t) = nullptr;
     int (*shadow_defaults)(AwsmShadow*) = nullptr;                      // optional: shadows (awsm_host_set_shadow)
     int (*shadow_pass)(AwsmHipCtx*, const AwsmShadow*, const void*, size_t, const AwsmDraw*, uint32_t) = nullptr;
+    int (*shadow_pass_views)(AwsmHipCtx*, const AwsmShadow*, const AwsmShadowView*, uint32_t) = nullptr;      // optional: point lights, cascades
     // optional: environment cubes at run time (awsm_host_env_cube_*)
     int (*env_cube_create)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t) = nullptr;
     int (*env_cube_write_face)(AwsmHipCtx*, AwsmCube, uint32_t, uint32_t, uint32_t, uint32_t, AwsmCubeFormat, const void*, size_t, const AwsmCubeLayout*) = nullptr;
@@ -286,6 +287,11 @@ struct AwsmHost {
     bool has_hud_meshes = false;
     uint32_t n_hud_meshes = 0, n_world_transparent_meshes = 0;   // what the two flags are kept from (a removed mesh takes its pass with it: ADVICE r3)
     bool has_transparent_meshes = false;
+    // ---- shadows from several views: the cascades record, and every view the last render sent (view 0 is shadow_block /
+    // shadow_casters too).  At the struct's end: every older member keeps its offset. ----
+    AwsmHostShadowCascades shadow_cascades{(uint32_t)sizeof(AwsmHostShadowCascades), 1u, 0.5f, 0.0f};
+    struct ShadowViewRec { uint8_t block[512]; std::vector<AwsmDraw> casters; };
+    std::vector<ShadowViewRec> shadow_views;
 };
 
 namespace {
@@ -722,6 +728,7 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.set_selection = reinterpret_cast<decltype(b.set_selection)>(dlsym(b.dl, "awsm_hip_set_selection"));
     b.shadow_defaults = reinterpret_cast<decltype(b.shadow_defaults)>(dlsym(b.dl, "awsm_hip_shadow_defaults"));      // optional (awsm_host_set_shadow)
     b.shadow_pass = reinterpret_cast<decltype(b.shadow_pass)>(dlsym(b.dl, "awsm_hip_shadow_pass"));
+    b.shadow_pass_views = reinterpret_cast<decltype(b.shadow_pass_views)>(dlsym(b.dl, "awsm_hip_shadow_pass_views"));
     b.env_cube_create = reinterpret_cast<decltype(b.env_cube_create)>(dlsym(b.dl, "awsm_hip_env_cube_create"));      // optional (awsm_host_env_cube_*)
     b.env_cube_write_face = reinterpret_cast<decltype(b.env_cube_write_face)>(dlsym(b.dl, "awsm_hip_env_cube_write_face"));
     b.env_cube_write_all_faces = reinterpret_cast<decltype(b.env_cube_write_all_faces)>(dlsym(b.dl, "awsm_hip_env_cube_write_all_faces"));
@@ -1920,7 +1927,8 @@ int awsm_host_set_shadow(AwsmHost* h, const AwsmHostShadow* s) {
     if (s->struct_size != sizeof(AwsmHostShadow)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow: AwsmHostShadow.struct_size = %u (set it to sizeof(AwsmHostShadow))", s->struct_size);
     const AwsmHostLight* l = h->lights.get(s->light);
     if (!l) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow: [light] not found");
-    if (l->kind == 2u) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow: a point light needs a cube map of depths; directional and spot lights only");
+    if (l->kind == 2u && !h->be.shadow_pass_views)
+        return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow: a point light needs a cube map of depths, and the backend library has no %s; directional and spot lights only", "awsm_hip_shadow_pass_views");
     h->shadow = *s;
     h->shadow_on = true;
     return AWSM_OK;
@@ -1932,6 +1940,40 @@ int awsm_host_shadow_camera(AwsmHost* h, void* block512, AwsmDraw* casters_out, 
     const uint32_t n = (uint32_t)h->shadow_casters.size();
     if (n_out) *n_out = n;
     if (casters_out) memcpy(casters_out, h->shadow_casters.data(), (size_t)std::min(n, cap) * sizeof(AwsmDraw));
+    return AWSM_OK;
+}
+
+int awsm_host_shadow_cascades_defaults(AwsmHostShadowCascades* out) {
+    if (!out) return AWSM_ERR_INVALID_ARGUMENT;
+    *out = AwsmHostShadowCascades{(uint32_t)sizeof(AwsmHostShadowCascades), 1u, 0.5f, 0.0f};
+    return AWSM_OK;
+}
+int awsm_host_set_shadow_cascades(AwsmHost* h, const AwsmHostShadowCascades* c) {
+    if (!h || !c) return AWSM_ERR_INVALID_ARGUMENT;
+    if (c->struct_size != sizeof(AwsmHostShadowCascades))
+        return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow_cascades: AwsmHostShadowCascades.struct_size = %u (set it to sizeof(AwsmHostShadowCascades))", c->struct_size);
+    if (c->count < 1u || c->count > 4u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow_cascades: count = %u (1 .. 4)", c->count);
+    if (!(c->lambda >= 0.0f && c->lambda <= 1.0f)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow_cascades: lambda = %g (0 .. 1)", (double)c->lambda);
+    if (!(c->max_distance >= 0.0f) || !std::isfinite(c->max_distance)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "set_shadow_cascades: max_distance = %g (>= 0; 0: the camera's far)", (double)c->max_distance);
+    if (c->count > 1u && !h->be.shadow_pass_views) return fail(h, AWSM_ERR_UNSUPPORTED, "set_shadow_cascades: the backend library has no %s", "awsm_hip_shadow_pass_views");
+    h->shadow_cascades = *c;
+    return AWSM_OK;
+}
+int awsm_host_shadow_view_count(AwsmHost* h, uint32_t* n_out) {
+    if (!h || !n_out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->shadow_rendered) return fail(h, AWSM_ERR_NOT_READY, "shadow_view_count: the last render had no shadow pass");
+    *n_out = (uint32_t)h->shadow_views.size();
+    return AWSM_OK;
+}
+int awsm_host_shadow_view(AwsmHost* h, uint32_t view, void* block512, AwsmDraw* casters_out, uint32_t cap, uint32_t* n_out) {
+    if (!h || (!casters_out && cap)) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->shadow_rendered) return fail(h, AWSM_ERR_NOT_READY, "shadow_view: the last render had no shadow pass");
+    if (view >= h->shadow_views.size()) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "shadow_view: view %u of %zu", view, h->shadow_views.size());
+    const AwsmHost::ShadowViewRec& rec = h->shadow_views[view];
+    if (block512) memcpy(block512, rec.block, 512);
+    const uint32_t n = (uint32_t)rec.casters.size();
+    if (n_out) *n_out = n;
+    if (casters_out) memcpy(casters_out, rec.casters.data(), (size_t)std::min(n, cap) * sizeof(AwsmDraw));
     return AWSM_OK;
 }
 
@@ -2000,14 +2042,186 @@ static void shadow_light_camera(AwsmHost* h, const AwsmHostLight& l, uint32_t S,
     pack_camera_block(h, v, p, pos, (float)S, (float)S, block);
 }
 
+// ---- several views of the shadowed light (include/awsm_host.h has the rules) ----
+// The union of the shadow candidates' world boxes -> whether there is any.
+static bool shadow_scene_union(const AwsmHost* h, double lo[3], double hi[3]) {
+    bool any = false;
+    for (int i = 0; i < 3; i++) lo[i] = hi[i] = 0.0;
+    for (const MeshRec& m : h->meshes.values()) {
+        if (m.hidden || m.hud || m.transparent || !m.has_world_aabb) continue;
+        const double a[3] = {m.world_aabb.min.x, m.world_aabb.min.y, m.world_aabb.min.z}, b[3] = {m.world_aabb.max.x, m.world_aabb.max.y, m.world_aabb.max.z};
+        for (int i = 0; i < 3; i++) { lo[i] = any ? std::min(lo[i], a[i]) : a[i]; hi[i] = any ? std::max(hi[i], b[i]) : b[i]; }
+        any = true;
+    }
+    return any;
+}
+// Mat4::look_to_rh(eye, f, up) in f64, up by §19's rule: +Y, or +Z when |f.y| > 0.999
+static void shadow_look_to(const double eye[3], const double f[3], double view[16]) {
+    const double up[3] = {0.0, std::fabs(f[1]) > 0.999 ? 0.0 : 1.0, std::fabs(f[1]) > 0.999 ? 1.0 : 0.0};
+    double s[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const double sl = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    for (int i = 0; i < 3; i++) s[i] /= sl;
+    const double u[3] = {s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0]};
+    const double v[16] = {s[0], u[0], -f[0], 0.0,   s[1], u[1], -f[1], 0.0,   s[2], u[2], -f[2], 0.0,
+                          -(s[0] * eye[0] + s[1] * eye[1] + s[2] * eye[2]), -(u[0] * eye[0] + u[1] * eye[1] + u[2] * eye[2]), f[0] * eye[0] + f[1] * eye[1] + f[2] * eye[2], 1.0};
+    memcpy(view, v, sizeof v);
+}
+// an f64 view and projection, rounded once to f32, into a block for an S x S map
+static void shadow_pack(AwsmHost* h, const double view[16], const double proj[16], const double eye[3], uint32_t S, uint8_t block[512]) {
+    float vf[16], pf[16];
+    for (int i = 0; i < 16; i++) { vf[i] = (float)view[i]; pf[i] = (float)proj[i]; }
+    Mat4 v, p;
+    memcpy(&v, vf, 64); memcpy(&p, pf, 64);
+    const float pos[3] = {(float)eye[0], (float)eye[1], (float)eye[2]};
+    pack_camera_block(h, v, p, pos, (float)S, (float)S, block);
+}
+
+// A point light's six faces -> the blocks, in the order +X, -X, +Y, -Y, +Z, -Z
+static void shadow_cube_faces(AwsmHost* h, const AwsmHostLight& l, uint32_t S, uint32_t R, uint8_t blocks[6][512]) {
+    double lo[3], hi[3];
+    const bool any = shadow_scene_union(h, lo, hi);
+    const double eye[3] = {l.position[0], l.position[1], l.position[2]};
+    double fa = l.range;      // near and far by the spot's rule
+    if (!(fa > 0.0)) {
+        fa = 0.0;
+        if (any) for (int k = 0; k < 8; k++) {
+            double dd = 0.0;
+            for (int i = 0; i < 3; i++) { const double p = ((k >> i) & 1) ? hi[i] : lo[i]; dd += (p - eye[i]) * (p - eye[i]); }
+            fa = std::max(fa, std::sqrt(dd));
+        }
+        fa = std::max(fa, 1.0);
+    }
+    const double n = std::max(0.05, fa * 1e-3);
+    const double t = ((double)S - 2.0 * ((double)R + 1.0)) / (double)S;      // 1 / tan(fovy / 2): the 90-degree face lands on [M, S - M)^2, M = R + 1
+    double proj[16] = {};
+    proj[0] = t; proj[5] = t; proj[10] = fa / (n - fa); proj[11] = -1.0; proj[14] = n * fa / (n - fa);
+    for (int face = 0; face < 6; face++) {
+        double f[3] = {0.0, 0.0, 0.0}, view[16];
+        f[face >> 1] = (face & 1) ? -1.0 : 1.0;
+        shadow_look_to(eye, f, view);
+        shadow_pack(h, view, proj, eye, S, blocks[face]);
+    }
+}
+
+// A directional light's N cascades, tightest first -> the blocks and AwsmShadow.light
+static void shadow_cascades(AwsmHost* h, const AwsmHostLight& l, uint32_t S, uint32_t N, uint8_t blocks[4][512], float light_out[4]) {
+    double f[3] = {l.direction[0], l.direction[1], l.direction[2]};
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    if (fl > 0.0) { f[0] /= fl; f[1] /= fl; f[2] /= fl; } else { f[0] = 0.0; f[1] = -1.0; f[2] = 0.0; }
+    for (int i = 0; i < 3; i++) light_out[i] = (float)-f[i];
+    light_out[3] = 0.0f;
+    // §19's directional view matrix and depth range, of the scene's union
+    double lo[3], hi[3], c[3] = {0, 0, 0}, r = 1.0;
+    if (shadow_scene_union(h, lo, hi)) {
+        double dd = 0.0;
+        for (int i = 0; i < 3; i++) { c[i] = 0.5 * (lo[i] + hi[i]); dd += (hi[i] - lo[i]) * (hi[i] - lo[i]); }
+        r = 0.5 * std::sqrt(dd);
+        if (!(r > 0.0)) r = 1.0;
+    }
+    double eye[3], view[16];
+    for (int i = 0; i < 3; i++) eye[i] = c[i] - 2.0 * r * f[i];
+    shadow_look_to(eye, f, view);
+    const double ln = r, lf = 3.0 * r;
+    // the camera: its near and far, and its corner rays in world space (the view matrix is rigid: world = R^T (p - t))
+    const float* cp = (const float*)&h->cam_proj;
+    const float* cv = (const float*)&h->cam_view;
+    const bool ortho = cp[15] != 0.0f;
+    const double p0 = cp[0], p5 = cp[5], p10 = cp[10], p14 = cp[14];
+    const double cn = p14 / p10, cf = ortho ? (p14 - 1.0) / p10 : p14 / (p10 + 1.0);
+    const double far_used = h->shadow_cascades.max_distance > 0.0f ? std::min(cf, (double)h->shadow_cascades.max_distance) : cf;
+    const double lambda = h->shadow_cascades.lambda;
+    auto split = [&](uint32_t j) {
+        const double uni = cn + (far_used - cn) * (double)j / (double)N;
+        const double lg = cn > 0.0 ? cn * std::pow(far_used / cn, (double)j / (double)N) : uni;      // (no logarithmic split from a near plane at or behind the eye)
+        return lambda * lg + (1.0 - lambda) * uni;
+    };
+    auto corner = [&](int k, double d, double out[3]) {      // corner ray k (NDC x, y = -1 or +1) at view depth d
+        const double nx = (k & 1) ? 1.0 : -1.0, ny = (k & 2) ? 1.0 : -1.0;
+        double pv[3];
+        if (ortho) { pv[0] = (nx - cp[12]) / p0; pv[1] = (ny - cp[13]) / p5; }
+        else { pv[0] = (nx + cp[8]) * d / p0; pv[1] = (ny + cp[9]) * d / p5; }
+        pv[2] = -d;
+        for (int i = 0; i < 3; i++) pv[i] -= cv[12 + i];
+        for (int i = 0; i < 3; i++) out[i] = (double)cv[4 * i + 0] * pv[0] + (double)cv[4 * i + 1] * pv[1] + (double)cv[4 * i + 2] * pv[2];
+    };
+    for (uint32_t j = 0; j < N; j++) {
+        double pts[8][3], cj[3] = {0, 0, 0};
+        for (int k = 0; k < 8; k++) {
+            corner(k & 3, split(j + (uint32_t)(k >> 2)), pts[k]);
+            for (int i = 0; i < 3; i++) cj[i] += pts[k][i] / 8.0;
+        }
+        double rj = 0.0;
+        for (int k = 0; k < 8; k++) {
+            double dd = 0.0;
+            for (int i = 0; i < 3; i++) dd += (pts[k][i] - cj[i]) * (pts[k][i] - cj[i]);
+            rj = std::max(rj, std::sqrt(dd));
+        }
+        // the window is wider than the slice's sphere by what keeps every corner in the layer's inner region at pcf_radius <= 2: three texels on
+        // each side and one for the snap below, r + 2 w / S <= w (1 - 6 / S)
+        rj *= S > 16u ? (double)S / ((double)S - 8.0) : 2.0;
+        rj = std::ceil(rj * 16.0) / 16.0;
+        if (!(rj > 0.0)) rj = 1.0 / 16.0;
+        const double texel = 2.0 * rj / (double)S;
+        double xy[2];
+        for (int a = 0; a < 2; a++) {
+            const double v = view[a] * cj[0] + view[4 + a] * cj[1] + view[8 + a] * cj[2] + view[12 + a];
+            xy[a] = std::floor(v / texel) * texel;
+        }
+        double proj[16] = {};
+        proj[0] = 1.0 / rj; proj[5] = 1.0 / rj; proj[12] = -xy[0] / rj; proj[13] = -xy[1] / rj;
+        proj[10] = 1.0 / (ln - lf); proj[14] = ln / (ln - lf); proj[15] = 1.0;
+        shadow_pack(h, view, proj, eye, S, blocks[j]);
+    }
+}
+
+// The views of a point light or of a cascaded directional one, through awsm_hip_shadow_pass_views
+static int render_shadow_views(AwsmHost* h, const AwsmHostLight& l, AwsmShadow& s) {
+    if (!h->be.shadow_pass_views) return fail(h, AWSM_ERR_UNSUPPORTED, "render: the backend library has no %s", "awsm_hip_shadow_pass_views");
+    uint8_t blocks[6][512];
+    uint32_t n_blocks;
+    const bool cube = l.kind == 2u;
+    if (cube) {
+        if (s.map_size < 16u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: a point light's shadow map_size = %u (16 at the least: a face keeps an apron of pcf_radius + 1 texels)", s.map_size);
+        shadow_cube_faces(h, l, s.map_size, s.pcf_radius, blocks);
+        for (int i = 0; i < 3; i++) s.light[i] = l.position[i];
+        s.light[3] = 1.0f;
+        n_blocks = 6;
+    } else {
+        n_blocks = h->shadow_cascades.count;
+        shadow_cascades(h, l, std::max(1u, s.map_size), n_blocks, blocks, s.light);
+    }
+    h->shadow_views.clear();
+    for (uint32_t i = 0; i < n_blocks; i++) {
+        AwsmHost::ShadowViewRec rec;
+        memcpy(rec.block, blocks[i], 512);
+        Mat4 lvp;
+        memcpy(&lvp, blocks[i] + 128, 64);
+        collect_draws(h, rec.casters, nullptr, nullptr, nullptr, &lvp);
+        if (cube && rec.casters.empty()) continue;      // a face whose frustum meets no candidate is not sent
+        h->shadow_views.push_back(std::move(rec));
+    }
+    if (h->shadow_views.empty()) return AWSM_OK;      // no face sees a candidate: no pass, every pixel lit
+    std::vector<AwsmShadowView> views(h->shadow_views.size());
+    for (size_t i = 0; i < views.size(); i++)
+        views[i] = AwsmShadowView{h->shadow_views[i].block, 512, h->shadow_views[i].casters.data(), (uint32_t)h->shadow_views[i].casters.size()};
+    const int rc = h->be.shadow_pass_views(h->ctx, &s, views.data(), (uint32_t)views.size());
+    if (rc) { h->shadow_views.clear(); return dev_fail(h, rc, "shadow_pass_views"); }
+    memcpy(h->shadow_block, h->shadow_views[0].block, 512);
+    h->shadow_casters = h->shadow_views[0].casters;
+    h->shadow_rendered = true;
+    return AWSM_OK;
+}
+
 // called by awsm_host_render between the geometry passes and the opaque pass
 static int render_shadow_pass(AwsmHost* h) {
     const AwsmHostLight* l = h->lights.get(h->shadow.light);
-    if (!l || l->kind == 2u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the shadowed light is gone");      // (checked at the top of the render too)
+    if (!l) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the shadowed light is gone");      // (checked at the top of the render too)
     AwsmShadow s{};
     s.struct_size = (uint32_t)sizeof s;
     s.map_size = h->shadow.map_size; s.pcf_radius = h->shadow.pcf_radius;
     s.bias = h->shadow.bias; s.slope_bias = h->shadow.slope_bias; s.max_slope = h->shadow.max_slope; s.strength = h->shadow.strength; s.facing_fade = h->shadow.facing_fade;
+    h->shadow_views.clear();
+    if (l->kind == 2u || (l->kind == 1u && h->shadow_cascades.count > 1u)) return render_shadow_views(h, *l, s);
     shadow_light_camera(h, *l, std::max(1u, s.map_size), h->shadow_block, s.light);
     Mat4 lvp;
     memcpy(&lvp, h->shadow_block + 128, 64);
@@ -2015,6 +2229,9 @@ static int render_shadow_pass(AwsmHost* h) {
     const int rc = h->be.shadow_pass(h->ctx, &s, h->shadow_block, 512, h->shadow_casters.data(), (uint32_t)h->shadow_casters.size());
     if (rc) return dev_fail(h, rc, "shadow_pass");
     h->shadow_rendered = true;
+    h->shadow_views.resize(1);
+    memcpy(h->shadow_views[0].block, h->shadow_block, 512);
+    h->shadow_views[0].casters = h->shadow_casters;
     return AWSM_OK;
 }
 

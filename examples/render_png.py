@@ -11,8 +11,9 @@ device); --env-ktx2 PATH loads a KTX2 cube map as the skybox and as the prefilte
 by the skybox either of them made: the prefiltered chain (128^2, down to 4^2) and the irradiance cube (32^2) are filtered from it on the device.
 --hdr FILE projects an equirectangular Radiance .hdr panorama into the skybox (--hdr-size N, default 512; --hdr-yaw R radians turns it about the
 vertical); an EXPOSURE= in the file is divided out.  Together with --bake-ibl the scene is lit from the file.
---shadow [LIGHT] casts shadows from one directional or spot light of the scene (--shadow-size N, --shadow-strength X): a depth map from the light,
-looked up per pixel and multiplied into the opaque image.
+--shadow [LIGHT] casts shadows from one directional, spot or point light of the scene (--shadow-size N, --shadow-strength X): a depth map from the
+light, looked up per pixel and multiplied into the opaque image; a point light gets the six faces of a cube, and --shadow-cascades N gives a
+directional light N nested maps along the camera's depth (1 .. 4).
 --ssao darkens creases and contact lines: ambient occlusion estimated from the geometry pass's depth (--ssao-radius R in world units, --ssao-intensity I).
 --taa N renders N frames of the still view with the projection jittered per frame and resolves each into a history (temporal anti-aliasing, in front of the
 post pass: it implies the post pass) and writes the last; with --select the N frames are the selected ones.
@@ -58,9 +59,10 @@ def main():
     ap.add_argument("--ssao-intensity", type=float, default=None, metavar="I", help="with --ssao: the estimator's scale (default 1.0)")
     ap.add_argument("--taa", type=int, default=0, metavar="N", help="temporal anti-aliasing: render N jittered frames of the still view, write the last (implies the post pass)")
     ap.add_argument("--shadow", nargs="?", const=-1, type=int, default=None, metavar="LIGHT",
-                    help="shadows from one directional or spot light: an index into the scene's lights (default: the first directional light); not with --via-glb, "
+                    help="shadows from one directional, spot or point light: an index into the scene's lights (default: the first directional light); not with --via-glb, "
                          "whose lights are the file's and have no index here")
     ap.add_argument("--shadow-size", type=int, default=None, metavar="N", help="with --shadow: the shadow map is N x N (default 2048)")
+    ap.add_argument("--shadow-cascades", type=int, default=None, metavar="N", help="with --shadow on a directional light: N nested maps along the camera's depth, 1 .. 4 (default 1)")
     ap.add_argument("--shadow-strength", type=float, default=None, metavar="X", help="with --shadow: how dark a shadow is, 0 .. 1 (default 0.7)")
     ap.add_argument("--select", action="append", default=[], metavar="X,Y", help="select the mesh under this pixel (outline + bounding box); may be repeated; not with --via-glb")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
@@ -107,7 +109,7 @@ def main():
     if a.shadow is not None:
         if a.via_glb:
             ap.error("--shadow names a light by its index in the scene description; a scene read from a .glb keeps no such index (Host.set_shadow takes a light's key)")
-        r.set_shadow(True if a.shadow < 0 else a.shadow, **{k: v for k, v in (("map_size", a.shadow_size), ("strength", a.shadow_strength)) if v is not None})
+        r.set_shadow(True if a.shadow < 0 else a.shadow, **{k: v for k, v in (("map_size", a.shadow_size), ("strength", a.shadow_strength), ("cascades", a.shadow_cascades)) if v is not None})
     if a.taa > 0:
         r.set_taa(True)
     stats = r.render(sync=True)

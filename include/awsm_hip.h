@@ -652,13 +652,42 @@ typedef struct AwsmShadow {
     uint32_t struct_size;
     uint32_t map_size;      /* S: the map is S x S keys, 1 <= S <= 8192 */
     uint32_t pcf_radius;    /* R in {0, 1, 2}: (2R+1)^2 taps */
-    float    light[4];      /* w == 0: xyz = unit vector TOWARDS the light (directional); w == 1: xyz = the light's position (spot) */
+    float    light[4];      /* w == 0: xyz = unit vector TOWARDS the light (directional); w == 1: xyz = the light's position (positional: spot or point) */
     float    bias, slope_bias, max_slope, strength, facing_fade;
 } AwsmShadow;
 int awsm_hip_shadow_defaults(AwsmShadow* out);
 int awsm_hip_shadow_pass(AwsmHipCtx* ctx, const AwsmShadow* shadow, const void* light_camera, size_t camera_bytes, const AwsmDraw* casters, uint32_t n);
 int awsm_hip_read_shadow_map(AwsmHipCtx* ctx, uint64_t* keys_out /* map_size^2 */);
 int awsm_hip_read_shadow(AwsmHipCtx* ctx, float* visibility_out, float* multiplier_out /* width x height each */);
+
+/* ---- shadows from several views of one light: the six faces of a cube around a point light, or nested windows (cascades) along the
+ * camera's depth for a directional one.
+ *   shadow_pass_views     in shadow_pass's window and in its place: view i's casters are rasterised from view i's block into layer i of the frame
+ *                         slot's stack of n_views map_size x map_size key layers, one view after another on the caller's stream, each by the chain
+ *                         shadow_pass runs.  A view with no casters is legal: an empty layer.  The frame's opaque pass then runs
+ *                         k_shadow_resolve_views in k_shadow_resolve's place: with M = pcf_radius + 1, a pixel's view is the lowest i whose
+ *                         (u_i, v_i) lies in [M, S - M)^2 with the pixel inside view i's volume; failing that the lowest i it is inside of; failing
+ *                         that none (255): V = 1.  Its receiver plane and its taps are taken in that view and from that layer; a neighbour
+ *                         serves the plane when it is inside that view, or when another view holds it and it lies in front of that view within
+ *                         its depth range (a cube's next face, the next cascade).  With one view this is shadow_pass's resolve, operation for
+ *                         operation.  A later shadow_pass or shadow_pass_views in the same frame replaces an
+ *                         earlier one; a refused call leaves the earlier one standing.
+ *                         AWSM_ERR_INVALID_ARGUMENT for n_views outside 1 .. AWSM_SHADOW_MAX_VIEWS or views == NULL; per view what shadow_pass
+ *                         refuses for its camera and casters, naming the view; everything else as shadow_pass.
+ *   read_shadow_map_view  layer `view` of the last submitted frame's pass.  AWSM_ERR_INVALID_ARGUMENT for a view that pass did not have (a pass through
+ *                         shadow_pass has view 0 alone); awsm_hip_read_shadow_map returns layer 0.
+ *   read_shadow_view      per pixel the view it was resolved in, 255 = none.  AWSM_ERR_NOT_READY as read_shadow, and when the frame's pass came
+ *                         through shadow_pass (k_shadow_resolve writes no such layer). ---- */
+#define AWSM_SHADOW_MAX_VIEWS 6
+typedef struct AwsmShadowView {
+    const void*     light_camera;   /* a 512-byte block in AWSM_BUF_CAMERA's layout, as awsm_hip_shadow_pass takes it */
+    size_t          camera_bytes;
+    const AwsmDraw* casters;
+    uint32_t        n_casters;      /* 0 is legal: an empty layer */
+} AwsmShadowView;
+int awsm_hip_shadow_pass_views(AwsmHipCtx* ctx, const AwsmShadow* shadow, const AwsmShadowView* views, uint32_t n_views /* 1 .. 6 */);
+int awsm_hip_read_shadow_map_view(AwsmHipCtx* ctx, uint32_t view, uint64_t* keys_out /* map_size^2 */);
+int awsm_hip_read_shadow_view(AwsmHipCtx* ctx, uint8_t* view_out /* width x height: the chosen view, 255 = none */);
 
 /* ---- the editor's selection overlay ("Visual bounding box around selected objects" of the reference's "Next up" list).  A built-in
  * of awsm_hip_transparent_pass, drawn as its last step — over the grid, the transparent meshes and the MSAA resolve, under the HUD transparent pass,

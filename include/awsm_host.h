@@ -305,7 +305,7 @@ int awsm_host_taa_jitter(AwsmHost* h, uint32_t frame_count, int moved, float out
  *   casters       the candidates whose world AABB meets that camera's frustum, in the order the world list would hold them.  Transparent and
  *                 HUD meshes neither cast nor are looked up.
  * set_shadow(NULL) turns it off.  AWSM_ERR_UNSUPPORTED, naming the symbol, when the backend library lacks awsm_hip_shadow_pass /
- * awsm_hip_shadow_defaults, and for a point light; AWSM_ERR_INVALID_ARGUMENT for a key that names no light.  A light removed later turns the
+ * awsm_hip_shadow_defaults, and for a point light when it lacks awsm_hip_shadow_pass_views (below); AWSM_ERR_INVALID_ARGUMENT for a key that names no light.  A light removed later turns the
  * feature off with AWSM_ERR_INVALID_ARGUMENT at the next awsm_host_render.  The record's other fields reach the backend unchanged, and its
  * refusals (and AWSM_ERR_UNSUPPORTED on a sharded host) come back from awsm_host_render.
  * shadow_camera: what the last awsm_host_render used — the 512-byte block, and up to `cap` caster draws (n_out: how many there were).
@@ -320,6 +320,31 @@ typedef struct AwsmHostShadow {
 int awsm_host_shadow_defaults(AwsmHost* h, AwsmHostShadow* out);      /* the backend's defaults; light = 0 */
 int awsm_host_set_shadow(AwsmHost* h, const AwsmHostShadow* shadow /* NULL = off */);
 int awsm_host_shadow_camera(AwsmHost* h, void* block512, AwsmDraw* casters_out, uint32_t cap, uint32_t* n_out);
+/* Shadows from several views of the shadowed light (awsm_hip_shadow_pass_views), when the backend library has that entry.
+ * A POINT light: set_shadow accepts it (AWSM_ERR_UNSUPPORTED, naming the symbol, over a backend without the entry).  Six views in the order
+ *   +X, -X, +Y, -Y, +Z, -Z: eye = the light's position, forward = the axis, up by the rule above; perspective of aspect 1 with
+ *   tan(fovy / 2) = S / (S - 2 (pcf_radius + 1)) — the 90-degree face lands on the layer's inner region, the rest is the apron the taps read —, near
+ *   and far by the spot's rule.  map_size < 16: AWSM_ERR_INVALID_ARGUMENT at the render.  Casters per face by that face's frustum, in the world
+ *   list's order; a face whose frustum meets no candidate is not sent (its pixels find no view and are lit); light = (position, 1).
+ * CASCADES for a directional light: set_shadow_cascades {count 1 .. 4, lambda 0 .. 1, max_distance >= 0 (0: the camera's far)}; defaults 1, 0.5, 0.
+ *   Spot and point lights ignore it; count = 1 is the single map above, call for call.  count = N > 1, with n, f the camera's near and far and
+ *   f' = min(f, max_distance or f): split depths d_j = lambda n (f'/n)^(j/N) + (1 - lambda) (n + (f' - n) j/N); slice j's eight corners lie on the
+ *   camera's corner rays at view depths d_j and d_j+1; c_j is their mean and r_j the largest distance from c_j to a corner times S / (S - 8) (2 at S <= 16: every
+ *   corner then lies three texels inside the window after the snap below), rounded up to a multiple of 1/16.  Every cascade has the directional view matrix and the near = r, far = 3 r above (the scene's union: depth means the same in every
+ *   layer) and the orthographic window [x - r_j, x + r_j] x [y - r_j, y + r_j], (x, y) = c_j in light space, each snapped down to a multiple of
+ *   the texel 2 r_j / S.  Composed in f64.  Casters per view by its frustum; views are sent tightest first; beyond the last a pixel is lit.
+ *   AWSM_ERR_UNSUPPORTED, naming the symbol, for count > 1 over a backend without the entry; AWSM_ERR_INVALID_ARGUMENT for the ranges.
+ * shadow_view_count / shadow_view: what the last awsm_host_render sent — how many views, and view i's block and casters as shadow_camera hands out
+ *   view 0's.  AWSM_ERR_NOT_READY when that render had no shadow pass; AWSM_ERR_INVALID_ARGUMENT for a view it did not have. */
+typedef struct AwsmHostShadowCascades {
+    uint32_t struct_size;
+    uint32_t count;
+    float lambda, max_distance;
+} AwsmHostShadowCascades;
+int awsm_host_shadow_cascades_defaults(AwsmHostShadowCascades* out);
+int awsm_host_set_shadow_cascades(AwsmHost* h, const AwsmHostShadowCascades* cascades);
+int awsm_host_shadow_view_count(AwsmHost* h, uint32_t* n_out);
+int awsm_host_shadow_view(AwsmHost* h, uint32_t view, void* block512, AwsmDraw* casters_out, uint32_t cap, uint32_t* n_out);
 /* CameraMatrices.focus_distance / .aperture (camera.rs:40-52; the reference's defaults are 10.0 and 5.6): camera bytes 496-503, uploaded with
  * the next frame.  Until this is called the host writes 0 and 0. */
 int awsm_host_camera_set_dof(AwsmHost* h, float focus_distance, float aperture);
