@@ -404,10 +404,11 @@ inline void enqueue_binning(const FrameDev& f, bool has_tris, hipStream_t s) {
     awsm_launch_bin_scan(&f, s);
     if (has_tris) { awsm_launch_bin_fill(&f, s); awsm_launch_bin_big(&f, 1, s); }
 }
-// A pass without triangles launches no k_deform_transform, which otherwise clears counters + tile_count (k_bin_scan clears tile_cursor)
-int clear_empty_pass(AwsmHipCtx* c, const FrameBufs& b, uint32_t n_tiles, hipStream_t s) {
-    HIPCHK(c, hipMemsetAsync(b.counters.ptr, 0, kCtrWords * sizeof(uint32_t), s));
-    HIPCHK(c, hipMemsetAsync((uint32_t*)b.counters.ptr + 12, 0, 2 * sizeof(uint32_t), s));
+// A pass without triangles launches no k_deform_transform, which otherwise clears counters + tile_count (k_bin_scan clears tile_cursor).
+// counters: the words the pass counts in — the FrameBufs' own, or those of one view of the shadow pass.
+int clear_empty_pass(AwsmHipCtx* c, const FrameBufs& b, uint32_t* counters, uint32_t n_tiles, hipStream_t s) {
+    HIPCHK(c, hipMemsetAsync(counters, 0, kCtrWords * sizeof(uint32_t), s));
+    HIPCHK(c, hipMemsetAsync(counters + 12, 0, 2 * sizeof(uint32_t), s));
     if (n_tiles) HIPCHK(c, hipMemsetAsync(b.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), s));
     return AWSM_OK;
 }
@@ -447,7 +448,7 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
     }
     ht.mark("geometry: slot wait + upload event");
     const bool has_geometry = world.total_tris && n_tiles;
-    if (!has_geometry && (rc = clear_empty_pass(c, FB(c), n_tiles, c->stream))) return rc;
+    if (!has_geometry && (rc = clear_empty_pass(c, FB(c), (uint32_t*)FB(c).counters.ptr, n_tiles, c->stream))) return rc;
     if (c->trace_dev) awsm_launch_handoff_signal(nullptr, 0u, trace_slot(c, 0), c->stream);
     if ((rc = record(c, EV_START))) return rc;
     // Measurement aid (tools/knockout.sh; static camera only): from the ninth frame on leave out the raster (4), the binning launches as well (6) or
@@ -672,7 +673,7 @@ int enqueue_transparent(AwsmHipCtx* c, PassKind kind) {
     if ((rc = record(c, EV_FWD_BEGIN, ss))) return rc;
     const bool has_geometry = f.total_tris && n_tiles;
     if (!has_geometry) {
-        if ((rc = clear_empty_pass(c, pass_bufs(c, kind), n_tiles, ss))) return rc;
+        if ((rc = clear_empty_pass(c, pass_bufs(c, kind), (uint32_t*)pass_bufs(c, kind).counters.ptr, n_tiles, ss))) return rc;
     } else {
         awsm_launch_resolve_draws(c->scene_dev, &f, ss);      // first: the transform tags each triangle with its draw's alpha mode
         awsm_launch_transform_forward(c->scene_dev, &f, c->lists[kind].n_blocks, ss);
@@ -1434,9 +1435,10 @@ int awsm_hip_hud_geometry_pass(AwsmHipCtx* c, const AwsmDraw* draws, uint32_t n)
 // The casters through the world pass's kernels into the slot's S x S map, with buffers of its own and the precautions of enqueue_hud_geometry: no
 // camera snapshot, no status words, the opaque pass's lists nulled, no geometry cache — nothing the world pass left is reset.  k_deform_transform
 // reads view_proj through the scene table: it is given the slot's second copy of the table, whose camera entry is the slot's copy of the light block.
-static int enqueue_shadow(AwsmHipCtx* c) {
+// One view of the light: `casters` (already in the pass's list buffer) seen through the light block `block` (already in the slot's second scene
+// table) into the S x S keys at `vis`, counting in `counters`.  Both entries and the replay of awsm_hip_frame_end come through here.
+static int enqueue_shadow_view(AwsmHipCtx* c, const PassList& casters, const uint8_t* block, uint32_t* counters, unsigned long long* vis) {
     const FrameBufs& sb = pass_bufs(c, kPassShadow);
-    const PassList& casters = c->lists[kPassShadow];
     const uint32_t S = c->shadow_pass[c->slot].p.map_size;
     FrameDev f;
     memset(&f, 0, sizeof f);
@@ -1446,24 +1448,72 @@ static int enqueue_shadow(AwsmHipCtx* c) {
     f.n_draws = (uint32_t)casters.draws.size();
     f.total_tris = casters.total_tris; f.total_verts = 3u * casters.total_tris;
     f.msaa = 0;                                  // single-sampled, whatever the frame is
-    f.camera = (const uint8_t*)c->shadow_cam[c->slot].ptr;
-    bind_pass(f, sb);                            // (vis = the map: every tile of it is written, a tile without casters becomes "no hit")
+    f.camera = block;
+    bind_pass(f, sb);
+    f.counters = counters;
+    f.vis = vis;                                 // (the map: every tile of it is written, a tile without casters becomes "no hit")
     f.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
     f.frame_serial = c->frame_serial;
-    int rc;
-    if ((rc = sync_scene(c))) return rc;
-    if (c->shadow_scene_seq[c->slot] != c->scene_uploads) {      // the scene table was uploaded since the copy was made
-        DevScene sc = c->scene;
-        sc.buf[AWSM_BUF_CAMERA] = (const uint8_t*)c->shadow_cam[c->slot].ptr;
-        if ((rc = upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc))) return rc;
-        c->shadow_scene_seq[c->slot] = c->scene_uploads;
-    }
     const uint32_t n_tiles = f.tiles_x * f.tiles_y;      // (S >= 1: never 0 — the map is always scanned and rasterised)
-    if (!f.total_tris) { if ((rc = clear_empty_pass(c, sb, n_tiles, c->stream))) return rc; }
+    if (!f.total_tris) { const int rc = clear_empty_pass(c, sb, counters, n_tiles, c->stream); if (rc) return rc; }
     else awsm_launch_transform(c->shadow_scene[c->slot], &f, casters.n_blocks, c->stream);      // through the slot's second scene table
     enqueue_binning(f, f.total_tris != 0, c->stream);
     awsm_launch_raster(&f, c->stream);
     HIPCHK(c, hipGetLastError());
+    return AWSM_OK;
+}
+
+// The slot's second scene table: the context's, with `block` as its camera entry
+static int upload_shadow_scene(AwsmHipCtx* c, const uint8_t* block) {
+    DevScene sc = c->scene;
+    sc.buf[AWSM_BUF_CAMERA] = block;
+    return upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc);
+}
+
+// awsm_hip_shadow_pass's one view: the pass's own list, counters and map; the table copy is made again only when the scene table was uploaded since
+static int enqueue_shadow(AwsmHipCtx* c) {
+    const FrameBufs& sb = pass_bufs(c, kPassShadow);
+    const uint8_t* const block = (const uint8_t*)c->shadow_cam[c->slot].ptr;
+    int rc;
+    if ((rc = sync_scene(c))) return rc;
+    if (c->shadow_scene_seq[c->slot] != c->scene_uploads) {
+        if ((rc = upload_shadow_scene(c, block))) return rc;
+        c->shadow_scene_seq[c->slot] = c->scene_uploads;
+    }
+    return enqueue_shadow_view(c, c->lists[kPassShadow], block, (uint32_t*)sb.counters.ptr, (unsigned long long*)sb.vis.ptr);
+}
+
+// awsm_hip_shadow_pass_views' views, in their order on the caller's stream, into layer i of the slot's stack of maps.  The views
+// share the pass's vertex arrays, setup records, tile tables and lists: in front of each view's kernels its draw list goes into the pass's list
+// buffer and its block into the slot's second table.  Each view counts its overflow in 16 words of its own.
+static int enqueue_shadow_views(AwsmHipCtx* c) {
+    FrameBufs& sb = pass_bufs(c, kPassShadow);
+    const AwsmHipCtx::ShadowViews& views = c->shadow_views[c->slot];
+    const size_t S = c->shadow_pass[c->slot].p.map_size;
+    int rc;
+    if ((rc = sync_scene(c))) return rc;
+    c->shadow_scene_seq[c->slot] = ~0ull;      // the slot's second table is rewritten per view: awsm_hip_shadow_pass makes its own copy anew
+    for (uint32_t i = 0; i < views.n; i++) {
+        const uint8_t* const block = (const uint8_t*)c->shadow_cam[c->slot].ptr + (size_t)i * 512;
+        if ((rc = upload_draw_list(c, sb, views.lists[i].draws, false))) return rc;
+        if ((rc = upload_shadow_scene(c, block))) return rc;
+        if ((rc = enqueue_shadow_view(c, views.lists[i], block, (uint32_t*)c->shadow_view_ctr[c->slot].ptr + (size_t)i * 16, (unsigned long long*)sb.vis.ptr + i * S * S))) return rc;
+    }
+    return AWSM_OK;
+}
+
+// The frame's shadow pass once more (awsm_hip_frame_end's replay; the light blocks are still in the slot's copy), and the counters it is judged
+// by: the pass's own, or of a pass of views the largest need of any view and whether any view lost entries.
+static int enqueue_frame_shadow(AwsmHipCtx* c) { return c->shadow_views[c->slot].n ? enqueue_shadow_views(c) : enqueue_shadow(c); }
+static int read_shadow_counters(AwsmHipCtx* c, uint32_t worst[kCtrWords]) {
+    const uint32_t n = c->shadow_views[c->slot].n;
+    if (!n) { HIPCHK(c, hipMemcpy(worst, pass_bufs(c, kPassShadow).counters.ptr, kCtrWords * sizeof(uint32_t), hipMemcpyDeviceToHost)); return AWSM_OK; }
+    uint32_t per_view[AWSM_SHADOW_MAX_VIEWS][16];
+    HIPCHK(c, hipMemcpy(per_view, c->shadow_view_ctr[c->slot].ptr, (size_t)n * sizeof per_view[0], hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        worst[kCtrEntries] = std::max(worst[kCtrEntries], per_view[i][kCtrEntries]);
+        worst[kCtrOverflow] |= per_view[i][kCtrOverflow];
+    }
     return AWSM_OK;
 }
 
@@ -1474,33 +1524,62 @@ int awsm_hip_shadow_defaults(AwsmShadow* out) {
     return AWSM_OK;
 }
 
+// What the two entries check alike.  `entry` names the caller in every message; `one` is its word for light[3] = 1.
+// The AwsmShadow record: the caller's fields over the defaults, finite and in range -> full
+static int check_shadow_record(AwsmHipCtx* c, const char* entry, const char* one, const AwsmShadow* s, AwsmShadow& full) {
+    awsm_hip_shadow_defaults(&full);
+    { const int rcm = merge_record(c, entry, "AwsmShadow", s, &full, sizeof full); if (rcm) return rcm; }
+    { const int rcf = check_finite(c, entry, full.light, 9); if (rcf) return rcf; }      // light[4] and the five parameters are contiguous
+    static_assert(offsetof(AwsmShadow, facing_fade) == offsetof(AwsmShadow, light) + 8 * sizeof(float) && sizeof(AwsmShadow) == 48, "AwsmShadow: light[4] and five floats behind three words");
+    if (full.map_size < 1u || full.map_size > 8192u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: map_size = %u (1 .. 8192)", entry, full.map_size);
+    if (full.pcf_radius > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: pcf_radius = %u (0, 1 or 2)", entry, full.pcf_radius);
+    if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: strength = %g (0 .. 1)", entry, (double)full.strength);
+    if (!(full.facing_fade > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: facing_fade = %g (> 0)", entry, (double)full.facing_fade);
+    if (!(full.max_slope >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: max_slope = %g (>= 0)", entry, (double)full.max_slope);
+    if (full.light[3] != 0.0f && full.light[3] != 1.0f) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: light[3] = %g (0: directional, 1: %s)", entry, (double)full.light[3], one);
+    return AWSM_OK;
+}
+// A light block: 512 bytes in the camera buffer's layout with a finite view_proj -> lvp.  label: the entry, or the entry and the view.
+static int check_light_block(AwsmHipCtx* c, const char* label, const void* block, size_t bytes, float lvp[16]) {
+    if (!block || bytes != 512) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", label, bytes);
+    memcpy(lvp, (const uint8_t*)block + 128, 16 * sizeof(float));
+    for (int k = 0; k < 16; k++) if (!std::isfinite(lvp[k])) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: the light camera's view_proj is not finite", label);
+    return AWSM_OK;
+}
+// The scene buffers a pass with casters reads
+static int check_caster_buffers(AwsmHipCtx* c, const char* entry) {
+    for (AwsmBuf b : {AWSM_BUF_TRANSFORMS, AWSM_BUF_GEOM_META, AWSM_BUF_VIS_GEOM_DATA}) if (!c->bufs[b].ptr) return fail(c, AWSM_ERR_NOT_READY, "%s: buffer %d missing", entry, (int)b);
+    return AWSM_OK;
+}
+// What a slot's shadow pass has besides its FrameBufs, made at the first use: the pass's 16 counter words, 16 per view for a pass of views
+// (view_slots = AWSM_SHADOW_MAX_VIEWS; 0: none), the second scene table, and room for cam_blocks light blocks.
+static int reserve_shadow_slot(AwsmHipCtx* c, uint32_t view_slots, uint32_t cam_blocks) {
+    DevBuf* const words[2] = {&pass_bufs(c, kPassShadow).counters, &c->shadow_view_ctr[c->slot]};
+    const size_t bytes[2] = {16 * sizeof(uint32_t), (size_t)view_slots * 16 * sizeof(uint32_t)};
+    for (int k = 0; k < 2; k++) if (bytes[k] && !words[k]->ptr) {
+        HIPCHK(c, hipMalloc(&words[k]->ptr, bytes[k]));
+        words[k]->size = bytes[k];
+        HIPCHK(c, hipMemsetAsync(words[k]->ptr, 0, bytes[k], c->stream));
+    }
+    if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
+    return dev_reserve(c, c->shadow_cam[c->slot], (size_t)cam_blocks * 512);
+}
+
 int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_camera, size_t camera_bytes, const AwsmDraw* casters, uint32_t n) {
     if (!c || !s || (!casters && n)) return AWSM_ERR_INVALID_ARGUMENT;
     if (!c->geometry_done || c->opaque_done) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass goes between the geometry pass and the opaque pass of a frame");
     if (is_sharded(c))
         return fail(c, AWSM_ERR_UNSUPPORTED, "shadow_pass on a sharded context: the resolve's neighbours need rows the shard never rasterised (no halo exchange)");
     AwsmShadow full;
-    awsm_hip_shadow_defaults(&full);
-    { const int rcm = merge_record(c, "shadow_pass", "AwsmShadow", s, &full, sizeof full); if (rcm) return rcm; }
-    if (!light_camera || camera_bytes != 512) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", camera_bytes);
-    { const int rcf = check_finite(c, "shadow_pass", full.light, 9); if (rcf) return rcf; }      // light[4] and the five parameters are contiguous
-    static_assert(offsetof(AwsmShadow, facing_fade) == offsetof(AwsmShadow, light) + 8 * sizeof(float) && sizeof(AwsmShadow) == 48, "AwsmShadow: light[4] and five floats behind three words");
     float lvp[16];
-    memcpy(lvp, (const uint8_t*)light_camera + 128, sizeof lvp);
-    for (float m : lvp) if (!std::isfinite(m)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: the light camera's view_proj is not finite");
-    if (full.map_size < 1u || full.map_size > 8192u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: map_size = %u (1 .. 8192)", full.map_size);
-    if (full.pcf_radius > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: pcf_radius = %u (0, 1 or 2)", full.pcf_radius);
-    if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: strength = %g (0 .. 1)", (double)full.strength);
-    if (!(full.facing_fade > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: facing_fade = %g (> 0)", (double)full.facing_fade);
-    if (!(full.max_slope >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: max_slope = %g (>= 0)", (double)full.max_slope);
-    if (full.light[3] != 0.0f && full.light[3] != 1.0f) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass: light[3] = %g (0: directional, 1: spot)", (double)full.light[3]);
-    static const AwsmBuf need[] = {AWSM_BUF_TRANSFORMS, AWSM_BUF_GEOM_META, AWSM_BUF_VIS_GEOM_DATA};
-    if (n) for (AwsmBuf b : need) if (!c->bufs[b].ptr) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass: buffer %d missing", (int)b);
+    int rc;
+    if ((rc = check_shadow_record(c, "shadow_pass", "spot", s, full))) return rc;
+    if ((rc = check_light_block(c, "shadow_pass", light_camera, camera_bytes, lvp))) return rc;
+    if (n && (rc = check_caster_buffers(c, "shadow_pass"))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<DrawDev> list;
     uint64_t tris = 0, blocks = 0;
-    int rc = build_draw_list(c, "shadow_pass", casters, n, AWSM_BUF_VIS_GEOM_DATA, 168u, list, &tris, &blocks);
-    if (rc) return rc;
+    if ((rc = build_draw_list(c, "shadow_pass", casters, n, AWSM_BUF_VIS_GEOM_DATA, 168u, list, &tris, &blocks))) return rc;
     // nothing refused from here on but for memory: the slot's state is this pass's
     FrameBufs& sb = pass_bufs(c, kPassShadow);
     PassList& cast = c->lists[kPassShadow];
@@ -1509,13 +1588,7 @@ int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_c
     st.p = full; memcpy(st.light_view_proj, lvp, sizeof lvp);
     cast.draws.swap(list);
     cast.total_tris = (uint32_t)tris; cast.n_blocks = (uint32_t)blocks;
-    if (!sb.counters.ptr) {
-        HIPCHK(c, hipMalloc(&sb.counters.ptr, 16 * sizeof(uint32_t)));
-        sb.counters.size = 16 * sizeof(uint32_t);
-        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, sb.counters.size, c->stream));
-    }
-    if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
-    if ((rc = dev_reserve(c, c->shadow_cam[c->slot], 512))) return rc;
+    if ((rc = reserve_shadow_slot(c, 0u, 1u))) return rc;
     if ((rc = dev_reserve(c, sb.vis, (size_t)full.map_size * full.map_size * 8))) return rc;
     if ((rc = reserve_pass_buffers(c, sb, cast.draws, cast.total_tris, false))) return rc;
     if ((rc = upload_small(c, c->shadow_cam[c->slot].ptr, light_camera, 512))) return rc;      // through the pinned ring, as small writes are
@@ -1525,52 +1598,7 @@ int awsm_hip_shadow_pass(AwsmHipCtx* c, const AwsmShadow* s, const void* light_c
     return AWSM_OK;
 }
 
-// ---- several views of one light ----
-// enqueue_shadow's chain once per view, in the views' order on the caller's stream, into layer i of the slot's stack of maps.  The views share the
-// shadow pass's vertex arrays, setup records, tile tables and lists; in front of each view's kernels its draw list goes into the pass's list buffer
-// and a scene table whose camera entry is the view's block into the slot's second table.  Each view counts its overflow in words of its own.
-static int enqueue_shadow_views(AwsmHipCtx* c) {
-    FrameBufs& sb = pass_bufs(c, kPassShadow);
-    const AwsmHipCtx::ShadowViews& views = c->shadow_views[c->slot];
-    const uint32_t S = c->shadow_pass[c->slot].p.map_size;
-    int rc;
-    if ((rc = sync_scene(c))) return rc;
-    c->shadow_scene_seq[c->slot] = ~0ull;      // the slot's second table is rewritten per view: awsm_hip_shadow_pass makes its own copy anew
-    for (uint32_t i = 0; i < views.n; i++) {
-        const PassList& casters = views.lists[i];
-        const uint8_t* const block = (const uint8_t*)c->shadow_cam[c->slot].ptr + (size_t)i * 512;
-        uint32_t* const counters = (uint32_t*)c->shadow_view_ctr[c->slot].ptr + (size_t)i * 16;
-        if ((rc = upload_draw_list(c, sb, casters.draws, false))) return rc;
-        FrameDev f;
-        memset(&f, 0, sizeof f);
-        f.width = S; f.height = S; f.y0 = 0; f.y1 = S; f.sy0 = 0; f.sy1 = S;
-        f.tiles_x = (S + kTile - 1) / kTile; f.tiles_y = f.tiles_x; f.tile_row0 = 0;
-        f.band_n = 1; f.band_r = 0; f.out_compact = 0;
-        f.n_draws = (uint32_t)casters.draws.size();
-        f.total_tris = casters.total_tris; f.total_verts = 3u * casters.total_tris;
-        f.msaa = 0;
-        f.camera = block;
-        bind_pass(f, sb);
-        f.counters = counters;
-        f.vis = (unsigned long long*)sb.vis.ptr + (size_t)i * S * S;
-        f.poison = c->handoff_poison ? c->handoff_poison + c->slot : nullptr;
-        f.frame_serial = c->frame_serial;
-        DevScene sc = c->scene;
-        sc.buf[AWSM_BUF_CAMERA] = block;
-        if ((rc = upload_small(c, c->shadow_scene[c->slot], &sc, sizeof sc))) return rc;
-        const uint32_t n_tiles = f.tiles_x * f.tiles_y;
-        if (!f.total_tris) {      // clear_empty_pass, on the view's own counters
-            HIPCHK(c, hipMemsetAsync(counters, 0, kCtrWords * sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(counters + 12, 0, 2 * sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(sb.tile_count.ptr, 0, n_tiles * sizeof(uint32_t), c->stream));
-        } else awsm_launch_transform(c->shadow_scene[c->slot], &f, casters.n_blocks, c->stream);
-        enqueue_binning(f, f.total_tris != 0, c->stream);
-        awsm_launch_raster(&f, c->stream);
-        HIPCHK(c, hipGetLastError());
-    }
-    return AWSM_OK;
-}
-
+// Several views of one light
 int awsm_hip_shadow_pass_views(AwsmHipCtx* c, const AwsmShadow* s, const AwsmShadowView* views, uint32_t n_views) {
     if (!c || !s) return AWSM_ERR_INVALID_ARGUMENT;
     if (!views || n_views < 1u || n_views > (uint32_t)AWSM_SHADOW_MAX_VIEWS)
@@ -1579,38 +1607,26 @@ int awsm_hip_shadow_pass_views(AwsmHipCtx* c, const AwsmShadow* s, const AwsmSha
     if (is_sharded(c))
         return fail(c, AWSM_ERR_UNSUPPORTED, "shadow_pass_views on a sharded context: the resolve's neighbours need rows the shard never rasterised (no halo exchange)");
     AwsmShadow full;
-    awsm_hip_shadow_defaults(&full);
-    { const int rcm = merge_record(c, "shadow_pass_views", "AwsmShadow", s, &full, sizeof full); if (rcm) return rcm; }
-    { const int rcf = check_finite(c, "shadow_pass_views", full.light, 9); if (rcf) return rcf; }
-    if (full.map_size < 1u || full.map_size > 8192u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: map_size = %u (1 .. 8192)", full.map_size);
-    if (full.pcf_radius > 2u) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: pcf_radius = %u (0, 1 or 2)", full.pcf_radius);
-    if (!(full.strength >= 0.0f && full.strength <= 1.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: strength = %g (0 .. 1)", (double)full.strength);
-    if (!(full.facing_fade > 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: facing_fade = %g (> 0)", (double)full.facing_fade);
-    if (!(full.max_slope >= 0.0f)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: max_slope = %g (>= 0)", (double)full.max_slope);
-    if (full.light[3] != 0.0f && full.light[3] != 1.0f) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: light[3] = %g (0: directional, 1: positional)", (double)full.light[3]);
+    int rc;
+    if ((rc = check_shadow_record(c, "shadow_pass_views", "positional", s, full))) return rc;
     float lvp[AWSM_SHADOW_MAX_VIEWS][16];
     uint8_t blocks_host[AWSM_SHADOW_MAX_VIEWS * 512];
+    char label[AWSM_SHADOW_MAX_VIEWS][40];      // "shadow_pass_views: view i"
     bool any_casters = false;
     for (uint32_t i = 0; i < n_views; i++) {
         const AwsmShadowView& v = views[i];
+        snprintf(label[i], sizeof label[i], "shadow_pass_views: view %u", i);
         if (!v.casters && v.n_casters) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u has %u casters at a null pointer", i, v.n_casters);
-        if (!v.light_camera || v.camera_bytes != 512)
-            return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u: the light camera is a 512-byte block in the layout of AWSM_BUF_CAMERA (got %zu bytes)", i, v.camera_bytes);
+        if ((rc = check_light_block(c, label[i], v.light_camera, v.camera_bytes, lvp[i]))) return rc;
         memcpy(blocks_host + (size_t)i * 512, v.light_camera, 512);
-        memcpy(lvp[i], (const uint8_t*)v.light_camera + 128, sizeof lvp[i]);
-        for (float m : lvp[i]) if (!std::isfinite(m)) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "shadow_pass_views: view %u: the light camera's view_proj is not finite", i);
         any_casters |= v.n_casters != 0;
     }
-    static const AwsmBuf need[] = {AWSM_BUF_TRANSFORMS, AWSM_BUF_GEOM_META, AWSM_BUF_VIS_GEOM_DATA};
-    if (any_casters) for (AwsmBuf b : need) if (!c->bufs[b].ptr) return fail(c, AWSM_ERR_NOT_READY, "shadow_pass_views: buffer %d missing", (int)b);
+    if (any_casters && (rc = check_caster_buffers(c, "shadow_pass_views"))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     PassList lists[AWSM_SHADOW_MAX_VIEWS];
     for (uint32_t i = 0; i < n_views; i++) {
-        char name[40];
-        snprintf(name, sizeof name, "shadow_pass_views: view %u", i);
         uint64_t tris = 0, blocks = 0;
-        const int rcl = build_draw_list(c, name, views[i].casters, views[i].n_casters, AWSM_BUF_VIS_GEOM_DATA, 168u, lists[i].draws, &tris, &blocks);
-        if (rcl) return rcl;
+        if ((rc = build_draw_list(c, label[i], views[i].casters, views[i].n_casters, AWSM_BUF_VIS_GEOM_DATA, 168u, lists[i].draws, &tris, &blocks))) return rc;
         lists[i].total_tris = (uint32_t)tris; lists[i].n_blocks = (uint32_t)blocks;
     }
     // nothing refused from here on but for memory: the slot's state is this pass's
@@ -1622,20 +1638,7 @@ int awsm_hip_shadow_pass_views(AwsmHipCtx* c, const AwsmShadow* s, const AwsmSha
     vs.n = n_views; memcpy(vs.view_proj, lvp, sizeof vs.view_proj);
     for (uint32_t i = 0; i < n_views; i++) { vs.lists[i].draws.swap(lists[i].draws); vs.lists[i].total_tris = lists[i].total_tris; vs.lists[i].n_blocks = lists[i].n_blocks; }
     c->lists[kPassShadow] = PassList();
-    int rc;
-    if (!sb.counters.ptr) {      // (the pass's own words, as awsm_hip_shadow_pass makes them: a later pass through it finds them)
-        HIPCHK(c, hipMalloc(&sb.counters.ptr, 16 * sizeof(uint32_t)));
-        sb.counters.size = 16 * sizeof(uint32_t);
-        HIPCHK(c, hipMemsetAsync(sb.counters.ptr, 0, sb.counters.size, c->stream));
-    }
-    DevBuf& ctr = c->shadow_view_ctr[c->slot];
-    if (!ctr.ptr) {
-        HIPCHK(c, hipMalloc(&ctr.ptr, AWSM_SHADOW_MAX_VIEWS * 16 * sizeof(uint32_t)));
-        ctr.size = AWSM_SHADOW_MAX_VIEWS * 16 * sizeof(uint32_t);
-        HIPCHK(c, hipMemsetAsync(ctr.ptr, 0, ctr.size, c->stream));
-    }
-    if (!c->shadow_scene[c->slot]) { HIPCHK(c, hipMalloc((void**)&c->shadow_scene[c->slot], sizeof(DevScene))); c->shadow_scene_seq[c->slot] = 0; }
-    if ((rc = dev_reserve(c, c->shadow_cam[c->slot], (size_t)AWSM_SHADOW_MAX_VIEWS * 512))) return rc;
+    if ((rc = reserve_shadow_slot(c, AWSM_SHADOW_MAX_VIEWS, AWSM_SHADOW_MAX_VIEWS))) return rc;      // (the pass's own words too: a later awsm_hip_shadow_pass finds them)
     if ((rc = dev_reserve(c, sb.vis, (size_t)n_views * full.map_size * full.map_size * 8))) return rc;
     for (uint32_t i = 0; i < n_views; i++)      // grow-only: the arrays end up sized for the largest view
         if ((rc = ensure_pass_capacity(c, sb, vs.lists[i].draws, vs.lists[i].total_tris, false))) return rc;
@@ -1645,17 +1648,20 @@ int awsm_hip_shadow_pass_views(AwsmHipCtx* c, const AwsmShadow* s, const AwsmSha
     return AWSM_OK;
 }
 
-int awsm_hip_read_shadow_map_view(AwsmHipCtx* c, uint32_t view, uint64_t* keys) {
+// Layer `view` of the last submitted frame's maps; `entry` names the caller in what is refused
+static int read_shadow_layer(AwsmHipCtx* c, const char* entry, uint32_t view, uint64_t* keys) {
     if (!c || !keys) return AWSM_ERR_INVALID_ARGUMENT;
-    if (!c->shadow_done || !c->shadow[c->slot].vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_shadow_map_view: the last submitted frame had no shadow pass");
+    if (!c->shadow_done || !c->shadow[c->slot].vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "%s: the last submitted frame had no shadow pass", entry);
     const uint32_t n = std::max(c->shadow_views[c->slot].n, 1u);
-    if (view >= n) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "read_shadow_map_view: view %u of a pass with %u", view, n);
+    if (view >= n) return fail(c, AWSM_ERR_INVALID_ARGUMENT, "%s: view %u of a pass with %u", entry, view, n);
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
     const size_t S = c->shadow_pass[c->slot].p.map_size;
     HIPCHK(c, hipMemcpy(keys, (const uint64_t*)c->shadow[c->slot].vis.ptr + (size_t)view * S * S, S * S * 8, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
+int awsm_hip_read_shadow_map(AwsmHipCtx* c, uint64_t* keys) { return read_shadow_layer(c, "read_shadow_map", 0u, keys); }
+int awsm_hip_read_shadow_map_view(AwsmHipCtx* c, uint32_t view, uint64_t* keys) { return read_shadow_layer(c, "read_shadow_map_view", view, keys); }
 
 int awsm_hip_read_shadow_view(AwsmHipCtx* c, uint8_t* view_out) {
     if (!c || !view_out) return AWSM_ERR_INVALID_ARGUMENT;
@@ -1665,16 +1671,6 @@ int awsm_hip_read_shadow_view(AwsmHipCtx* c, uint8_t* view_out) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rcs = sync_all(c); if (rcs) return rcs; }
     HIPCHK(c, hipMemcpy(view_out, c->shadow_view_layers[c->slot].ptr, px, hipMemcpyDeviceToHost));
-    return AWSM_OK;
-}
-
-int awsm_hip_read_shadow_map(AwsmHipCtx* c, uint64_t* keys) {
-    if (!c || !keys) return AWSM_ERR_INVALID_ARGUMENT;
-    if (!c->shadow_done || !c->shadow[c->slot].vis.ptr) return fail(c, AWSM_ERR_NOT_READY, "read_shadow_map: the last submitted frame had no shadow pass");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rcs = sync_all(c); if (rcs) return rcs; }
-    const size_t S = c->shadow_pass[c->slot].p.map_size;
-    HIPCHK(c, hipMemcpy(keys, c->shadow[c->slot].vis.ptr, S * S * 8, hipMemcpyDeviceToHost));
     return AWSM_OK;
 }
 
@@ -1866,16 +1862,7 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         { int rch = handoff_check(c); if (rch) return rch; }      // a gate ended unopened: the frame it guarded was dropped
         memset(c->counters_host + 8, 0, 8 * sizeof(uint32_t));
         uint32_t hud_fwd[kCtrWords] = {}, hud_geo[kCtrWords] = {}, shadow_geo[kCtrWords] = {};      // the HUD transparent pass's, the HUD geometry pass's and the shadow pass's own counters (same layout)
-        const uint32_t shadow_n_views = c->shadow_done ? c->shadow_views[c->slot].n : 0u;
-        if (shadow_n_views) {      // a pass of views: the largest need of any view, and whether any view lost entries
-            uint32_t per_view[AWSM_SHADOW_MAX_VIEWS][16];
-            HIPCHK(c, hipMemcpy(per_view, c->shadow_view_ctr[c->slot].ptr, (size_t)shadow_n_views * sizeof per_view[0], hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < shadow_n_views; i++) {
-                shadow_geo[kCtrEntries] = std::max(shadow_geo[kCtrEntries], per_view[i][kCtrEntries]);
-                shadow_geo[kCtrOverflow] |= per_view[i][kCtrOverflow];
-            }
-        } else
-        if (c->shadow_done) HIPCHK(c, hipMemcpy(shadow_geo, pass_bufs(c, kPassShadow).counters.ptr, sizeof shadow_geo, hipMemcpyDeviceToHost));
+        if (c->shadow_done) { const int rcs = read_shadow_counters(c, shadow_geo); if (rcs) return rcs; }
         if (c->transparent_done) HIPCHK(c, hipMemcpy(c->counters_host + 8, pass_bufs(c, kPassTransparent).counters.ptr, kCtrWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (c->hud_transparent_done) HIPCHK(c, hipMemcpy(hud_fwd, pass_bufs(c, kPassHudTransparent).counters.ptr, sizeof hud_fwd, hipMemcpyDeviceToHost));
         if (c->hud_geometry_done) HIPCHK(c, hipMemcpy(hud_geo, pass_bufs(c, kPassHud).counters.ptr, sizeof hud_geo, hipMemcpyDeviceToHost));
@@ -1900,7 +1887,7 @@ int awsm_hip_frame_end(AwsmHipCtx* c, AwsmFrameStats* out) {
         }
         if (shadow_over) {      // the light's pass, in its place between the geometry passes and the opaque pass; the light block is still in the slot's copy
             if ((rc = grow_after_overflow(c, pass_bufs(c, kPassShadow), shadow_geo))) return rc;
-            if ((rc = shadow_n_views ? enqueue_shadow_views(c) : enqueue_shadow(c))) return rc;      // (every view again, in order)
+            if ((rc = enqueue_frame_shadow(c))) return rc;      // (of a pass of views every view again, in order)
         }
         if ((geom_over || hud_geo_over || shadow_over) && c->opaque_done && (rc = enqueue_opaque(c))) return rc;
         // (the transparent passes have a tile kernel of their own: no raster items to size with their lists)

@@ -2174,23 +2174,30 @@ static void shadow_cascades(AwsmHost* h, const AwsmHostLight& l, uint32_t S, uin
     }
 }
 
-// The views of a point light or of a cascaded directional one, through awsm_hip_shadow_pass_views
-static int render_shadow_views(AwsmHost* h, const AwsmHostLight& l, AwsmShadow& s) {
-    if (!h->be.shadow_pass_views) return fail(h, AWSM_ERR_UNSUPPORTED, "render: the backend library has no %s", "awsm_hip_shadow_pass_views");
+// called by awsm_host_render between the geometry passes and the opaque pass: the light's views into h->shadow_views (one for a spot light or an
+// uncascaded sun, the cube's faces with casters for a point light, the cascades otherwise), then through awsm_hip_shadow_pass or ..._views
+static int render_shadow_pass(AwsmHost* h) {
+    const AwsmHostLight* l = h->lights.get(h->shadow.light);
+    if (!l) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the shadowed light is gone");      // (checked at the top of the render too)
+    AwsmShadow s{};
+    s.struct_size = (uint32_t)sizeof s;
+    s.map_size = h->shadow.map_size; s.pcf_radius = h->shadow.pcf_radius;
+    s.bias = h->shadow.bias; s.slope_bias = h->shadow.slope_bias; s.max_slope = h->shadow.max_slope; s.strength = h->shadow.strength; s.facing_fade = h->shadow.facing_fade;
+    h->shadow_views.clear();
+    const bool cube = l->kind == 2u, several = cube || (l->kind == 1u && h->shadow_cascades.count > 1u);
     uint8_t blocks[6][512];
-    uint32_t n_blocks;
-    const bool cube = l.kind == 2u;
+    uint32_t n_blocks = 1;
+    if (several && !h->be.shadow_pass_views) return fail(h, AWSM_ERR_UNSUPPORTED, "render: the backend library has no %s", "awsm_hip_shadow_pass_views");
     if (cube) {
         if (s.map_size < 16u) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: a point light's shadow map_size = %u (16 at the least: a face keeps an apron of pcf_radius + 1 texels)", s.map_size);
-        shadow_cube_faces(h, l, s.map_size, s.pcf_radius, blocks);
-        for (int i = 0; i < 3; i++) s.light[i] = l.position[i];
+        shadow_cube_faces(h, *l, s.map_size, s.pcf_radius, blocks);
+        for (int i = 0; i < 3; i++) s.light[i] = l->position[i];
         s.light[3] = 1.0f;
         n_blocks = 6;
-    } else {
+    } else if (several) {
         n_blocks = h->shadow_cascades.count;
-        shadow_cascades(h, l, std::max(1u, s.map_size), n_blocks, blocks, s.light);
-    }
-    h->shadow_views.clear();
+        shadow_cascades(h, *l, std::max(1u, s.map_size), n_blocks, blocks, s.light);
+    } else shadow_light_camera(h, *l, std::max(1u, s.map_size), blocks[0], s.light);
     for (uint32_t i = 0; i < n_blocks; i++) {
         AwsmHost::ShadowViewRec rec;
         memcpy(rec.block, blocks[i], 512);
@@ -2204,34 +2211,12 @@ static int render_shadow_views(AwsmHost* h, const AwsmHostLight& l, AwsmShadow& 
     std::vector<AwsmShadowView> views(h->shadow_views.size());
     for (size_t i = 0; i < views.size(); i++)
         views[i] = AwsmShadowView{h->shadow_views[i].block, 512, h->shadow_views[i].casters.data(), (uint32_t)h->shadow_views[i].casters.size()};
-    const int rc = h->be.shadow_pass_views(h->ctx, &s, views.data(), (uint32_t)views.size());
-    if (rc) { h->shadow_views.clear(); return dev_fail(h, rc, "shadow_pass_views"); }
-    memcpy(h->shadow_block, h->shadow_views[0].block, 512);
+    const int rc = several ? h->be.shadow_pass_views(h->ctx, &s, views.data(), (uint32_t)views.size())
+                           : h->be.shadow_pass(h->ctx, &s, views[0].light_camera, 512, views[0].casters, views[0].n_casters);
+    if (rc) { h->shadow_views.clear(); return dev_fail(h, rc, several ? "shadow_pass_views" : "shadow_pass"); }
+    memcpy(h->shadow_block, h->shadow_views[0].block, 512);      // (view 0, for what reads one block and one list)
     h->shadow_casters = h->shadow_views[0].casters;
     h->shadow_rendered = true;
-    return AWSM_OK;
-}
-
-// called by awsm_host_render between the geometry passes and the opaque pass
-static int render_shadow_pass(AwsmHost* h) {
-    const AwsmHostLight* l = h->lights.get(h->shadow.light);
-    if (!l) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "render: the shadowed light is gone");      // (checked at the top of the render too)
-    AwsmShadow s{};
-    s.struct_size = (uint32_t)sizeof s;
-    s.map_size = h->shadow.map_size; s.pcf_radius = h->shadow.pcf_radius;
-    s.bias = h->shadow.bias; s.slope_bias = h->shadow.slope_bias; s.max_slope = h->shadow.max_slope; s.strength = h->shadow.strength; s.facing_fade = h->shadow.facing_fade;
-    h->shadow_views.clear();
-    if (l->kind == 2u || (l->kind == 1u && h->shadow_cascades.count > 1u)) return render_shadow_views(h, *l, s);
-    shadow_light_camera(h, *l, std::max(1u, s.map_size), h->shadow_block, s.light);
-    Mat4 lvp;
-    memcpy(&lvp, h->shadow_block + 128, 64);
-    collect_draws(h, h->shadow_casters, nullptr, nullptr, nullptr, &lvp);
-    const int rc = h->be.shadow_pass(h->ctx, &s, h->shadow_block, 512, h->shadow_casters.data(), (uint32_t)h->shadow_casters.size());
-    if (rc) return dev_fail(h, rc, "shadow_pass");
-    h->shadow_rendered = true;
-    h->shadow_views.resize(1);
-    memcpy(h->shadow_views[0].block, h->shadow_block, 512);
-    h->shadow_views[0].casters = h->shadow_casters;
     return AWSM_OK;
 }
 

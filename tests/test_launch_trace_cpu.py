@@ -76,11 +76,12 @@ COVERED = on("caller", "count_covered")      # awsm_hip_frame_end with a stats s
 def test_the_script_covers_what_it_should(frames):
     by_frame, text = frames
     scenarios = {k[0] for k in by_frame}
-    assert {"sync", "overlap_handoff", "overlap_events", "hud", "hud_msaa", "hud_msaa_overlap", "shadow", "transparent_grid_selection", "ssao", "post_taa",
+    assert {"sync", "overlap_handoff", "overlap_events", "hud", "hud_msaa", "hud_msaa_overlap", "shadow", "shadow_views", "shadow_views_msaa",
+            "shadow_refusals", "transparent_grid_selection", "ssao", "post_taa",
             "shard_rows", "shard_bands", "shard_bands_msaa", "all_at_once"} <= scenarios
-    assert {"replay_" + w for w in ("world", "hud_geometry", "shadow", "transparent_bins", "transparent_fragments", "hud_transparent_bins",
+    assert {"replay_" + w for w in ("world", "hud_geometry", "shadow", "shadow_views", "transparent_bins", "transparent_fragments", "hud_transparent_bins",
                                     "hud_transparent_fragments")} <= scenarios
-    assert text.count("raises-overflow=") == 9      # one per replay scenario (the seven, the MSAA one, all_at_once)
+    assert text.count("raises-overflow=") == 10      # one per replay scenario (the eight, the MSAA one, all_at_once)
     # the slot-free wait appears: a slot whose shading the host finds unfinished makes the caller's stream wait for it
     assert re.search(r"^H hipEventQuery (ev\d+)\nH hipStreamWaitEvent caller \1$", text, re.M)
 
@@ -140,6 +141,21 @@ def test_shadow_pass(frames):
     assert f["shadow", "no shadow pass"] == geometry() + opaque() + COVERED
 
 
+def test_shadow_pass_views(frames):
+    f, _ = frames
+    resolved = opaque(behind=("shadow_resolve",)) + COVERED      # one resolve for all the views, behind the opaque pass's kernels
+    # the world pass, then every view's chain in the views' order on the caller's stream
+    assert f["shadow_views", "2 views, map 64"] == geometry() + geometry() + geometry() + resolved
+    assert f["shadow_views", "3 views, the middle one empty"] == geometry() + geometry() + empty_geometry() + geometry() + resolved
+    assert f["shadow_views", "6 views"] == geometry() + 6 * geometry() + resolved
+    assert f["shadow_views", "shadow_pass after views"] == geometry() + geometry() + resolved
+    assert f["shadow_views", "1 view"] == geometry() + geometry() + resolved
+    assert f["shadow_views", "no shadow pass"] == geometry() + opaque() + COVERED
+    assert f["shadow_views_msaa", "2 views, map 64"] == geometry() + geometry() + geometry() + resolved      # (the maps are single-sampled)
+    assert f["shadow_views_msaa", "3 views, the middle one empty"] == geometry() + geometry() + empty_geometry() + geometry() + resolved
+    assert f["shadow_refusals", "refused"] == geometry() + opaque() + COVERED      # a refused pass enqueues nothing and leaves no resolve behind
+
+
 def test_transparent_pass_with_grid_and_selection(frames):
     f, _ = frames
     assert f["transparent_grid_selection", "grid + selection"] == geometry() + opaque() + forward(behind=("selection",)) + COVERED
@@ -174,6 +190,10 @@ def test_frame_end_replays_from_the_first_pass_that_lost_entries(frames):
     for what in ("world", "hud_geometry", "shadow"):
         assert f["replay_" + what, "overflowing"] == frame
         assert f["replay_" + what, "frame_end"] == COVERED + geometry() + tail_opaque
+    # a pass of views whose second view lost entries: every view again, in the views' order, then the opaque pass
+    views = geometry() + geometry() + geometry()
+    assert f["replay_shadow_views", "overflowing"] == geometry() + geometry() + views + frame[len(3 * geometry()):]
+    assert f["replay_shadow_views", "frame_end"] == COVERED + views + tail_opaque
     # behind a transparent pass's list, bins or fragments, the world's or the HUD's: the world transparent pass first, always
     for what in ("transparent_bins", "transparent_fragments", "hud_transparent_bins", "hud_transparent_fragments"):
         assert f["replay_" + what, "overflowing"] == frame

@@ -3,7 +3,7 @@
 Builds csrc/awsm_hip.cpp and csrc/awsm_resources.cpp host-only, links them with tests/trace/trace_hip.cpp — a stand-in for the HIP runtime and for
 every launch wrapper — and runs one fixed script of small frames over awsm-renderer_amd/hip_backend.py.  The library writes what the host layer
 enqueued: one line per launch wrapper (`L name stream scalars args=<hash of the argument struct>`), per traced runtime call (`H ...`), per
-scenario (`== name`) and per note of this script (`-- ...`: the frame statistics).  Two trees whose host layers enqueue the same thing give the
+scenario (`== name`) and per note of this script (`-- ...`: the frame statistics, a refused call's status and text).  Two trees whose host layers enqueue the same thing give the
 same file byte for byte; --verbose adds the argument structs' words, so that a difference names its offset.
 
     python tests/trace/driver.py --out trace.txt [--csrc DIR] [--verbose] [--only NAME]
@@ -106,6 +106,15 @@ class Script:
     def arm(self, which, needed=6000, skip=0):
         self.lib.awsm_trace_arm(which, skip, needed)
 
+    def refused(self, call):
+        """`call` must be refused by the backend: its status and text go into the trace (pointer values, which differ from run to run, do not)."""
+        try:
+            call()
+        except self.hb.AwsmHipError as e:
+            self.note("refused: " + re.sub(r"0x[0-9a-f]+", "0x*", str(e)))
+        else:
+            raise AssertionError("the backend accepted what the script expects it to refuse")
+
     def light(self):
         return self.np.tile(self.np.eye(4, dtype=self.np.float32).reshape(-1), 8).tobytes()
 
@@ -164,6 +173,62 @@ class Script:
             d.geometry_pass(WORLD); d.shadow_pass(self.light(), casters, map_size=size); d.opaque_pass(); self.end(d)
         self.note(d.read_shadow_map().shape)
         self.frame("no shadow pass"); d.geometry_pass(WORLD); d.opaque_pass(); self.end(d)      # no shadow pass in a frame: no resolve in that frame
+        d.close()
+
+    def shadow_views(self, name, msaa=0):
+        """Passes of several views, then the two entries in turn on one device (MSAA: the first two frames only)."""
+        self.begin(name)
+        d = self.device(msaa=msaa)
+        view, empty = (self.light(), CASTERS), (self.light(), [])
+        frames = [("2 views, map 64", [view, view]), ("3 views, the middle one empty", [view, empty, view])]
+        if not msaa:
+            frames += [("6 views", [view] * 6), ("shadow_pass after views", None), ("1 view", [view])]
+        for label, views in frames:
+            self.frame(label)
+            d.geometry_pass(WORLD)
+            if views is None:      # the slot's scene-table copy was overwritten per view: this pass makes its own anew
+                d.shadow_pass(self.light(), CASTERS, map_size=64)
+            else:
+                d.shadow_pass_views(views, map_size=64)
+            d.opaque_pass(); self.end(d)
+            if label.startswith("2 views"):
+                self.note(d.read_shadow_map(view=1).shape)
+                self.note(d.read_shadow_map().shape)
+        if not msaa:
+            self.frame("no shadow pass"); d.geometry_pass(WORLD); d.opaque_pass(); self.end(d)
+            self.refused(lambda: d.read_shadow_map(view=1))      # nothing to read: each entry answers in its own words
+            self.refused(lambda: d.read_shadow_map())
+        d.close()
+
+    def shadow_refusals(self, name):
+        """What the two entries refuse, in the words they refuse it with (the texts are part of the trace: two trees must agree on them)."""
+        self.begin(name)
+        d = self.device()
+        np = self.np
+        nan, inf = float("nan"), float("inf")
+        poisoned = np.frombuffer(self.light(), np.float32).copy(); poisoned[35] = nan
+        broken = [dict(CASTERS[0], tri_count=1 << 30)]
+        bad_records = (dict(map_size=0), dict(map_size=8193), dict(pcf_radius=3), dict(strength=1.5), dict(strength=-0.1), dict(facing_fade=0.0), dict(max_slope=-0.01),
+                       dict(light=(0.0, 1.0, 0.0, 0.5)), dict(light=(nan, 1.0, 0.0, 0.0)), dict(bias=nan), dict(slope_bias=inf), dict(struct_size=2), dict(struct_size=5000))
+        single = lambda block=self.light(), casters=CASTERS, **kw: d.shadow_pass(block, casters, **kw)
+        views = lambda v=((self.light(), CASTERS), (self.light(), CASTERS)), **kw: d.shadow_pass_views(v, **kw)
+        self.refused(single); self.refused(views)      # before the frame's geometry pass
+        self.frame("refused"); d.geometry_pass(WORLD)
+        for bad in bad_records:
+            self.refused(lambda: single(**bad)); self.refused(lambda: views(**bad))
+        for block in (self.light()[:508], self.light() + bytes(4), b"", poisoned.tobytes()):
+            self.refused(lambda: single(block)); self.refused(lambda: views([(self.light(), CASTERS), (block, CASTERS)]))
+        self.refused(lambda: single(casters=broken)); self.refused(lambda: views([(self.light(), CASTERS), (self.light(), broken)]))
+        for bad in (dict(v=[]), dict(n_views=0), dict(v=[(self.light(), CASTERS)] * 7), dict(n_views=7)):
+            self.refused(lambda: views(**bad))
+        d.opaque_pass(); self.end(d)      # no pass was accepted: no resolve
+        self.refused(single); self.refused(views)      # the window has closed
+        d.close()
+        self.frame("sharded context")
+        d = self.device()
+        d.set_shard_rows(16, 40)
+        d.geometry_pass(WORLD)
+        self.refused(single); self.refused(views)      # a sharded context
         d.close()
 
     def transparent(self, name, msaa=0):
@@ -242,7 +307,11 @@ class Script:
             if last and what == "hud_geometry": self.arm(0)
             d.hud_geometry_pass(HUD)
             if last and what == "shadow": self.arm(0)
-            d.shadow_pass(self.light(), CASTERS, map_size=64)
+            if last and what == "shadow_views": self.arm(0, skip=1)      # the second view's scan: the flag goes up in that view's own counter words
+            if what == "shadow_views":
+                d.shadow_pass_views([(self.light(), CASTERS)] * 3, map_size=64)
+            else:
+                d.shadow_pass(self.light(), CASTERS, map_size=64)
             d.opaque_pass()
             if last and what == "transparent_bins": self.arm(0)
             if last and what == "transparent_fragments": self.arm(1)
@@ -268,6 +337,9 @@ class Script:
         yield "hud_msaa_overlap", lambda n: self.hud(n, 4, overlap=True)
         yield "shadow", lambda n: self.shadow(n)
         yield "shadow_msaa", lambda n: self.shadow(n, 4)
+        yield "shadow_views", lambda n: self.shadow_views(n)
+        yield "shadow_views_msaa", lambda n: self.shadow_views(n, 4)
+        yield "shadow_refusals", lambda n: self.shadow_refusals(n)
         yield "transparent_grid_selection", lambda n: self.transparent(n)
         yield "transparent_grid_selection_msaa", lambda n: self.transparent(n, 4)
         yield "ssao", lambda n: self.ssao(n)
@@ -278,7 +350,7 @@ class Script:
         yield "shard_rows_msaa", lambda n: self.shards(n, False, 4)
         yield "shard_bands", lambda n: self.shards(n, True)
         yield "shard_bands_msaa", lambda n: self.shards(n, True, 4)
-        for what in ("world", "hud_geometry", "shadow", "transparent_bins", "transparent_fragments", "hud_transparent_bins", "hud_transparent_fragments"):
+        for what in ("world", "hud_geometry", "shadow", "shadow_views", "transparent_bins", "transparent_fragments", "hud_transparent_bins", "hud_transparent_fragments"):
             yield "replay_" + what, lambda n, w=what: self.replay(n, w)
         yield "replay_world_msaa", lambda n: self.replay(n, "world", msaa=4)             # the merged hud keys: a new world pass needs a new merge
         yield "all_at_once", lambda n: self.replay(n, "world", msaa=4, overlap=True)     # every pass, overlapped, MSAA, and a replay of all of it
