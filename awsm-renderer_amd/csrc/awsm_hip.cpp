@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "bin_record.hpp"
 #include "launch.hpp"
 
 using namespace awsm;
@@ -413,6 +414,25 @@ int clear_empty_pass(AwsmHipCtx* c, const FrameBufs& b, uint32_t* counters, uint
     return AWSM_OK;
 }
 
+// The slot's last world pass formed its clip positions in the binning and stored none (FrameDev::clip_from_world): form them now, from the slot's
+// wcache and the camera snapshot that frame was submitted with, into the slot's clip buffer (awsm_hip_read_transformed; and in front of anything
+// that replaces the snapshot outside a geometry pass).  Enqueued on the caller's stream, which the world pass ran on.
+int materialize_clip(AwsmHipCtx* c) {
+    FrameBufs& b = FB(c);
+    if (!b.clip_in_bin_last) return AWSM_OK;
+    const uint32_t n = 3u * c->lists[kPassWorld].total_tris;
+    if (n && b.wcache.ptr && b.clip.ptr && b.camera.ptr) {
+        FrameDev f;
+        memset(&f, 0, sizeof f);
+        f.wcache = (float4*)b.wcache.ptr; f.clip = (float4*)b.clip.ptr; f.camera = (const uint8_t*)b.camera.ptr;
+        f.total_verts = n; f.clip_from_world = kClipReadBack;      // (launch.hpp: the transform's wrapper runs k_clip_from_world alone)
+        awsm_launch_transform(c->scene_dev, &f, 0, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    b.clip_in_bin_last = false;      // the buffer now holds that frame's clip positions
+    return AWSM_OK;
+}
+
 // replay: the frame's geometry pass is enqueued again (a bin list that overflowed, world arrays that moved under the hud pass): the camera snapshot the first
 // enqueue took stays — pix2view / cam_pos were composed from that camera at awsm_hip_geometry_pass — and the geometry cache is not consulted.
 int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
@@ -460,7 +480,13 @@ int enqueue_geometry(AwsmHipCtx* c, bool replay = false) {
 #else
     const int knockout = 0;
 #endif
-    if (has_geometry && !(knockout & 1)) awsm_launch_transform(c->scene_dev, &f, world.n_blocks, c->stream);
+    // Clip positions formed in the binning (FrameDev::clip_from_world): a pass with a wcache and a snapshot that covers view_proj (bytes 128..191 of
+    // the camera block; in a replay the first enqueue's snapshot stays).  With a cache to consult and a block map the hit is decided once per draw.
+    f.clip_from_world = (c->clip_in_bin && f.wcache && FB(c).camera.ptr && c->bufs[AWSM_BUF_CAMERA].ptr && c->bufs[AWSM_BUF_CAMERA].size >= 192) ? 1u : 0u;
+    f.draw_hit_at = (f.clip_from_world && f.cache_on && f.block_draw && (size_t)FB(c).draw_hit_at + f.n_draws <= FB(c).block_map.size / 4) ? FB(c).draw_hit_at : 0u;
+    // ... and the fill pass of the binning reads the count pass's compact records, where the frame's tile coordinates fit them (bin_record.hpp)
+    f.bin_rec_at = (c->clip_in_bin && bin_rec_fits(f.tiles_x, f.tiles_y) && ((size_t)FB(c).bin_rec_at + f.total_tris) * 8 <= FB(c).tri_rec.size) ? FB(c).bin_rec_at : 0u;
+    if (has_geometry && !(knockout & 1)) { awsm_launch_transform(c->scene_dev, &f, world.n_blocks, c->stream); FB(c).clip_in_bin_last = f.clip_from_world != 0u; }
     if ((rc = record(c, EV_TRANSFORM))) return rc;
     ht.mark("geometry: transform launch");
     if (n_tiles && !(knockout & 2)) enqueue_binning(f, world.total_tris != 0, c->stream);
@@ -791,7 +817,9 @@ int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_c
         if ((rc = dev_reserve(c, b.draws_prev, nd * sizeof(DrawDev)))) return rc;
         if ((rc = dev_reserve(c, b.wcache, nv * 16))) return rc;
         const size_t blocks_bound = nv / 256 + nd + 1;
-        if ((rc = dev_reserve(c, b.block_map, blocks_bound * 4))) return rc;
+        // (behind the map, in its allocation: k_draw_decide's word per draw — FrameDev::draw_hit_at)
+        b.draw_hit_at = (c->clip_in_bin && blocks_bound + nd < (1ull << 30)) ? (uint32_t)blocks_bound : 0u;
+        if ((rc = dev_reserve(c, b.block_map, (blocks_bound + (b.draw_hit_at ? nd : 0)) * 4))) return rc;
         b.block_map_valid = false;
         if (b.cache_mark.size < blocks_bound * 4) { if ((rc = dev_realloc(c, b.cache_mark, (blocks_bound + blocks_bound / 2) * 4, true))) return rc; }
     }
@@ -808,7 +836,9 @@ int size_pass_buffers(AwsmHipCtx* c, FrameBufs& b, size_t tri_cap, size_t draw_c
     if (!forward && !shadow && (rc = dev_reserve(c, b.tri_shade, nt * 32))) return rc;
     if (!forward && !shadow && (rc = dev_reserve(c, b.draw_lean, nd * sizeof(LeanDrawDev)))) return rc;
     if ((rc = dev_reserve(c, b.big_list, nt * 4))) return rc;
-    if ((rc = dev_reserve(c, b.tri_rec, nt * kTriRecBytes))) return rc;
+    // (behind the set-up records, in their allocation: the world pass's compact bin records, 8 bytes per triangle — FrameDev::bin_rec_at, in records)
+    b.bin_rec_at = (world_pass && c->clip_in_bin && nt * (kTriRecBytes / 8) <= 0xFFFFFFFFull) ? (uint32_t)(nt * (kTriRecBytes / 8)) : 0u;
+    if ((rc = dev_reserve(c, b.tri_rec, nt * kTriRecBytes + (b.bin_rec_at ? nt * 8 : 0)))) return rc;
     const uint32_t tiles_x = (dm.w + kTile - 1) / kTile, tiles_y_full = (dm.h + kTile - 1) / kTile;
     const size_t n_tiles_full = (size_t)tiles_x * tiles_y_full;
     if ((rc = dev_reserve(c, b.tile_count, n_tiles_full * 4))) return rc;
@@ -864,7 +894,7 @@ int upload_draw_list(AwsmHipCtx* c, FrameBufs& b, const std::vector<DrawDev>& dr
         if (!keep_prev || !b.block_map.ptr) return AWSM_OK;
         std::vector<uint32_t> map;
         for (size_t i = 0; i < draws_host.size(); i++) map.insert(map.end(), (3ull * draws_host[i].tri_count + 255) / 256, (uint32_t)i);
-        if (map.size() * 4 > b.block_map.size || map.size() * 4 > (1u << 20)) return AWSM_OK;
+        if (map.size() * 4 > b.block_map.size || map.size() * 4 > (1u << 20) || (b.draw_hit_at && map.size() > b.draw_hit_at)) return AWSM_OK;
         const int rc = upload_small(c, b.block_map.ptr, map.data(), map.size() * 4);
         if (!rc) b.block_map_valid = true;
         return rc;
@@ -949,6 +979,7 @@ int awsm_hip_create(const AwsmConfig* cfg, AwsmHipCtx** out) {
     if (hipMalloc((void**)&c->scene_dev, sizeof(DevScene)) != hipSuccess) return bail(AWSM_ERR_OUT_OF_MEMORY);
     c->overlap = (cfg->flags & AWSM_CFG_OVERLAP_FRAMES) != 0;
     { const char* e = getenv("AWSM_GEOMETRY_CACHE"); c->geometry_cache = !(e && e[0] == '0'); }      // "0": k_deform_transform recomputes every draw every frame (A/B measurements, tests)
+    { const char* e = getenv("AWSM_CLIP_IN_BIN"); c->clip_in_bin = !(e && e[0] == '0'); }      // "0": k_deform_transform writes clip and decides cache hits per workgroup, k_bin reads clip (ctx.hpp)
     {   // k_shade_lean as a persistent grid of N workgroups per CU (it is VALU-bound from 4 waves/SIMD up): the rest of each CU's
         // wave slots, registers and LDS stays free for the next frame's geometry kernels on the other stream
         const char* e = getenv("AWSM_LEAN_WGS_PER_CU");
@@ -1721,8 +1752,9 @@ int awsm_hip_opaque_pass(AwsmHipCtx* c, const AwsmOpaqueParams* p) {
     if (!p->has_opaque && c->camera_written_since_snapshot && c->bufs[AWSM_BUF_CAMERA].ptr) {
         // the "empty" pipeline (skybox only) may run without a geometry pass of its own: it then has no snapshot of the camera it was given.  Rare
         // and cheap to make right: drain, copy, go on.
-        int rcs = sync_all(c);
+        int rcs = materialize_clip(c);      // (a geometry pass of this slot may have left its clip positions to this snapshot)
         if (rcs) return rcs;
+        if ((rcs = sync_all(c))) return rcs;
         compose_pixel_to_view(c, FB(c));
         HIPCHK(c, hipMemcpy(FB(c).camera.ptr, c->bufs[AWSM_BUF_CAMERA].ptr, std::min<size_t>(512, c->bufs[AWSM_BUF_CAMERA].size), hipMemcpyDeviceToDevice));
         c->camera_written_since_snapshot = false;
@@ -2439,6 +2471,7 @@ int awsm_hip_read_transformed_forward(AwsmHipCtx* c, float* clip_out, float* nt_
 int awsm_hip_read_transformed(AwsmHipCtx* c, float* clip_out, float* nt_out, uint32_t max_vertices) {
     if (!c) return AWSM_ERR_INVALID_ARGUMENT;
     if (!c->geometry_done) return fail(c, AWSM_ERR_NOT_READY, "read_transformed before geometry_pass");
+    if (clip_out) { HIPCHK(c, hipSetDevice(c->device)); const int rc = materialize_clip(c); if (rc) return rc; }      // (read_pass_vertices drains every stream before it copies)
     return read_pass_vertices(c, FB(c), std::min(max_vertices, 3u * c->lists[kPassWorld].total_tris), clip_out, nt_out, nullptr);
 }
 

@@ -79,6 +79,12 @@ struct FrameBufs {
     uint32_t cache_serial = 0;             // its frame serial
     PassKind kind = kPassWorld;            // which pass this is, and its frame slot (two bytes of the struct's tail padding: every other member keeps its offset)
     uint8_t slot = 0;
+    // Clip positions formed in the binning (FrameDev::clip_from_world; the world geometry pass only): where k_draw_decide's word per draw starts in
+    // block_map (words; 0: none) and the compact bin records in tri_rec (8-byte records; 0: none) — both share the older buffer's allocation, so that
+    // FrameDev names them with a 32-bit offset — and whether the slot's last world pass ran that way: its clip buffer then holds nothing of that
+    // frame, and awsm_hip_read_transformed forms it on demand.
+    uint32_t draw_hit_at = 0, bin_rec_at = 0;
+    bool clip_in_bin_last = false;
 };
 
 }  // namespace awsm
@@ -288,6 +294,10 @@ struct AwsmHipCtx {
         PassList lists[AWSM_SHADOW_MAX_VIEWS];
     } shadow_views[kSlots];
     DevBuf shadow_view_ctr[kSlots], shadow_view_layers[kSlots];
+
+    // AWSM_CLIP_IN_BIN=0 (read at awsm_hip_create): the world geometry pass keeps the earlier path — k_deform_transform writes clip, a cache hit too,
+    // every workgroup decides its draw's cache hit itself, k_bin reads clip (A/B measurements, tests)
+    bool clip_in_bin = true;
 };
 
 #define HIPCHK(c, call)                                                                            \

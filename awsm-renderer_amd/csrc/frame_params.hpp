@@ -143,6 +143,8 @@ constexpr uint32_t kMaxDirtyRanges = 12;
 // world pass's set are the picker's, 12 and 13 k_bin_scan's arrival counter and ready flag.
 enum CounterWord : uint32_t { kCtrBinned = 0, kCtrEntries, kCtrOverflow, kCtrCovered, kCtrBig, kCtrFragments, kCtrFragOverflow, kCtrExtraItems, kCtrWords };
 
+constexpr uint32_t kClipReadBack = 2u;           // FrameDev::clip_from_world
+
 struct FrameDev {
     uint32_t width, height;
     uint32_t y0, y1;              // rows the geometry pass rasterises: the shard's rows [sy0, sy1), plus one halo row on each side with MSAA
@@ -186,22 +188,35 @@ struct FrameDev {
     // tri_shade, tri_info — stays valid in the frame slot's arrays from one frame of the slot to the next as long as the draw sits at the same place of the
     // draw list (same DrawDev, index and first_tri included: prev_draws is the list those arrays were computed for) and none of its inputs was written since
     // (dirty: the byte ranges awsm_hip_buffer_write / buffer_create received since that frame, by buffer).  Such a draw's blocks only form
-    // clip = view_proj * wcache — the same operation on the same f32 values as the full path, so the same bits.  cache_on = 0: every block takes the full path.
+    // clip = view_proj * wcache — the same operation on the same f32 values as the full path, so the same bits — or, with clip_from_world, nothing at all.
+    // cache_on = 0: every block takes the full path.
     const uint32_t* block_draw;   // world geometry pass: the draw index of every k_deform_transform workgroup (null: the kernel searches the list)
     float4* wcache;               // total_verts  (world position as apply_vertex.wgsl forms it, model * (pos, 1)); geometry pass only, may be null
     const DrawDev* prev_draws;    // the draw list the slot's arrays were last computed for (== draws when the list did not change)
     uint32_t prev_n_draws;
     uint32_t cache_on;
     uint32_t cache_serial;        // frame serial of that computation: if its frame was dropped by a timed-out gate (poison) the arrays are older than prev_draws says
-    uint32_t* cache_mark;         // null, or one word per workgroup of the launch: a workgroup that takes the cached path stores frame_serial there (AwsmFrameStats.geometry_cache_blocks)
+    // Clip positions formed where they are consumed (a geometry pass with a wcache; AWSM_CLIP_IN_BIN=0 turns it off): k_deform_transform writes no clip —
+    // a cache hit writes nothing per vertex at all — and the set-up phase of k_bin<count> forms clip = view_proj * wcache itself (clip_from_world_pos,
+    // the full path's own last step on the same f32 values) with view_proj from `camera`, the snapshot the frame was submitted with.  0: k_deform_transform
+    // writes clip and k_bin reads it.  kClipReadBack: not a pass at all — awsm_launch_transform runs k_clip_from_world alone over total_verts (wcache, clip
+    // and camera set), for awsm_hip_read_transformed.  (This word, draw_hit_at and bin_rec_at sit where the struct had four bytes of padding each:
+    // every other member keeps its offset and the struct its size, so no kernel that does not read them changed.)
+    uint32_t clip_from_world;
+    uint32_t* cache_mark;        // null, or one word per workgroup of the launch: a workgroup that takes the cached path stores frame_serial there (AwsmFrameStats.geometry_cache_blocks)
     uint32_t n_dirty;             // ranges in dirty[] (<= kMaxDirtyRanges; more than that and the host turns the cache off for the frame)
     uint32_t dirty[12][3];        // {AwsmBuf, first byte, one past the last byte (saturating)}
-    TriRec* tri_rec;              // total_tris   (k_bin<count> -> k_bin<fill>, k_raster_tile, k_shade)
+    uint32_t draw_hit_at;         // 0, or: block_draw[draw_hit_at + i] = 1 when draw i keeps its cached outputs — decided once per draw by k_draw_decide, in front of
+                                  // k_deform_transform, whose workgroups then need two dependent loads (block_draw -> this word) instead of the walk through
+                                  // draws / prev_draws / geometry meta / dirty ranges; the words live behind the block map, in its allocation
+    TriRec* tri_rec;             // total_tris   (k_bin<count> -> k_bin<fill>, k_raster_tile, k_shade)
     uint32_t* tri_info;           // total_tris   (draw index in bits 0..23, AWSM_DRAW_* flags of the owning draw in bits 24..30, bit 31: ALPHA_MODE_MASK draw — transparent pass)
     uint4* tri_shade;             // 2 x total_tris (geometry pass only, may be null: {info word, 0, TEXCOORD_0 of corner 0} {TEXCOORD_0 of corner 1, of corner 2}: what
                                   //               compute.wgsl:182-197 + texture_uvs.wgsl:64-84 fetch per pixel through meta -> indices -> attribute data, once per
                                   //               triangle; k_deform_transform)
     uint32_t attr_data_bytes;     // size of the attribute data buffer (k_deform_transform reads the corners' TEXCOORD_0 from it, bounds-checked)
+    uint32_t bin_rec_at;          // 0, or: the pass's compact bin records (bin_record.hpp, 8 bytes per triangle: k_bin<count> -> k_bin<fill>) start at
+                                  // (uint2*)tri_rec + bin_rec_at — behind the set-up records, in their allocation
     LeanDrawDev* draw_lean;       // n_draws (k_resolve_draws); null = the lean route is off for this frame
     uint32_t* shade_todo;         // [0] = count, [4 ..] = (block id << 2 | wavefront) of the 16x4-pixel groups k_shade_lean left to the general kernel
     uint32_t shade_todo_cap;

@@ -13,6 +13,7 @@
 // image and the tile is written to HBM once, coalesced.
 #include "frame_params.hpp"
 #include "raster_setup.hpp"
+#include "bin_record.hpp"
 #include "launch.hpp"
 
 // The geometry chain's wavefronts take issue priority over the opaque pass's on a SIMD they share (s_setprio; round 5).  The overlapped frame is as long as
@@ -41,7 +42,8 @@ struct GeomMetaDev {
 };
 
 // Geometry cache: is draw `d` — at the same place of the list as `p`, the draw the slot's arrays were last computed for — also unchanged in everything
-// k_deform_transform reads for it except the camera?  Wave-uniform (one draw per workgroup): scalar loads and branches.  Conservative where a block's extent
+// k_deform_transform reads for it except the camera?  Asked once per draw by k_draw_decide (one thread per draw), or — a pass without a block map — once per
+// workgroup by k_deform_transform itself (wave-uniform there: scalar loads and branches).  Conservative where a block's extent
 // is not known here (a skin's joint count, a morph's value block): any write at or behind the block's first byte counts.  Buffers whose every write
 // invalidates every draw (attribute data / indices, morph values, skin index-weights) are the host's business: it turns the cache off for the frame.
 AWSM_DI bool draw_unchanged(const DevScene* __restrict__ sc, const FrameDev& f, const DrawDev& d, const DrawDev& p, const uint32_t* __restrict__ gmp) {
@@ -62,6 +64,35 @@ AWSM_DI bool draw_unchanged(const DevScene* __restrict__ sc, const FrameDev& f, 
     if (gmp[2] != 0u && hit(AWSM_BUF_MORPH_WEIGHTS, gmp[3], gmp[3] + 4u + 4u * gmp[2])) return false;
     if (gmp[5] != 0u && hit(AWSM_BUF_SKIN_MATRICES, gmp[6], 0xFFFFFFFFu)) return false;
     return true;
+}
+
+// apply_vertex.wgsl's last step, clip = view_proj * world, in ONE place: the full path of k_deform_transform, the set-up phase of k_bin<count>
+// (FrameDev::clip_from_world) and k_clip_from_world (the read-back) all form it here — one unit, one set of flags, -ffp-contract=off: sixteen
+// v_mul_f32 and twelve v_add_f32 in this order at every call site, no fused form.
+AWSM_DI f4 clip_from_world_pos(const m4& view_proj, float wx, float wy, float wz, float ww) { return mul(view_proj, {wx, wy, wz, ww}); }
+// view_proj of the camera block at `camera` (bytes 128..191).  Nothing writes the block while the kernel runs: constant address space, scalar loads.
+AWSM_DI m4 load_view_proj(const uint8_t* camera) {
+    const __attribute__((address_space(4))) float* p = (const __attribute__((address_space(4))) float*)(camera + 128);
+    m4 m;
+#pragma unroll
+    for (int i = 0; i < 4; i++) m.c[i] = {p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]};
+    return m;
+}
+
+// Geometry cache, the decision once per draw (one thread per draw) instead of once per workgroup: hit[i] = 1 when draw i keeps what the slot's arrays
+// hold.  Launched in front of k_deform_transform<false> when the pass has a block map; the workgroups then need block_draw -> hit[], two dependent
+// loads, instead of the walk through draws / prev_draws / geometry meta / dirty ranges that all workgroups of a draw repeated.
+__global__ __launch_bounds__(256) void k_draw_decide(const DevScene* __restrict__ sc, FrameDev f) {
+    if (frame_poisoned(f)) return;
+    uint32_t* const hit = const_cast<uint32_t*>(f.block_draw) + f.draw_hit_at;      // the words behind the block map (frame_params.hpp)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= f.n_draws) return;
+    bool same = false;
+    if (f.cache_on && i < f.prev_n_draws) {
+        const DrawDev d = f.draws[i];
+        same = draw_unchanged(sc, f, d, f.prev_draws[i], reinterpret_cast<const uint32_t*>(sc->buf[AWSM_BUF_GEOM_META] + d.geom_meta_off));
+    }
+    hit[i] = same ? 1u : 0u;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -102,21 +133,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FWD ? 4 : A
         uint32_t mid = (lo + hi) >> 1;
         if (f.draws[mid].first_block <= b) lo = mid; else hi = mid;
     }
+    const bool decided = !FWD && f.draw_hit_at != 0u && f.block_draw != nullptr;      // k_draw_decide ran in front of this kernel
+    if (decided && f.block_draw[f.draw_hit_at + lo] != 0u) {      // (workgroup-uniform) k_draw_decide found the draw unchanged: nothing to do per vertex
+        if (f.cache_mark && tid == 0u) f.cache_mark[blockIdx.x] = f.frame_serial;
+        return;
+    }
     const DrawDev d = f.draws[lo];
     const uint32_t nverts = 3u * d.tri_count;
     const uint32_t local0 = (b - d.first_block) * 256u;
     const uint32_t count = min(256u, nverts - local0);
 
     const uint32_t* gmp = reinterpret_cast<const uint32_t*>(sc->buf[AWSM_BUF_GEOM_META] + d.geom_meta_off);
-    if (!FWD && f.cache_on && lo < f.prev_n_draws && draw_unchanged(sc, f, d, f.prev_draws[lo], gmp)) {
+    // (with the per-draw words every draw was decided above: a draw that comes here changed)
+    if (!FWD && !decided && f.cache_on && lo < f.prev_n_draws && draw_unchanged(sc, f, d, f.prev_draws[lo], gmp)) {
         // Geometry cache hit (frame_params.hpp): the draw's world positions, normals, tangents and per-triangle words in this slot's arrays are still what the
-        // full path below would write — only the camera moved.  clip = view_proj * world, the full path's own last step on the same f32 values.
+        // full path below would write — only the camera moved.  clip = view_proj * world, the full path's own last step on the same f32 values — formed
+        // here, or by the binning's set-up phase from the same wcache (clip_from_world).
         if (f.cache_mark && tid == 0u) f.cache_mark[blockIdx.x] = f.frame_serial;
-        if (tid < count) {
+        if (!f.clip_from_world && tid < count) {
             const size_t gv = (size_t)3u * d.first_tri + local0 + tid;
             const float4 w = f.wcache[gv];
             const m4 view_proj = load_m4(reinterpret_cast<const float*>(sc->buf[AWSM_BUF_CAMERA] + 128));
-            const f4 clip = mul(view_proj, {w.x, w.y, w.z, w.w});
+            const f4 clip = clip_from_world_pos(view_proj, w.x, w.y, w.z, w.w);
             f.clip[gv] = make_float4(clip.x, clip.y, clip.z, clip.w);
         }
         return;
@@ -214,7 +252,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FWD ? 4 : A
     }
     const m4 view_proj = load_m4(reinterpret_cast<const float*>(sc->buf[AWSM_BUF_CAMERA] + 128));
     const f4 world_pos = mul(model, {pos.x, pos.y, pos.z, 1.0f});
-    const f4 clip = mul(view_proj, world_pos);
+    const f4 clip = clip_from_world_pos(view_proj, world_pos.x, world_pos.y, world_pos.z, world_pos.w);
 
     const m3 mm = upper3(model);
     const f3 c0 = mm.c[0], c1 = mm.c[1], c2 = mm.c[2];
@@ -238,7 +276,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FWD ? 4 : A
 
     const uint32_t lv = local0 + tid;
     const size_t gv = (size_t)3u * d.first_tri + lv;
-    f.clip[gv] = make_float4(clip.x, clip.y, clip.z, clip.w);
+    if (FWD || !f.clip_from_world) f.clip[gv] = make_float4(clip.x, clip.y, clip.z, clip.w);
     if (!FWD && f.wcache) f.wcache[gv] = make_float4(world_pos.x, world_pos.y, world_pos.z, world_pos.w);
     f.nrm[gv] = make_float4(world_normal.x, world_normal.y, world_normal.z, 0.0f);
     f.tan[gv] = make_float4(tangent_ortho.x, tangent_ortho.y, tangent_ortho.z, tangent.w);
@@ -307,7 +345,13 @@ AWSM_DI void bin_tri_load(const FrameDev& f, uint32_t r, BinTri& b) {
     b.ok = false;
     if (r < f.total_tris) {
         if (SETUP) {   // the first phase of the counting pass does the setup once and leaves it for everyone downstream
-            const float4 v0 = f.clip[(size_t)r * 3], v1 = f.clip[(size_t)r * 3 + 1], v2 = f.clip[(size_t)r * 3 + 2];
+            float4 v0, v1, v2;
+            if (f.clip_from_world) {      // (uniform) nobody wrote clip: the three world positions and the frame's camera give it — the same operation on the same values
+                const float4 w0 = f.wcache[(size_t)r * 3], w1 = f.wcache[(size_t)r * 3 + 1], w2 = f.wcache[(size_t)r * 3 + 2];
+                const m4 view_proj = load_view_proj(f.camera);
+                const f4 c0 = clip_from_world_pos(view_proj, w0.x, w0.y, w0.z, w0.w), c1 = clip_from_world_pos(view_proj, w1.x, w1.y, w1.z, w1.w), c2 = clip_from_world_pos(view_proj, w2.x, w2.y, w2.z, w2.w);
+                v0 = make_float4(c0.x, c0.y, c0.z, c0.w); v1 = make_float4(c1.x, c1.y, c1.z, c1.w); v2 = make_float4(c2.x, c2.y, c2.z, c2.w);
+            } else { v0 = f.clip[(size_t)r * 3]; v1 = f.clip[(size_t)r * 3 + 1]; v2 = f.clip[(size_t)r * 3 + 2]; }
             // A shard (bands or a row strip) sees most triangles of the frame only to drop them: decide that from a conservative
             // row range (+-1 pixel around the unsnapped vertices; any w <= 0 or non-finite value keeps the triangle) before the setup,
             // and leave just the "no fragment" marker.  The exact rows of a kept triangle come from tri_setup as before.
@@ -346,7 +390,7 @@ AWSM_DI void bin_tri_load(const FrameDev& f, uint32_t r, BinTri& b) {
     }
     b.wdt = b.tx1 - b.tx0 + 1;
     b.ntiles = b.ok ? b.wdt * (b.ty1 - b.ty0 + 1) : 0;
-    b.big = b.ntiles > 16;
+    b.big = b.ntiles > (int)kBinRecTiles;      // (16: what the compact record's mask holds, bin_record.hpp)
     b.small = b.ok && !b.big;
 }
 AWSM_DI bool bin_tile_hit(const FrameDev& f, const TriSetup& t, int ntiles, int tx, int l) {
@@ -379,8 +423,22 @@ AWSM_DI void bin_big_walk(const FrameDev& f, uint32_t block, uint32_t n_blocks) 
 }
 constexpr uint32_t kBinBigBlocks = 64;        // fill pass: the first workgroups of k_bin<true> walk the big triangles (no launch of their own)
 
-template <bool FILL>
+// The fill pass's view of a small triangle from the count pass's compact record (bin_record.hpp): its tile window, and which tiles of it took it.
+AWSM_DI uint32_t bin_rec_read(const uint2* bin_rec, const FrameDev& f, uint32_t r, BinTri& b) {
+    BinRec q = bin_rec_unpack({0u, 0u});
+    if (r < f.total_tris) { const uint2 w = bin_rec[r]; q = bin_rec_unpack({w.x, w.y}); }
+    b.ok = q.ok; b.big = q.ok && q.big; b.small = q.ok && !q.big;
+    b.tx0 = (int)q.tx0; b.tx1 = (int)(q.tx0 + q.wm1); b.ty0 = (int)q.ty0; b.ty1 = (int)(q.ty0 + q.hm1);
+    b.wdt = (int)q.wm1 + 1; b.ntiles = 0;
+    return q.mask;
+}
+
+// REC (the world pass with a record array, bin_rec): the count pass leaves per triangle which tiles of its window took it, the fill pass takes window and
+// tiles from that record for the small triangles — no set-up record, no tile test; the big ones keep the full records (bin_big_walk).  !REC: both
+// passes as they were, bin_rec is not read.
+template <bool FILL, bool REC>
 __global__ __launch_bounds__(256) void k_bin(FrameDev f) {
+    uint2* const bin_rec = reinterpret_cast<uint2*>(f.tri_rec) + f.bin_rec_at;      // REC: behind the set-up records, in their allocation (frame_params.hpp)
 #if AWSM_GEOM_PRIO
     __builtin_amdgcn_s_setprio(AWSM_GEOM_PRIO);
 #endif
@@ -401,10 +459,12 @@ __global__ __launch_bounds__(256) void k_bin(FrameDev f) {
     // ---- phase 0: setup (count pass) / load, window of the small triangles, big triangles walked by the wavefront ----
     uint32_t my_ok = 0;
     BinTri keep;                                  // kBinBatches == 1: the triangle stays in registers for the later phases
+    uint32_t rec_mask = 0u;                       // REC: bit per tile of the triangle's window, row by row (count pass: gathered in phase A; fill pass: loaded)
     for (uint32_t j = 0; j < kBinBatches; j++) {
         const uint32_t r = r0 + j * 256u;
         BinTri& b = keep;
-        bin_tri_load<!FILL>(f, r, b);
+        if (FILL && REC) rec_mask = bin_rec_read(bin_rec, f, r, b);
+        else bin_tri_load<!FILL>(f, r, b);
         AWSM_STAMP_AT(f, FILL ? 2 : 0, 7);
         my_ok += b.ok ? 1u : 0u;
         {   // tile window of the workgroup's small triangles: reduced inside the wavefront first — 256 threads updating the same four LDS
@@ -452,13 +512,23 @@ __global__ __launch_bounds__(256) void k_bin(FrameDev f) {
         BinTri reload;
         if (kBinBatches > 1) bin_tri_load<false>(f, r, reload);
         const BinTri& b = kBinBatches > 1 ? reload : keep;
-        if (b.small)
+        if (b.small) {
+            uint32_t bit = 1u;      // (REC) the tile's bit: this loop order is the record's
             for (int l = b.ty0; l <= b.ty1; l++)
-                for (int tx = b.tx0; tx <= b.tx1; tx++)
-                    if (bin_tile_hit(f, b.t, b.ntiles, tx, l)) {
+                for (int tx = b.tx0; tx <= b.tx1; tx++, bit <<= 1)
+                    if ((FILL && REC) ? (rec_mask & bit) != 0u : bin_tile_hit(f, b.t, b.ntiles, tx, l)) {
+                        if (!FILL && REC) rec_mask |= bit;
                         if (use_lds) atomicAdd(&lcount[(l - wy0) * ww + (tx - wx0)], 1u);
                         else bin_emit<FILL>(f, tx, l, r);
                     }
+        }
+        if (!FILL && REC && r < f.total_tris) {
+            BinRec q;
+            q.ok = b.ok; q.big = b.big; q.tx0 = (uint32_t)b.tx0; q.ty0 = (uint32_t)b.ty0; q.wm1 = (uint32_t)(b.tx1 - b.tx0); q.hm1 = (uint32_t)(b.ty1 - b.ty0); q.mask = rec_mask;
+            if (!b.small) { q.tx0 = 0u; q.ty0 = 0u; q.wm1 = 0u; q.hm1 = 0u; }
+            const BinRecWords w = bin_rec_pack(q);
+            bin_rec[r] = make_uint2(w.w0, w.w1);
+        }
     }
     if (!use_lds) return;
     __syncthreads();
@@ -482,14 +552,16 @@ __global__ __launch_bounds__(256) void k_bin(FrameDev f) {
         BinTri reload;
         if (kBinBatches > 1) bin_tri_load<false>(f, r, reload);
         const BinTri& b = kBinBatches > 1 ? reload : keep;
-        if (b.small)
+        if (b.small) {
+            uint32_t bit = 1u;
             for (int l = b.ty0; l <= b.ty1; l++)
-                for (int tx = b.tx0; tx <= b.tx1; tx++)
-                    if (bin_tile_hit(f, b.t, b.ntiles, tx, l)) {
+                for (int tx = b.tx0; tx <= b.tx1; tx++, bit <<= 1)
+                    if ((FILL && REC) ? (rec_mask & bit) != 0u : bin_tile_hit(f, b.t, b.ntiles, tx, l)) {
                         const uint32_t li = (uint32_t)((l - wy0) * ww + (tx - wx0));
                         const uint32_t pos = lbase[li] + atomicAdd(&lcount[li], 1u);
                         if (pos < f.bin_capacity) f.bin_list[pos] = r;
                     }
+        }
     }
     AWSM_STAMP_AT(f, 2, 6);
 }
@@ -1088,6 +1160,16 @@ __global__ __launch_bounds__(256) void k_hud_merge(const unsigned long long* __r
     out[i] = h == ~0ull ? w : ((depth << 32) | (h & 0xFFFFFFFFull));
 }
 
+// awsm_hip_read_transformed after a pass that ran with clip_from_world: the clip positions nobody stored, formed on demand from the slot's wcache
+// and the camera snapshot of the frame that was rendered (f.camera), into the slot's clip buffer.
+__global__ __launch_bounds__(256) void k_clip_from_world(FrameDev f, uint32_t n_verts) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_verts) return;
+    const float4 w = f.wcache[i];
+    const f4 clip = clip_from_world_pos(load_view_proj(f.camera), w.x, w.y, w.z, w.w);
+    f.clip[i] = make_float4(clip.x, clip.y, clip.z, clip.w);
+}
+
 // Small host->device uploads (dirty ranges of the scene mirrors, the draw list) read the pinned staging ring directly
 // from a kernel: the copy stays in the compute queue, where an SDMA copy would stall the in-order stream on a
 // cross-engine signal for longer than the whole transform kernel runs.
@@ -1149,15 +1231,26 @@ extern "C" void awsm_launch_handoff_wait(const uint32_t* flag, uint32_t serial, 
 extern "C" void awsm_launch_hud_merge(const unsigned long long* world, const unsigned long long* hud, unsigned long long* out, size_t first, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(awsm::k_hud_merge, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, s, world, hud, out, first, n);
 }
+// FrameDev::clip_from_world == kClipReadBack: not a pass — k_clip_from_world over the frame's total_verts (awsm_hip_read_transformed).
+// FrameDev::draw_hit_at != 0 (with a block map): k_draw_decide goes in front of the transform and decides the geometry cache once per draw.
 extern "C" void awsm_launch_transform(const awsm::DevScene* sc, const awsm::FrameDev* f, uint32_t n_blocks, hipStream_t s) {
-    if (n_blocks) hipLaunchKernelGGL(awsm::k_deform_transform<false>, dim3(n_blocks), dim3(256), 0, s, sc, *f);
+    if (f->clip_from_world == awsm::kClipReadBack) {
+        if (f->total_verts) hipLaunchKernelGGL(awsm::k_clip_from_world, dim3((f->total_verts + 255u) / 256u), dim3(256), 0, s, *f, f->total_verts);
+        return;
+    }
+    if (!n_blocks) return;
+    if (f->draw_hit_at && f->block_draw && f->n_draws) hipLaunchKernelGGL(awsm::k_draw_decide, dim3((f->n_draws + 255u) / 256u), dim3(256), 0, s, sc, *f);
+    hipLaunchKernelGGL(awsm::k_deform_transform<false>, dim3(n_blocks), dim3(256), 0, s, sc, *f);
 }
 extern "C" void awsm_launch_transform_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, uint32_t n_blocks, hipStream_t s) {
     if (n_blocks) hipLaunchKernelGGL(awsm::k_deform_transform<true>, dim3(n_blocks), dim3(256), 0, s, sc, *f);
 }
+// FrameDev::bin_rec_at != 0 (count and fill alike): the pass has compact records (bin_record.hpp) — then the frame must fit them (bin_rec_fits: the caller's check)
 extern "C" void awsm_launch_bin_count(const awsm::FrameDev* f, hipStream_t s) {
     const uint32_t per = 256u * awsm::kBinBatches, nb = (f->total_tris - f->rank0 + per - 1u) / per;
-    if (nb) hipLaunchKernelGGL(awsm::k_bin<false>, dim3(nb), dim3(256), 0, s, *f);
+    if (!nb) return;
+    if (f->bin_rec_at) hipLaunchKernelGGL((awsm::k_bin<false, true>), dim3(nb), dim3(256), 0, s, *f);
+    else hipLaunchKernelGGL((awsm::k_bin<false, false>), dim3(nb), dim3(256), 0, s, *f);
 }
 extern "C" void awsm_launch_bin_big(const awsm::FrameDev* f, int fill, hipStream_t s) {
     if (f->total_tris <= f->rank0) return;
@@ -1180,7 +1273,9 @@ extern "C" void awsm_launch_bin_scan(const awsm::FrameDev* f, hipStream_t s) {
 }
 extern "C" void awsm_launch_bin_fill(const awsm::FrameDev* f, hipStream_t s) {
     const uint32_t per = 256u * awsm::kBinBatches, nb = (f->total_tris - f->rank0 + per - 1u) / per;
-    if (nb) hipLaunchKernelGGL(awsm::k_bin<true>, dim3(nb + awsm::kBinBigBlocks), dim3(256), 0, s, *f);
+    if (!nb) return;
+    if (f->bin_rec_at) hipLaunchKernelGGL((awsm::k_bin<true, true>), dim3(nb + awsm::kBinBigBlocks), dim3(256), 0, s, *f);
+    else hipLaunchKernelGGL((awsm::k_bin<true, false>), dim3(nb + awsm::kBinBigBlocks), dim3(256), 0, s, *f);
 }
 extern "C" void awsm_launch_raster(const awsm::FrameDev* f, hipStream_t s) {
     const uint32_t n_tiles = f->tiles_x * f->tiles_y;

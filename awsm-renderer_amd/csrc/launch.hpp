@@ -18,8 +18,11 @@ void awsm_launch_handoff_signal(uint32_t* flag, uint32_t serial, unsigned long l
 void awsm_launch_handoff_wait(const uint32_t* flag, uint32_t serial, unsigned long long budget_ticks, uint32_t* timeouts_host, uint32_t timeouts_known,
                               uint32_t* poison, uint32_t poison_serial, hipStream_t s);
 void awsm_launch_hud_merge(const unsigned long long* world, const unsigned long long* hud, unsigned long long* out, size_t first, size_t n, hipStream_t s);
+// (FrameDev::draw_hit_at: k_draw_decide goes in front; FrameDev::clip_from_world == kClipReadBack: the read-back kernel alone — no new wrapper for
+// either, the set of wrappers is what the host layer's stand-ins know)
 void awsm_launch_transform(const awsm::DevScene* sc, const awsm::FrameDev* f, uint32_t n_blocks, hipStream_t s);
 void awsm_launch_transform_forward(const awsm::DevScene* sc, const awsm::FrameDev* f, uint32_t n_blocks, hipStream_t s);
+// (FrameDev::bin_rec_at: the count pass writes compact records, bin_record.hpp, the fill pass reads them instead of the set-up records)
 void awsm_launch_bin_count(const awsm::FrameDev* f, hipStream_t s);
 void awsm_launch_bin_big(const awsm::FrameDev* f, int fill, hipStream_t s);
 void awsm_launch_bin_scan(const awsm::FrameDev* f, hipStream_t s);
