@@ -31,6 +31,13 @@
 #ifndef AWSM_LEAN_WAVES
 #define AWSM_LEAN_WAVES 6
 #endif
+// 1: lean_core issues the BRDF table's four loads right behind the surface terms and consumes them behind the first kLeanDeferredLights lights'
+//    arithmetic (lean::brdf_lut_issue / brdf_lut_finish / light_term / add_term).
+// 0: the text, and with it the instruction stream, from before that: the table looked up and consumed inside the IBL block, the lights added one by
+//    one (lean::brdf_lut, lean::direct).  For A/B builds (tools/build_variants.sh NAME "-DAWSM_LEAN_LUT_LATE=0").
+#ifndef AWSM_LEAN_LUT_LATE
+#define AWSM_LEAN_LUT_LATE 1
+#endif
 
 namespace awsm {
 
@@ -1367,6 +1374,120 @@ AWSM_DI void direct(const Lit& s, f3 l, f3 radiance, f3& color) {
 }
 }  // namespace lean
 
+#if AWSM_LEAN_LUT_LATE
+// ---- The BRDF table's round trip behind the lights.  brdf_lut above in two halves — brdf_lut_issue forms the footprint and
+// issues the four loads, brdf_lut_finish converts and blends — and the light body of lean_core's loop with direct above as a function that hands the
+// light's term back instead of adding it, so that lean_core can evaluate lights while the table's texels are on their way and add afterwards.
+// The code above is RELAXED: for a * b + c * d the compiler picks the product it fuses, and it picks again when the code around the sum changes.  These
+// restatements must give the bits the loop gave, so they are compiled with contraction OFF and every fused multiply-add the loop's instructions had is
+// written out (read from k_shade_lean<false,0,false>'s assembly of the commit before; profiles/lut_late_isa.txt): nothing is left to choose.
+// The price: this route's light body, table lookup and IBL sum exist twice while the knob lives — an edit to the math goes into both copies — and
+// this copy records one toolchain's choices (bench.py's dumps equal the earlier order's word for word: profiles/lut_late_identity.txt).
+#pragma clang fp contract(off)
+namespace lean {
+constexpr uint32_t kLeanDeferredLights = 2u;      // six registers a light; three lights cost k_shade_lean<false,0,.> its seventh wavefront (73 / 74 VGPRs)
+AWSM_DI float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+AWSM_DI float dot_yxz(f3 a, f3 b) { return fma_(a.z, b.z, fma_(a.x, b.x, a.y * b.y)); }      // fm::fdot as the loop folded it: y's product rounded, x and z fused
+// n.v as every instantiation formed it: the x product is shared with reflect's dot, y fused onto it, and the z product rounded on its own and ADDED
+AWSM_DI float dot_nv(f3 n, f3 v) { return n.z * v.z + fma_(v.y, n.y, v.x * n.x); }
+// reflect3(-v, n) likewise: dot(n, -v) as a chain on the negated x product, then -v - n (2 d) with the product rounded first
+AWSM_DI f3 reflect_view(f3 v, f3 n) {
+    const float d = fma_(-v.z, n.z, fma_(n.y, -v.y, -(v.x * n.x))), d2 = d + d;
+    return {-v.x - n.x * d2, -v.y - n.y * d2, -v.z - n.z * d2};
+}
+struct LutTap { uint32_t t00, t10, t01, t11; float fx, fy; };
+AWSM_DI void brdf_lut_issue(const uint16_t* lut, uint32_t lut_w, uint32_t lut_h, float n_dot_v, float roughness, LutTap& t) {
+    const float u = saturate(n_dot_v), v = saturate(roughness);
+    const int W = (int)lut_w, H = (int)lut_h;
+    const float x = fma_(u, (float)W, -0.5f), y = fma_(v, (float)H, -0.5f);          // in [-0.5, extent - 0.5]: no range guard needed
+    const float flx = floorf(x), fly = floorf(y);
+    t.fx = x - flx; t.fy = y - fly;
+    const int xi = (int)flx, yi = (int)fly;
+    const int i0 = max(xi, 0), i1 = min(xi + 1, W - 1), j0 = max(yi, 0), j1 = min(yi + 1, H - 1);
+    const uint32_t r0 = (uint32_t)(j0 * W) << 2, r1 = (uint32_t)(j1 * W) << 2;
+    t.t00 = gload<uint32_t>(lut, r0 + ((uint32_t)i0 << 2)); t.t10 = gload<uint32_t>(lut, r0 + ((uint32_t)i1 << 2));
+    t.t01 = gload<uint32_t>(lut, r1 + ((uint32_t)i0 << 2)); t.t11 = gload<uint32_t>(lut, r1 + ((uint32_t)i1 << 2));
+    // A comment that takes the two fractions as operands: they exist from here on.  Left alone the compiler moves the two subtractions down to
+    // brdf_lut_finish and keeps x, floor x, y, floor y across everything in between — four registers for what fits in two, and with them
+    // k_shade_lean<false,0,.> needs 73 / 74 registers instead of 71 / 72: the seventh wavefront hangs on this line.
+    asm volatile("; MARK lut_issued" : "+v"(t.fx), "+v"(t.fy));
+}
+AWSM_DI float lut_blend(float g, float left, float f, float right) { return fma_(g, left, f * right); }      // the left / top texel's product fused
+AWSM_DI f2 brdf_lut_finish(const LutTap& t) {
+    const float fx = t.fx, fy = t.fy, gx = 1.0f - fx, gy = 1.0f - fy;
+    const float r_top = lut_blend(gx, f16_bits_to_f32((unsigned short)(t.t00 & 0xFFFFu)), fx, f16_bits_to_f32((unsigned short)(t.t10 & 0xFFFFu)));
+    const float r_bot = lut_blend(gx, f16_bits_to_f32((unsigned short)(t.t01 & 0xFFFFu)), fx, f16_bits_to_f32((unsigned short)(t.t11 & 0xFFFFu)));
+    const float g_top = lut_blend(gx, f16_bits_to_f32((unsigned short)(t.t00 >> 16)), fx, f16_bits_to_f32((unsigned short)(t.t10 >> 16)));
+    const float g_bot = lut_blend(gx, f16_bits_to_f32((unsigned short)(t.t01 >> 16)), fx, f16_bits_to_f32((unsigned short)(t.t11 >> 16)));
+    return {lut_blend(gy, r_top, fy, r_bot), lut_blend(gy, g_top, fy, g_bot)};
+}
+// A light's term as its two factors, bd k_d + F spec and radiance n.l occlusion: the colour takes it with ONE fused multiply-add per channel (add_term),
+// so the product must not be rounded on its own.
+struct LightTerm { f3 brdf, light; };
+AWSM_DI void add_term(f3& color, const LightTerm& t) {
+    color = {fma_(t.light.x, t.brdf.x, color.x), fma_(t.light.y, t.brdf.y, color.y), fma_(t.light.z, t.brdf.z, color.z)};
+}
+// the end of brdf_ibl, the part that reads the table: (base_contribution + specular) + emissive with no product fused, as the loop's kernel had it
+AWSM_DI f3 ibl_color(f3 F0, float f90, f2 lut, f3 prefiltered, float occlusion, f3 base_contribution, f3 emissive) {
+    const float g = f90 * lut.y, m = 0.5f + 0.5f * occlusion;      // mixf(1, occlusion, 0.5)
+    const f3 spec_term = {F0.x * lut.x + g, F0.y * lut.x + g, F0.z * lut.x + g};
+    const f3 specular = {m * (prefiltered.x * spec_term.x), m * (prefiltered.y * spec_term.y), m * (prefiltered.z * spec_term.z)};
+    return {(base_contribution.x + specular.x) + emissive.x, (base_contribution.y + specular.y) + emissive.y, (base_contribution.z + specular.z) + emissive.z};
+}
+// Light i of lean_core's loop, direct included.  false (wave-uniform): the whole wavefront skips the light (AWSM_NO_LIGHT_SKIP: never) and `t` is
+// untouched — the caller adds nothing, not a zero, so a -0 channel keeps its sign.
+AWSM_DI bool light_term(const Lit& s, const void* lights_pre, const void* lights, f3 world_position, uint32_t i, LightTerm& t) {
+    const f32x4 pre0 = cload<f32x4>(lights_pre, i * 32u), pre1 = cload<f32x4>(lights_pre, i * 32u + 16u);
+    const uint32_t kind = (uint32_t)pre0.w;
+    f3 l = {pre0.x, pre0.y, pre0.z}, radiance = {pre1.x, pre1.y, pre1.z};
+    if (kind == 2u || kind == 3u) {
+        const f32x4 pos_range = cload<f32x4>(lights, i * 64u);
+        const f3 stl = mk3(pos_range.x, pos_range.y, pos_range.z) - world_position;
+        const float d2 = dot_yxz(stl, stl);
+        const float inv_d = d2 > 0.0f ? fm::rsq(d2) : 0.0f;
+        const float dist = d2 * inv_d, dist2 = dist * dist;
+        float att;   // math.wgsl:12-19 inverse_square
+        if (pos_range.w == 0.0f) att = fm::rcp(fmaxf(dist2, 0.01f));
+        else { const float fo = fma_(-fm::rcp(pos_range.w * pos_range.w), dist2, 1.0f); att = fm::rcp(dist2 + 1.0f) * saturate(fo * fo); }
+        const f3 to_light = stl * inv_d;
+        if (kind == 3u) {
+            const f32x4 dir_inner = cload<f32x4>(lights, i * 64u + 16u), kind_outer = cload<f32x4>(lights, i * 64u + 48u);
+            const float cos_l = fma_(-l.z, to_light.z, fma_(to_light.y, -l.y, -(l.x * to_light.x)));
+            const float sm = saturate((cos_l - kind_outer.y) * fm::rcp(dir_inner.w - kind_outer.y));
+            att = att * (sm * sm);
+        }
+        l = to_light;
+        radiance = {radiance.x * att, radiance.y * att, radiance.z * att};
+#ifndef AWSM_NO_LIGHT_SKIP
+        if (__builtin_amdgcn_ballot_w64(!(att == 0.0f)) == 0ull) return false;      // out of the light's range (or cone) for the whole wavefront
+#endif
+    } else if (kind != 1u) { l = {0.0f, 0.0f, 0.0f}; radiance = {0.0f, 0.0f, 0.0f}; }
+    const float ndl = saturate(dot_yxz(s.n, l));
+#ifndef AWSM_NO_LIGHT_SKIP
+    if (__builtin_amdgcn_ballot_w64(ndl > 0.0f) == 0ull) return false;              // behind the surface for the whole wavefront (direct above)
+#endif
+    const f3 sum = {s.v.x + l.x, s.v.y + l.y, s.v.z + l.z};
+    const float len_sq = dot_yxz(sum, sum);
+    const bool has_half = len_sq > 1e-8f;
+    const float inv_len = has_half ? fm::rsq(len_sq) : 0.0f;
+    const float ndh = saturate(dot_yxz(s.n, sum) * inv_len);
+    const float vdh = dot_yxz(s.v, sum) * inv_len;
+    const float p = saturate(1.0f - (has_half ? vdh : s.ndv_dir));
+    const float p2 = p * p, p5 = (p2 * p2) * p;
+    const f3 F = {fma_(s.df90.x, p5, s.F0.x), fma_(s.df90.y, p5, s.F0.y), fma_(s.df90.z, p5, s.F0.z)};
+    const float dd = fma_(s.a2m1, ndh * ndh, 1.0f);
+    const float den = (fma_(dd, kPi * dd, kEps) * fma_(s.one_m_gk, ndl, s.gk)) * fmaxf(s.ndv4 * ndl, kEps);
+    const float spec = has_half ? (s.a2_g1v * ndl) * fm::rcp(den) : 0.0f;
+    const float k_d = 1.0f - fma_(s.df90max, p5, s.F0max);
+    const float w = ndl * s.occlusion;
+    t.brdf = {fma_(s.bd.x, k_d, F.x * spec), fma_(s.bd.y, k_d, F.y * spec), fma_(s.bd.z, k_d, F.z * spec)};
+    t.light = {radiance.x * w, radiance.y * w, radiance.z * w};
+    return true;
+}
+}  // namespace lean
+#pragma clang fp contract(fast)
+#endif
+
 // Per-wavefront LDS staging of the per-triangle records (level 1 of the chain).  A 16x4 strip holds a handful of distinct triangles, and the
 // 208 bytes that belong to one — setup record 80, three vertex normals 48, three tangents 48, {info word, three TEXCOORD_0} 32 — used to be
 // loaded by every lane that shows it (13 vector loads of 16 bytes per lane: 60 % of what a pixel pulled through its CU's L1 / TA path).  Now the
@@ -2035,8 +2156,16 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     sf.metallic = clampf(metallic_in, 0.0f, 1.0f);
     sf.roughness = fmaxf(clampf(roughness_in, 0.0f, 1.0f), 0.04f);
     sf.alpha = sf.roughness * sf.roughness;
+#if AWSM_LEAN_LUT_LATE
+    const float ndv = lean::dot_nv(sf.n, sf.v);
+#else
     const float ndv = fm::fdot(sf.n, sf.v);
+#endif
     sf.n_dot_v_ibl = saturate(ndv);
+#if AWSM_LEAN_LUT_LATE
+    lean::LutTap lut_tap;      // the table's four texels are on their way from here; their first use sits behind the deferred lights
+    lean::brdf_lut_issue(sc->lut_rg16f, sc->lut_w, sc->lut_h, sf.n_dot_v_ibl, sf.roughness, lut_tap);
+#endif
     sf.n_dot_v_dir = fmaxf(ndv, 1e-4f);
     const float f0b = ior_to_f0(1.5f);
     sf.F0 = mix3(splat3(fminf(f0b, 1.0f)), base, sf.metallic);
@@ -2057,6 +2186,38 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     lit.occlusion = occlusion;
     f3 color;
     asm volatile("; MARK ibl");
+#if AWSM_LEAN_LUT_LATE
+    // brdf_ibl up to the table; then the first kLeanDeferredLights lights, evaluated while the table's texels are in flight (a term reads neither the
+    // table nor `color`: a hundred or two instructions to issue instead of a wait).  The window is unrolled, so the terms sit in registers (static
+    // indices, scalar branches on i < n_lights), `live` (scalar) remembers which lights the wavefront did not skip, and the colour is then formed in
+    // the order it always had: the IBL colour, light 0, light 1 — nothing for a skipped light — and the lights from the window on through the loop.
+    const f3 prefiltered = lean::prefiltered(sc, lean::reflect_view(sf.v, sf.n), sf.roughness);
+    f3 base_contribution;
+    {
+        const f3 irradiance = lean::irradiance(sc, sf.n);
+        const f3 F_view = fresnel_schlick_f90(sf.n_dot_v_ibl, sf.F0, sf.f90);
+        const float F_view_max = fmaxf(fmaxf(F_view.x, F_view.y), F_view.z);
+        const f3 base_layer = (base * (1.0f / kPi)) * irradiance;
+        const float k_d = (1.0f - F_view_max) * (1.0f - sf.metallic);
+        base_contribution = (base_layer * k_d) * occlusion;
+    }
+    asm volatile("; MARK lights");
+    const uint32_t n_lights = min(cload<uint32_t>(sc->buf[AWSM_BUF_LIGHTS_INFO], 0u), f.lights_cap);
+    const void* lights = sc->buf[AWSM_BUF_LIGHTS];
+    lean::LightTerm term[lean::kLeanDeferredLights];      // (read only under `live`)
+    uint32_t live = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < lean::kLeanDeferredLights; i++)
+        if (i < n_lights && lean::light_term(lit, f.lights_pre, lights, world_position, i, term[i])) live |= 1u << i;
+    color = lean::ibl_color(sf.F0, sf.f90, lean::brdf_lut_finish(lut_tap), prefiltered, occlusion, base_contribution, emissive);
+#pragma unroll
+    for (uint32_t i = 0; i < lean::kLeanDeferredLights; i++)
+        if (live & (1u << i)) lean::add_term(color, term[i]);
+    for (uint32_t i = lean::kLeanDeferredLights; i < n_lights; i++) {
+        lean::LightTerm t;
+        if (lean::light_term(lit, f.lights_pre, lights, world_position, i, t)) lean::add_term(color, t);
+    }
+#else
     {   // brdf_ibl (brdf.wgsl:517-576): the uniform cubes of the builder default, or texel cubes (brdf.wgsl:268-290: irradiance at level 0 along N,
         // prefiltered at roughness * (mips - 1) along R) through the shared seam-aware sampler
         const f3 prefiltered = lean::prefiltered(sc, reflect3(-sf.v, sf.n), sf.roughness);
@@ -2103,6 +2264,7 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
         } else if (kind != 1u) { light_dir = {0.0f, 0.0f, 0.0f}; radiance = {0.0f, 0.0f, 0.0f}; }
         lean::direct(lit, light_dir, radiance, color);
     }
+#endif
     asm volatile("; MARK store");
     if (ITEMS) { item->color = color; return true; }
     store_pixel(f, p, {color.x, color.y, color.z, 1.0f});
