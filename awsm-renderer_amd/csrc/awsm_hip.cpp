@@ -1065,6 +1065,7 @@ int awsm_hip_destroy(AwsmHipCtx* c) {
     for (auto& b : c->taa_img) fr(b); fr(c->taa_layers);
     for (auto& b : c->sel_tables) fr(b);
     fr(c->sel_layers);
+    fr(c->pick_scratch);
     for (auto& b : c->shadow_layers) fr(b); for (auto& b : c->shadow_cam) fr(b); for (auto& b : c->shadow_view_ctr) fr(b); for (auto& b : c->shadow_view_layers) fr(b); for (DevScene* sc : c->shadow_scene) if (sc) (void)hipFree(sc);
     for (auto& b : c->display8) fr(b); fr(c->effects16); fr(c->bloom_a); fr(c->bloom_b); fr(c->dof_lc); fr(c->dof_blur);
     for (int k = 0; k < kPassKinds * kSlots; k++) {

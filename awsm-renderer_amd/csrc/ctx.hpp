@@ -298,6 +298,10 @@ struct AwsmHipCtx {
     // AWSM_CLIP_IN_BIN=0 (read at awsm_hip_create): the world geometry pass keeps the earlier path — k_deform_transform writes clip, a cache hit too,
     // every workgroup decides its draw's cache hit itself, k_bin reads clip (A/B measurements, tests)
     bool clip_in_bin = true;
+
+    // awsm_hip_pick_ex / pick_rect / read_pick_map (awsm_pick.cpp): their scratch — the point answer, the per-draw counters, the key
+    // table, the entry list, the map — grow-only, per context: the queries are synchronous
+    DevBuf pick_scratch;
 };
 
 #define HIPCHK(c, call)                                                                            \

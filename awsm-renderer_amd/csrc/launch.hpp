@@ -10,6 +10,7 @@
 #include "env_cube.hpp"
 #include "tex_pool.hpp"
 #include "selection.hpp"
+#include "pick.hpp"
 
 extern "C" {
 // kernels_geometry.hip
@@ -52,6 +53,10 @@ void awsm_launch_shadow_resolve(const awsm::ShadowArgs* args, uint32_t msaa, hip
 // kernels_selection.hip
 void awsm_launch_selection(const awsm::SelectionDev* args, hipStream_t s);
 void awsm_launch_selection_layers(const awsm::SelectionDev* args, hipStream_t s);
+// kernels_pick.hip (called from awsm_pick.cpp alone: the frame pipeline's files enqueue none of them)
+void awsm_launch_pick_point(const awsm::PickDev* args, hipStream_t s);
+void awsm_launch_pick_map(const awsm::PickDev* args, hipStream_t s);
+void awsm_launch_pick_rect(const awsm::PickDev* args, hipStream_t s);
 // kernels_taa.hip
 void awsm_launch_taa(const awsm::TaaArgs* args, uint32_t msaa, hipStream_t s);
 void awsm_launch_taa_layers(const awsm::TaaArgs* args, uint32_t msaa, hipStream_t s);

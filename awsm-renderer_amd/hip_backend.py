@@ -45,7 +45,26 @@ EXPORTS = ["awsm_hip_create", "awsm_hip_destroy", "awsm_hip_last_error", "awsm_h
            "awsm_hip_shadow_defaults", "awsm_hip_shadow_pass", "awsm_hip_read_shadow_map", "awsm_hip_read_shadow",
            "awsm_hip_shadow_pass_views", "awsm_hip_read_shadow_map_view", "awsm_hip_read_shadow_view",
            "awsm_hip_selection_defaults", "awsm_hip_set_selection", "awsm_hip_read_selection",
-           "awsm_hip_taa_defaults", "awsm_hip_set_taa", "awsm_hip_read_taa"]
+           "awsm_hip_taa_defaults", "awsm_hip_set_taa", "awsm_hip_read_taa",
+           "awsm_hip_pick_query_defaults", "awsm_hip_pick_ex", "awsm_hip_pick_rect", "awsm_hip_read_pick_map"]
+
+AWSM_PICK_TRANSPARENT = 1
+PICK_LAYERS = ("world", "world_transparent", "hud", "hud_transparent")      # AwsmPickHit.layer / AwsmPickRectEntry.layer
+PICK_MISS = 0xFFFFFFFF                                                      # read_pick_map's word where nothing is hit
+
+
+class AwsmPickQuery(C.Structure):
+    """A pick query (awsm_hip_pick_ex / pick_rect / read_pick_map): AWSM_PICK_TRANSPARENT and the alpha a fragment must have been blended with."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("alpha_threshold", C.c_float)]
+
+
+class AwsmPickHit(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("mesh_key_high", C.c_uint32), ("mesh_key_low", C.c_uint32), ("triangle_index", C.c_uint32), ("layer", C.c_uint32),
+                ("alpha", C.c_float), ("depth_bits", C.c_uint32)]
+
+
+class AwsmPickRectEntry(C.Structure):
+    _fields_ = [("layer", C.c_uint32), ("mesh_key_high", C.c_uint32), ("mesh_key_low", C.c_uint32), ("pixels", C.c_uint32)]
 
 
 class AwsmConfig(C.Structure):
@@ -362,6 +381,12 @@ def load_library():
     lib.awsm_hip_shadow_pass_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.awsm_hip_read_shadow_map_view.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.awsm_hip_read_shadow_view.argtypes = [C.c_void_p, C.c_void_p]
+    # optional symbols (AWSM_HIP_ABI_VERSION unchanged): a library of the same ABI built without them loads, and the methods that need them say so
+    for name, argtypes in (("awsm_hip_pick_query_defaults", [C.c_void_p]), ("awsm_hip_pick_ex", [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+                           ("awsm_hip_pick_rect", [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+                           ("awsm_hip_read_pick_map", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     _lib = lib
     return lib
 
@@ -453,6 +478,43 @@ class HipDevice:
         out = (C.c_uint32 * 4)()
         self._chk(self.lib.awsm_hip_pick(self.ctx, x, y, out), "pick")
         return ((out[1] << 32) | out[2], out[3]) if out[0] else None
+
+    def _pick_fn(self, name: str):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise AwsmHipError(-6, name, "%s does not export %s" % (LIB_PATH, name))
+        return fn
+
+    def _pick_query(self, transparent, alpha_threshold, struct_size=None, flags=None):
+        q = AwsmPickQuery(C.sizeof(AwsmPickQuery) if struct_size is None else struct_size,
+                          (AWSM_PICK_TRANSPARENT if transparent else 0) if flags is None else flags, alpha_threshold)
+        return C.byref(q)
+
+    def pick_ex(self, x: int, y: int, transparent: bool = False, alpha_threshold: float = 0.5, **raw):
+        """awsm_hip_pick_ex: the hit at (x, y) of the last submitted frame, through the transparent passes' fragment lists when `transparent` ->
+        dict(mesh_key, triangle_index, layer, alpha, depth_bits) or None.  layer indexes PICK_LAYERS.  raw: struct_size / flags as given (tests)."""
+        hit = AwsmPickHit()
+        self._chk(self._pick_fn("awsm_hip_pick_ex")(self.ctx, x, y, self._pick_query(transparent, alpha_threshold, **raw), C.byref(hit)), "pick_ex")
+        if not hit.valid:
+            return None
+        return {"mesh_key": (hit.mesh_key_high << 32) | hit.mesh_key_low, "triangle_index": hit.triangle_index, "layer": hit.layer, "alpha": hit.alpha,
+                "depth_bits": hit.depth_bits}
+
+    def pick_rect(self, x0: int, y0: int, x1: int, y1: int, transparent: bool = False, alpha_threshold: float = 0.5, cap: int = 4096, **raw):
+        """awsm_hip_pick_rect over [x0, x1) x [y0, y1) -> ([(layer, mesh_key, pixels)] of at most `cap` entries, the number of distinct pairs)."""
+        out = (AwsmPickRectEntry * max(1, cap))()
+        n = C.c_uint32(0)
+        self._chk(self._pick_fn("awsm_hip_pick_rect")(self.ctx, x0, y0, x1, y1, self._pick_query(transparent, alpha_threshold, **raw), out if cap else None, cap,
+                                                      C.byref(n)), "pick_rect")
+        return [(e.layer, (e.mesh_key_high << 32) | e.mesh_key_low, e.pixels) for e in out[:min(n.value, cap)]], n.value
+
+    def read_pick_map(self, transparent: bool = False, alpha_threshold: float = 0.5, **raw):
+        """awsm_hip_read_pick_map -> (word [H, W] uint32: layer << 28 | draw index in its pass's expanded list, PICK_MISS for a miss;
+        triangle [H, W] uint32)."""
+        word = np.zeros((self.height, self.width), np.uint32)
+        tri = np.zeros((self.height, self.width), np.uint32)
+        self._chk(self._pick_fn("awsm_hip_read_pick_map")(self.ctx, self._pick_query(transparent, alpha_threshold, **raw), word.ctypes.data, tri.ctypes.data), "read_pick_map")
+        return word, tri
 
     def set_stage_timers(self, enabled: bool):
         """hipEventRecord between the stages of a frame (frame_end's ms_* fields); off = no bubbles between the kernels."""

@@ -162,6 +162,8 @@ def load_library():
         "awsm_host_brdf_lut_generate": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_resize": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "awsm_host_set_shard_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32]), "awsm_host_set_shard_bands": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]), "awsm_host_set_render_timings": (C.c_int, [vp, C.c_int]),
         "awsm_host_pick": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+        "awsm_host_pick_ex": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+        "awsm_host_pick_rect": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_float, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "awsm_host_set_anti_aliasing": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "awsm_host_set_post_processing": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_int]),
         "awsm_host_clear_post_processing": (C.c_int, [vp]),
@@ -733,11 +735,25 @@ class Host:
         """CameraMatrices.focus_distance / .aperture (camera bytes 496-503; the reference's defaults 10.0 and 5.6)."""
         self._chk(self.lib.awsm_host_camera_set_dof(self.h, focus_distance, aperture), "camera_set_dof")
 
-    def pick(self, x: int, y: int):
-        """AwsmRenderer::pick: the MeshKey under pixel (x, y) of the last rendered frame, or None (PickResult::Miss)."""
+    def pick(self, x: int, y: int, transparent: bool = False, alpha_threshold: float = 0.5):
+        """AwsmRenderer::pick: the MeshKey under pixel (x, y) of the last rendered frame, or None (PickResult::Miss).  transparent=True: a
+        transparent mesh whose fragment there was blended with alpha >= alpha_threshold is hit too (awsm_hip_pick_ex has the rule)."""
         hit, key = C.c_uint32(0), C.c_uint64(0)
-        self._chk(self.lib.awsm_host_pick(self.h, x, y, C.byref(hit), C.byref(key)), "pick")
+        if transparent:
+            self._chk(self.lib.awsm_host_pick_ex(self.h, x, y, 1, alpha_threshold, C.byref(hit), C.byref(key), None), "pick_ex")
+        else:
+            self._chk(self.lib.awsm_host_pick(self.h, x, y, C.byref(hit), C.byref(key)), "pick")
         return key.value if hit.value else None
+
+    def pick_rect(self, x0: int, y0: int, x1: int, y1: int, transparent: bool = False, alpha_threshold: float = 0.5, cap: int = 1024):
+        """The meshes the rectangle [x0, x1) x [y0, y1) of the last rendered frame shows -> [(MeshKey, layer, pixels)], ordered by layer (0 world
+        opaque, 1 world transparent, 2 HUD opaque, 3 HUD transparent), then by draw order."""
+        keys, layers, pixels = (C.c_uint64 * max(1, cap))(), (C.c_uint32 * max(1, cap))(), (C.c_uint32 * max(1, cap))()
+        n = C.c_uint32(0)
+        self._chk(self.lib.awsm_host_pick_rect(self.h, x0, y0, x1, y1, 1 if transparent else 0, alpha_threshold, keys, layers, pixels, cap, C.byref(n)), "pick_rect")
+        if n.value > cap:
+            return self.pick_rect(x0, y0, x1, y1, transparent, alpha_threshold, n.value)
+        return [(int(keys[i]), int(layers[i]), int(pixels[i])) for i in range(n.value)]
 
     def set_shard_bands(self, n: int, r: int, compact_output: bool = False):
         self._chk(self.lib.awsm_host_set_shard_bands(self.h, n, r, 1 if compact_output else 0), "set_shard_bands")
@@ -1127,6 +1143,14 @@ class Renderer:
     def set_selection(self, mesh_keys=(), on: bool = True, **overrides):
         """Outline and box the meshes `mesh_keys` (keys from pick()) in every later render(); on=False for off."""
         self.host.set_selection(mesh_keys, on, **overrides)
+
+    def pick(self, x: int, y: int, transparent: bool = False, alpha_threshold: float = 0.5):
+        """The MeshKey under pixel (x, y) of the last frame, or None; transparent=True picks through the transparent meshes' fragments."""
+        return self.host.pick(x, y, transparent, alpha_threshold)
+
+    def pick_rect(self, x0: int, y0: int, x1: int, y1: int, transparent: bool = False, alpha_threshold: float = 0.5):
+        """[(MeshKey, layer, pixels)] of the meshes the rectangle [x0, x1) x [y0, y1) of the last frame shows."""
+        return self.host.pick_rect(x0, y0, x1, y1, transparent, alpha_threshold)
 
     def set_shadow(self, light=True, cascades: Optional[int] = None, cascade_lambda: float = 0.5, cascade_distance: float = 0.0, **overrides):
         """Shadows from one of the scene's lights: an index into scene.lights (directional, spot or point), True for the first directional light

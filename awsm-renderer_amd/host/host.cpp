@@ -75,6 +75,8 @@ struct Backend {
     int (*set_taa)(AwsmHipCtx*, const AwsmTaa*) = nullptr;              // optional: temporal anti-aliasing (awsm_host_set_taa)
     int (*selection_defaults)(AwsmSelection*) = nullptr;                // optional: the editor's selection overlay (awsm_host_set_selection)
     int (*set_selection)(AwsmHipCtx*, const AwsmSelection*, const uint32_t*, uint32_t, const AwsmSelectionBox*, uint32_t) = nullptr;
+    int (*pick_ex)(AwsmHipCtx*, int32_t, int32_t, const AwsmPickQuery*, AwsmPickHit*) = nullptr;      // optional: picking through the transparent passes (awsm_host_pick_ex / _pick_rect)
+    int (*pick_rect)(AwsmHipCtx*, int32_t, int32_t, int32_t, int32_t, const AwsmPickQuery*, AwsmPickRectEntry*, uint32_t, uint32_t*) = nullptr;
     int (*shadow_defaults)(AwsmShadow*) = nullptr;                      // optional: shadows (awsm_host_set_shadow)
     int (*shadow_pass)(AwsmHipCtx*, const AwsmShadow*, const void*, size_t, const AwsmDraw*, uint32_t) = nullptr;
     int (*shadow_pass_views)(AwsmHipCtx*, const AwsmShadow*, const AwsmShadowView*, uint32_t) = nullptr;      // optional: point lights, cascades
@@ -726,6 +728,8 @@ int awsm_host_create(const char* backend_path, int device, void* stream, uint32_
     b.set_taa = reinterpret_cast<decltype(b.set_taa)>(dlsym(b.dl, "awsm_hip_set_taa"));      // optional (awsm_host_set_taa)
     b.selection_defaults = reinterpret_cast<decltype(b.selection_defaults)>(dlsym(b.dl, "awsm_hip_selection_defaults"));      // optional (awsm_host_set_selection)
     b.set_selection = reinterpret_cast<decltype(b.set_selection)>(dlsym(b.dl, "awsm_hip_set_selection"));
+    b.pick_ex = reinterpret_cast<decltype(b.pick_ex)>(dlsym(b.dl, "awsm_hip_pick_ex"));      // optional (awsm_host_pick_ex)
+    b.pick_rect = reinterpret_cast<decltype(b.pick_rect)>(dlsym(b.dl, "awsm_hip_pick_rect"));      // optional (awsm_host_pick_rect)
     b.shadow_defaults = reinterpret_cast<decltype(b.shadow_defaults)>(dlsym(b.dl, "awsm_hip_shadow_defaults"));      // optional (awsm_host_set_shadow)
     b.shadow_pass = reinterpret_cast<decltype(b.shadow_pass)>(dlsym(b.dl, "awsm_hip_shadow_pass"));
     b.shadow_pass_views = reinterpret_cast<decltype(b.shadow_pass_views)>(dlsym(b.dl, "awsm_hip_shadow_pass_views"));
@@ -1441,6 +1445,44 @@ int awsm_host_pick(AwsmHost* h, int32_t x, int32_t y, uint32_t* hit, uint64_t* m
     if (rc) return dev_fail(h, rc, "pick");
     *hit = p.valid;
     *mesh_key = p.valid ? (((uint64_t)p.mesh_key_high << 32) | p.mesh_key_low) : 0;   // KeyData::from_ffi
+    return AWSM_OK;
+}
+// ... and through the transparent passes' fragment lists (include/awsm_hip.h: awsm_hip_pick_ex): the query's record from the two plain arguments
+static int pick_query(AwsmHost* h, const char* entry, int transparent, float alpha_threshold, AwsmPickQuery* q) {
+    if (!(alpha_threshold >= 0.0f && alpha_threshold <= 1.0f)) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "%s: alpha_threshold = %g (0 .. 1)", entry, (double)alpha_threshold);
+    q->struct_size = (uint32_t)sizeof(AwsmPickQuery); q->flags = transparent ? AWSM_PICK_TRANSPARENT : 0u; q->alpha_threshold = alpha_threshold;
+    return AWSM_OK;
+}
+int awsm_host_pick_ex(AwsmHost* h, int32_t x, int32_t y, int transparent, float alpha_threshold, uint32_t* hit, uint64_t* mesh_key, uint32_t* layer) {
+    if (!h || !hit || !mesh_key) return AWSM_ERR_INVALID_ARGUMENT;
+    if (!h->be.pick_ex) return fail(h, AWSM_ERR_UNSUPPORTED, "pick_ex: the backend library has no %s", "awsm_hip_pick_ex");
+    AwsmPickQuery q;
+    int rc = pick_query(h, "pick_ex", transparent, alpha_threshold, &q);
+    if (rc) return rc;
+    AwsmPickHit p{};
+    if ((rc = h->be.pick_ex(h->ctx, x, y, &q, &p))) return dev_fail(h, rc, "pick_ex");
+    *hit = p.valid;
+    *mesh_key = p.valid ? (((uint64_t)p.mesh_key_high << 32) | p.mesh_key_low) : 0;
+    if (layer) *layer = p.valid ? p.layer : 0u;
+    return AWSM_OK;
+}
+int awsm_host_pick_rect(AwsmHost* h, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int transparent, float alpha_threshold, uint64_t* keys, uint32_t* layers,
+                        uint32_t* pixels, uint32_t cap, uint32_t* n_out) {
+    if (!h || !n_out) return AWSM_ERR_INVALID_ARGUMENT;
+    if (cap && !keys) return fail(h, AWSM_ERR_INVALID_ARGUMENT, "pick_rect: keys == NULL with cap = %u", cap);
+    if (!h->be.pick_rect) return fail(h, AWSM_ERR_UNSUPPORTED, "pick_rect: the backend library has no %s", "awsm_hip_pick_rect");
+    AwsmPickQuery q;
+    int rc = pick_query(h, "pick_rect", transparent, alpha_threshold, &q);
+    if (rc) return rc;
+    std::vector<AwsmPickRectEntry> entries(cap);
+    uint32_t n = 0;
+    if ((rc = h->be.pick_rect(h->ctx, x0, y0, x1, y1, &q, cap ? entries.data() : nullptr, cap, &n))) return dev_fail(h, rc, "pick_rect");
+    for (uint32_t i = 0; i < std::min(n, cap); i++) {
+        keys[i] = ((uint64_t)entries[i].mesh_key_high << 32) | entries[i].mesh_key_low;
+        if (layers) layers[i] = entries[i].layer;
+        if (pixels) pixels[i] = entries[i].pixels;
+    }
+    *n_out = n;
     return AWSM_OK;
 }
 int awsm_host_set_render_timings(AwsmHost* h, int enabled) { int rc = h->be.set_stage_timers(h->ctx, enabled); return rc ? dev_fail(h, rc, "set_stage_timers") : AWSM_OK; }

@@ -20,6 +20,9 @@ post pass: it implies the post pass) and writes the last; with --select the N fr
 --grid draws the editor's ground grid (the plane y = 0: unit lines, every tenth stronger, the X axis red and the Z axis blue) under the transparent meshes.
 --select X,Y (may be repeated) picks the mesh under each pixel of a first frame and renders again with those meshes selected: an outline around their
 visible pixels and a wire box around each one's world bounding box, dimmed where other geometry hides it.
+--select-transparent [T] lets --select hit a transparent mesh where its fragment was drawn with alpha >= T (default 0.5): the pick then reads the
+transparent pass's fragment lists as well as the visibility keys; such a mesh gets its box only.  --select-rect X0,Y0,X1,Y1 selects every mesh the
+rectangle shows (a marquee).
 """
 import argparse
 import os
@@ -65,6 +68,9 @@ def main():
     ap.add_argument("--shadow-cascades", type=int, default=None, metavar="N", help="with --shadow on a directional light: N nested maps along the camera's depth, 1 .. 4 (default 1)")
     ap.add_argument("--shadow-strength", type=float, default=None, metavar="X", help="with --shadow: how dark a shadow is, 0 .. 1 (default 0.7)")
     ap.add_argument("--select", action="append", default=[], metavar="X,Y", help="select the mesh under this pixel (outline + bounding box); may be repeated; not with --via-glb")
+    ap.add_argument("--select-transparent", nargs="?", const=0.5, type=float, default=None, metavar="T",
+                    help="with --select / --select-rect: pick through the transparent meshes' fragments too, those drawn with alpha >= T (default 0.5); a transparent mesh gets its box only")
+    ap.add_argument("--select-rect", metavar="X0,Y0,X1,Y1", help="select every mesh the rectangle [X0, X1) x [Y0, Y1) shows; not with --via-glb")
     ap.add_argument("--via-glb", action="store_true", help="write the scene to a .glb next to the output and render from the file (native glTF reader)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -114,15 +120,22 @@ def main():
         r.set_taa(True)
     stats = r.render(sync=True)
     picked = []
-    if a.select:
+    if a.select or a.select_rect:
         if a.via_glb:
-            ap.error("--select picks through the scene description's meshes; not with --via-glb")
+            ap.error("--select / --select-rect pick through the scene description's meshes; not with --via-glb")
+        through = a.select_transparent is not None
+        threshold = a.select_transparent if through else 0.5
         for xy in a.select:
             x, y = (int(v) for v in xy.split(","))
-            key = r.host.pick(x, y)
+            key = r.host.pick(x, y, transparent=through, alpha_threshold=threshold)
             print(f"--select {x},{y}: " + ("nothing there" if key is None else f"mesh {key:#x}"))
             if key is not None and key not in picked:
                 picked.append(key)
+        if a.select_rect:
+            x0, y0, x1, y1 = (int(v) for v in a.select_rect.split(","))
+            shown = r.host.pick_rect(x0, y0, x1, y1, transparent=through, alpha_threshold=threshold)
+            print(f"--select-rect {x0},{y0},{x1},{y1}: " + (", ".join(f"mesh {key:#x} (layer {layer}, {px} px)" for key, layer, px in shown) or "nothing there"))
+            picked += [key for key, layer, _ in shown if key not in picked and layer < 2]      # HUD meshes are not selectable (the host leaves them out)
         if picked:
             r.set_selection(picked)
             stats = r.render(sync=True)

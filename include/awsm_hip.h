@@ -768,6 +768,51 @@ int awsm_hip_taa_defaults(AwsmTaa* out);
 int awsm_hip_set_taa(AwsmHipCtx* ctx, const AwsmTaa* taa /* NULL = off, history dropped */);
 int awsm_hip_read_taa(AwsmHipCtx* ctx, uint16_t* resolved_rgba16f_out, float* lookup_xy_out, uint8_t* used_out);
 
+/* ---- picking that sees transparent meshes: point and rectangle queries ("Make transparent meshes pickable" of the reference's
+ * "Next up" list).  awsm_hip_pick reads the visibility keys, and a transparent mesh has none; these queries also read the fragment lists the
+ * transparent passes of the last submitted frame left.  Over sample 0, the hit at a pixel is the first of these that exists:
+ *   1. the LAST fragment of the HUD transparent pass's list with alpha >= alpha_threshold   (layer 3; only if that pass ran this frame)
+ *   2. the HUD geometry key                                                                 (layer 2)
+ *   3. the LAST fragment of the world transparent pass's list with alpha >= alpha_threshold (layer 1)
+ *   4. the world visibility key                                                             (layer 0)
+ * The pipeline tests LessEqual and writes depth, so a later fragment of a list is nearer.  The alpha is the one the fragment was blended with (a MASK
+ * fragment that survived its cutoff: 1).  What the lists do not hold cannot be picked: a fragment the depth test or a cutoff discarded, and one
+ * behind a fragment that wrote depth, whatever that one's alpha.  With AWSM_PICK_TRANSPARENT clear steps 1 and 3 are left out and every answer is
+ * awsm_hip_pick's.  With it set and no transparent pass in the frame, the opaque layers alone answer.
+ *   pick_query_defaults  flags 0, alpha_threshold 0.5; struct_size = sizeof(AwsmPickQuery).
+ *   pick_ex        the rule at (x, y).  triangle_index: primitive-local, in the pass the hit belongs to; alpha: 1 for layers 0 and 2; depth_bits:
+ *                  the key's depth word for layers 0 and 2, for a fragment the depth its triangle's set-up record gives at the pixel (sample 0).
+ *   pick_rect      the rule at every pixel of [x0, x1) x [y0, y1) clamped to the frame -> the distinct (layer, mesh key) pairs with the pixels each
+ *                  holds, ordered by layer, then by the draw's place in its pass's list; draws that share a mesh key are merged into the first.
+ *                  *n_out = the distinct pairs, of which at most cap are written; an empty rectangle gives 0.  Integer sums: deterministic.
+ *   read_pick_map  test aid: the rule at every pixel of the frame, word = layer << 28 | index of the draw in its pass's list as the device expands
+ *                  it (a draw without triangles dropped, one entry per instance), all ones for a miss; triangle = triangle_index.  Either may be NULL.
+ * query == NULL: the defaults.  All three are synchronous, read the last submitted frame's slot and wait for every stream first.
+ * AWSM_ERR_NOT_READY before a geometry pass, and with the flag set while a transparent pass's counters show a bin or fragment list overflow that
+ * awsm_hip_frame_end has not replayed yet; AWSM_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags, a threshold outside [0, 1] or NaN,
+ * out == NULL with cap > 0; AWSM_ERR_UNSUPPORTED on a sharded context for the flag and for pick_rect (a rectangle's answer would need merging
+ * across ranks).  Optional symbols: AWSM_HIP_ABI_VERSION is unchanged. ---- */
+#define AWSM_PICK_TRANSPARENT 1u
+typedef struct AwsmPickQuery {
+    uint32_t struct_size;
+    uint32_t flags;             /* AWSM_PICK_TRANSPARENT */
+    float    alpha_threshold;   /* 0..1 */
+} AwsmPickQuery;
+typedef struct AwsmPickHit {
+    uint32_t valid;             /* 0 = background / outside the frame */
+    uint32_t mesh_key_high, mesh_key_low;
+    uint32_t triangle_index;
+    uint32_t layer;             /* 0 world opaque, 1 world transparent, 2 HUD opaque, 3 HUD transparent */
+    float    alpha;
+    uint32_t depth_bits;        /* f32 bits */
+} AwsmPickHit;
+typedef struct AwsmPickRectEntry { uint32_t layer, mesh_key_high, mesh_key_low, pixels; } AwsmPickRectEntry;
+int awsm_hip_pick_query_defaults(AwsmPickQuery* out);
+int awsm_hip_pick_ex(AwsmHipCtx* ctx, int32_t x, int32_t y, const AwsmPickQuery* query, AwsmPickHit* out);
+int awsm_hip_pick_rect(AwsmHipCtx* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1, const AwsmPickQuery* query, AwsmPickRectEntry* out, uint32_t cap,
+                       uint32_t* n_out);
+int awsm_hip_read_pick_map(AwsmHipCtx* ctx, const AwsmPickQuery* query, uint32_t* word_out, uint32_t* triangle_out /* width x height each */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -356,6 +356,15 @@ int awsm_host_mesh_set_instances(AwsmHost* h, AwsmKey mesh, const float* trs10, 
 int awsm_host_mesh_append_instances(AwsmHost* h, AwsmKey mesh, const float* trs10, uint32_t n);
 /* AwsmRenderer::pick (picker.rs:55-121): *hit = 1 and *mesh_key = the MeshKey (KeyData::as_ffi) under pixel (x, y) of the last frame, else *hit = 0 */
 int awsm_host_pick(AwsmHost* h, int32_t x, int32_t y, uint32_t* hit, uint64_t* mesh_key);
+/* The same through the transparent passes of the last frame (awsm_hip_pick_ex in awsm_hip.h has the rule): transparent != 0 lets a fragment
+ * that was blended with alpha >= alpha_threshold be hit.  *layer (may be NULL): 0 world opaque, 1 world transparent, 2 HUD opaque, 3 HUD
+ * transparent.  awsm_host_pick_rect: the distinct (layer, MeshKey) pairs the rectangle [x0, x1) x [y0, y1) shows, with the pixels each holds, in
+ * the backend's order; *n_out = how many there are, of which at most cap are written (layers and pixels may be NULL).
+ * AWSM_ERR_INVALID_ARGUMENT for a threshold outside [0, 1] or a NULL keys with cap > 0; AWSM_ERR_UNSUPPORTED, naming the symbol, on a backend
+ * library without awsm_hip_pick_ex / awsm_hip_pick_rect; the backend's own refusals otherwise. */
+int awsm_host_pick_ex(AwsmHost* h, int32_t x, int32_t y, int transparent, float alpha_threshold, uint32_t* hit, uint64_t* mesh_key, uint32_t* layer);
+int awsm_host_pick_rect(AwsmHost* h, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int transparent, float alpha_threshold, uint64_t* keys, uint32_t* layers,
+                        uint32_t* pixels, uint32_t cap, uint32_t* n_out);
 int awsm_host_set_shard_bands(AwsmHost* h, uint32_t n, uint32_t r, uint32_t compact_output);   /* awsm_hip_set_shard_bands */
 /* AwsmRendererLogging.render_timings (debug.rs:8-12; the spans of render.rs:150-320): per-stage times in the frame stats, on by default;
  * off = awsm_hip_set_stage_timers(ctx, 0), the ms_* fields of the stats read 0 and the frame loses its event bubbles */
