@@ -31,13 +31,6 @@
 #ifndef AWSM_LEAN_WAVES
 #define AWSM_LEAN_WAVES 6
 #endif
-// 1: lean_core issues the BRDF table's four loads right behind the surface terms and consumes them behind the first kLeanDeferredLights lights'
-//    arithmetic (lean::brdf_lut_issue / brdf_lut_finish / light_term / add_term).
-// 0: the text, and with it the instruction stream, from before that: the table looked up and consumed inside the IBL block, the lights added one by
-//    one (lean::brdf_lut, lean::direct).  For A/B builds (tools/build_variants.sh NAME "-DAWSM_LEAN_LUT_LATE=0").
-#ifndef AWSM_LEAN_LUT_LATE
-#define AWSM_LEAN_LUT_LATE 1
-#endif
 
 namespace awsm {
 
@@ -1284,26 +1277,33 @@ AWSM_DI m4 cload_m4(const void* base, uint32_t byte_off) {
 
 namespace lean {
 struct Tap { uint32_t t00, t10, t01, t11; float fx, fy; };
+template <typename T> AWSM_DI T gload_any(const void* base, uint32_t off) { return gload<T>(base, off); }
+template <typename T> AWSM_DI T gload_any(unsigned long long base, uint32_t off) { return gload64<T>(base, off); }
 // A texture entry of the lean record, decoded: base address, log2 extents.  Decoding all five before the first texel load means the
 // record's loads are waited for once, ahead of the burst (a wait inside the burst would also wait for the texels issued so far:
 // vmcnt counts in order).
-struct Tex { unsigned long long base; uint32_t lw, lh; };
+// BASE: const void* — the record sits in scalar registers (a strip inside one draw: the base address in an SGPR pair, 32-bit byte offsets per lane
+// -> global_load ... v_off, s[base], no 64-bit address arithmetic at all); unsigned long long — per lane (a strip over several draws)
+template <typename BASE> struct TexT { BASE base; uint32_t lw, lh; };
+typedef TexT<unsigned long long> Tex;
+typedef TexT<const void*> TexS;
 AWSM_DI Tex decode(uint32_t lo, uint32_t hi) { return {((unsigned long long)(hi & 0xFFFFu) << 32) | lo, (hi >> 16) & 15u, (hi >> 20) & 15u}; }
+AWSM_DI TexS decode_s(uint32_t lo, uint32_t hi) { return {reinterpret_cast<const void*>(((unsigned long long)(hi & 0xFFFFu) << 32) | lo), (hi >> 16) & 15u, (hi >> 20) & 15u}; }
 // sample_level_fast's addressing for a power-of-two repeat texture whose extent comes as log2: texel (i0, j0) and its right / lower
 // neighbours.  The two texels of a row are one 8-byte load; when the footprint wraps around the row end (i0 = W - 1) the second
 // texel of each pair is re-fetched from the row start — a branch almost never taken, and its loads land in the pair's registers
 // under the wrapped lanes' exec mask, so nothing waits.
-AWSM_DI void fetch(const Tex& x, float u, float v, Tap& t) {
+template <typename BASE> AWSM_DI void fetch(const TexT<BASE>& x, float u, float v, Tap& t) {
     const float xf = __builtin_amdgcn_ldexpf(u, (int)x.lw) - 0.5f, yf = __builtin_amdgcn_ldexpf(v, (int)x.lh) - 0.5f;     // u * W - 0.5 (W a power of two: exact product)
     const float flx = floorf(xf), fly = floorf(yf);
     t.fx = xf - flx; t.fy = yf - fly;
     const uint32_t xi = (uint32_t)(int)flx, yi = (uint32_t)(int)fly;
     const uint32_t i0 = __builtin_amdgcn_ubfe(xi, 0u, x.lw), j0 = __builtin_amdgcn_ubfe(yi, 0u, x.lh), j1 = __builtin_amdgcn_ubfe(yi + 1u, 0u, x.lh);
     const uint32_t sh = x.lw + 2u, i0b = i0 << 2;
-    const u32x2a4 p0 = gload64<u32x2a4>(x.base, (j0 << sh) | i0b), p1 = gload64<u32x2a4>(x.base, (j1 << sh) | i0b);
+    const u32x2a4 p0 = gload_any<u32x2a4>(x.base, (j0 << sh) | i0b), p1 = gload_any<u32x2a4>(x.base, (j1 << sh) | i0b);
     t.t00 = p0.x; t.t10 = p0.y; t.t01 = p1.x; t.t11 = p1.y;
     if (__builtin_amdgcn_ubfe(xi + 1u, 0u, x.lw) == 0u) {      // i1 wrapped to column 0
-        t.t10 = gload64<uint32_t>(x.base, j0 << sh); t.t11 = gload64<uint32_t>(x.base, j1 << sh);
+        t.t10 = gload_any<uint32_t>(x.base, j0 << sh); t.t11 = gload_any<uint32_t>(x.base, j1 << sh);
     }
 }
 struct Weights { float w00, w10, w01, w11; };
@@ -1317,72 +1317,17 @@ template <int BYTE> AWSM_DI float ub(uint32_t t) {
 template <int BYTE> AWSM_DI float channel(const Tap& t, const Weights& w) {      // the bilinear sum of the RAW 0..255 values: the 1/255 sits in the draw's factors
     return ub<BYTE>(t.t00) * w.w00 + ub<BYTE>(t.t10) * w.w10 + ub<BYTE>(t.t01) * w.w01 + ub<BYTE>(t.t11) * w.w11;
 }
-// brdf.wgsl:293-302 (sample_brdf_lut above, same arithmetic; global-address-space loads)
-AWSM_DI f2 brdf_lut(const uint16_t* lut, uint32_t lut_w, uint32_t lut_h, float n_dot_v, float roughness) {
-    const float u = saturate(n_dot_v), v = saturate(roughness);
-    const int W = (int)lut_w, H = (int)lut_h;
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;          // in [-0.5, extent - 0.5]: no range guard needed
-    const float flx = floorf(x), fly = floorf(y);
-    const float fx = x - flx, fy = y - fly;
-    const int xi = (int)flx, yi = (int)fly;
-    const int i0 = max(xi, 0), i1 = min(xi + 1, W - 1), j0 = max(yi, 0), j1 = min(yi + 1, H - 1);
-    const uint32_t r0 = (uint32_t)(j0 * W) << 2, r1 = (uint32_t)(j1 * W) << 2;
-    const uint32_t t00 = gload<uint32_t>(lut, r0 + ((uint32_t)i0 << 2)), t10 = gload<uint32_t>(lut, r0 + ((uint32_t)i1 << 2));
-    const uint32_t t01 = gload<uint32_t>(lut, r1 + ((uint32_t)i0 << 2)), t11 = gload<uint32_t>(lut, r1 + ((uint32_t)i1 << 2));
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    const float r_top = f16_bits_to_f32((unsigned short)(t00 & 0xFFFFu)) * gx + f16_bits_to_f32((unsigned short)(t10 & 0xFFFFu)) * fx;
-    const float r_bot = f16_bits_to_f32((unsigned short)(t01 & 0xFFFFu)) * gx + f16_bits_to_f32((unsigned short)(t11 & 0xFFFFu)) * fx;
-    const float g_top = f16_bits_to_f32((unsigned short)(t00 >> 16)) * gx + f16_bits_to_f32((unsigned short)(t10 >> 16)) * fx;
-    const float g_bot = f16_bits_to_f32((unsigned short)(t01 >> 16)) * gx + f16_bits_to_f32((unsigned short)(t11 >> 16)) * fx;
-    return {r_top * gy + r_bot * fy, g_top * gy + g_bot * fy};
-}
-// brdf_direct (brdf.wgsl:308-381) for a material without sheen / clearcoat, the same terms arranged for fewer instructions: one
-// reciprocal for the three denominators of D * G1(l) / (4 n.l n.v), clamps as output modifiers, per-pixel factors hoisted.
-// x -> sat(1 - x) equals 1 - sat(max(x, 0)) for every x, and sat(n.l) serves both as n.l >= 0 and as the saturated value (n, l unit).
-// F is increasing in F0 per channel, so max(F) = F(max(F0)): k_d needs one multiply-add.  (The half vector's length and its two dot products stay as
-// the WGSL forms them — v + l first: measured, |v + l|^2 = 2 + 2 v.l and n.(v + l) = n.v + n.l lose their relative accuracy to cancellation when the
-// light comes from behind the viewer's side at grazing angles, and a GGX lobe multiplies that by 4 / (alpha^4): 13 pixels of a random view went out of bounds.)
-struct Lit {
-    f3 n, v, F0, df90, bd;          // bd = base * (1 - metallic) / pi
-    float ndv_raw, ndv_dir, ndv4, a2m1, a2_g1v, gk, one_m_gk, occlusion, F0max, df90max;
-};
-AWSM_DI void direct(const Lit& s, f3 l, f3 radiance, f3& color) {
-    const float ndl = saturate(fm::fdot(s.n, l));
-#ifndef AWSM_NO_LIGHT_SKIP
-    // A light behind the surface for every pixel of the wavefront (a 16x4 strip is mostly one surface: a ceiling under four lights from above, a wall
-    // facing away) adds exactly zero — w = n.l * occlusion = 0 multiplies finite factors (den >= kEps^2 > 0, radiance and F finite), and 0 + c = c — so
-    // the wavefront skips the term: same bits, ~45 instructions fewer per skipped light (round 5).
-    if (__builtin_amdgcn_ballot_w64(ndl > 0.0f) == 0ull) return;
-#endif
-    const f3 sum = s.v + l;
-    const float len_sq = fm::fdot(sum, sum);
-    const bool has_half = len_sq > 1e-8f;
-    const float inv_len = has_half ? fm::rsq(len_sq) : 0.0f;
-    const float ndh = saturate(fm::fdot(s.n, sum) * inv_len);
-    const float vdh = fm::fdot(s.v, sum) * inv_len;
-    const float p = saturate(1.0f - (has_half ? vdh : s.ndv_dir));
-    const float p2 = p * p, p5 = (p2 * p2) * p;
-    const f3 F = {s.F0.x + s.df90.x * p5, s.F0.y + s.df90.y * p5, s.F0.z + s.df90.z * p5};
-    const float dd = (ndh * ndh) * s.a2m1 + 1.0f;
-    const float den = (((kPi * dd) * dd + kEps) * (ndl * s.one_m_gk + s.gk)) * fmaxf(s.ndv4 * ndl, kEps);
-    const float spec = has_half ? (s.a2_g1v * ndl) * fm::rcp(den) : 0.0f;
-    const float k_d = 1.0f - (s.F0max + s.df90max * p5);
-    const float w = ndl * s.occlusion;
-    color.x += (s.bd.x * k_d + F.x * spec) * (radiance.x * w);
-    color.y += (s.bd.y * k_d + F.y * spec) * (radiance.y * w);
-    color.z += (s.bd.z * k_d + F.z * spec) * (radiance.z * w);
-}
 }  // namespace lean
 
-#if AWSM_LEAN_LUT_LATE
-// ---- The BRDF table's round trip behind the lights.  brdf_lut above in two halves — brdf_lut_issue forms the footprint and
-// issues the four loads, brdf_lut_finish converts and blends — and the light body of lean_core's loop with direct above as a function that hands the
-// light's term back instead of adding it, so that lean_core can evaluate lights while the table's texels are on their way and add afterwards.
-// The code above is RELAXED: for a * b + c * d the compiler picks the product it fuses, and it picks again when the code around the sum changes.  These
-// restatements must give the bits the loop gave, so they are compiled with contraction OFF and every fused multiply-add the loop's instructions had is
-// written out (read from k_shade_lean<false,0,false>'s assembly of the commit before; profiles/lut_late_isa.txt): nothing is left to choose.
-// The price: this route's light body, table lookup and IBL sum exist twice while the knob lives — an edit to the math goes into both copies — and
-// this copy records one toolchain's choices (bench.py's dumps equal the earlier order's word for word: profiles/lut_late_identity.txt).
+// ---- The lighting of the lean route, with the BRDF table's round trip behind the lights.  The table lookup
+// (brdf.wgsl:293-302, sample_brdf_lut's arithmetic on global-address-space loads) comes in two halves — brdf_lut_issue forms the footprint and issues
+// the four loads, brdf_lut_finish converts and blends — and a light is a function that hands its term back instead of adding it, so that lean_core
+// can evaluate lights while the table's texels are on their way and add afterwards.
+// The code around this block is RELAXED: for a * b + c * d the compiler picks the product it fuses, and it picks again when the code around the sum
+// changes.  This route's bits were fixed while the table was still consumed inside the IBL block and the lights were added one by one, so these
+// functions are compiled with contraction OFF and every fused multiply-add that loop's instructions had is written out (read from
+// k_shade_lean<false,0,false>'s assembly of that commit; profiles/lut_late_isa.txt, lut_late_identity.txt): nothing is left to choose.  They are the
+// route's one definition of its light body, table lookup and IBL sum, and they record one toolchain's choices.
 #pragma clang fp contract(off)
 namespace lean {
 constexpr uint32_t kLeanDeferredLights = 2u;      // six registers a light; three lights cost k_shade_lean<false,0,.> its seventh wavefront (73 / 74 VGPRs)
@@ -1434,8 +1379,21 @@ AWSM_DI f3 ibl_color(f3 F0, float f90, f2 lut, f3 prefiltered, float occlusion, 
     const f3 specular = {m * (prefiltered.x * spec_term.x), m * (prefiltered.y * spec_term.y), m * (prefiltered.z * spec_term.z)};
     return {(base_contribution.x + specular.x) + emissive.x, (base_contribution.y + specular.y) + emissive.y, (base_contribution.z + specular.z) + emissive.z};
 }
-// Light i of lean_core's loop, direct included.  false (wave-uniform): the whole wavefront skips the light (AWSM_NO_LIGHT_SKIP: never) and `t` is
-// untouched — the caller adds nothing, not a zero, so a -0 channel keeps its sign.
+// brdf_direct (brdf.wgsl:308-381) for a material without sheen / clearcoat, the same terms arranged for fewer instructions: one
+// reciprocal for the three denominators of D * G1(l) / (4 n.l n.v), clamps as output modifiers, per-pixel factors hoisted (Lit).
+// x -> sat(1 - x) equals 1 - sat(max(x, 0)) for every x, and sat(n.l) serves both as n.l >= 0 and as the saturated value (n, l unit).
+// F is increasing in F0 per channel, so max(F) = F(max(F0)): k_d needs one multiply-add.  (The half vector's length and its two dot products stay as
+// the WGSL forms them — v + l first: measured, |v + l|^2 = 2 + 2 v.l and n.(v + l) = n.v + n.l lose their relative accuracy to cancellation when the
+// light comes from behind the viewer's side at grazing angles, and a GGX lobe multiplies that by 4 / (alpha^4): 13 pixels of a random view went out of bounds.)
+struct Lit {
+    f3 n, v, F0, df90, bd;          // bd = base * (1 - metallic) / pi
+    float ndv_dir, ndv4, a2m1, a2_g1v, gk, one_m_gk, occlusion, F0max, df90max;
+};
+// Light i of lean_core's loop.  false (wave-uniform): the whole wavefront skips the light (AWSM_NO_LIGHT_SKIP: never) and `t` is untouched — the
+// caller adds nothing, not a zero, so a -0 channel keeps its sign.  Skipping gives the same bits: a light behind the surface for every pixel of the
+// wavefront (a 16x4 strip is mostly one surface: a ceiling under four lights from above, a wall facing away), or a spot whose cone misses all of
+// them, would add exactly zero — w = n.l * occlusion = 0, or att = 0, multiplies finite factors (den >= kEps^2 > 0, radiance and F finite), and
+// 0 + c = c — at ~45 instructions fewer per skipped light (round 5).
 AWSM_DI bool light_term(const Lit& s, const void* lights_pre, const void* lights, f3 world_position, uint32_t i, LightTerm& t) {
     const f32x4 pre0 = cload<f32x4>(lights_pre, i * 32u), pre1 = cload<f32x4>(lights_pre, i * 32u + 16u);
     const uint32_t kind = (uint32_t)pre0.w;
@@ -1464,7 +1422,7 @@ AWSM_DI bool light_term(const Lit& s, const void* lights_pre, const void* lights
     } else if (kind != 1u) { l = {0.0f, 0.0f, 0.0f}; radiance = {0.0f, 0.0f, 0.0f}; }
     const float ndl = saturate(dot_yxz(s.n, l));
 #ifndef AWSM_NO_LIGHT_SKIP
-    if (__builtin_amdgcn_ballot_w64(ndl > 0.0f) == 0ull) return false;              // behind the surface for the whole wavefront (direct above)
+    if (__builtin_amdgcn_ballot_w64(ndl > 0.0f) == 0ull) return false;              // behind the surface for the whole wavefront
 #endif
     const f3 sum = {s.v.x + l.x, s.v.y + l.y, s.v.z + l.z};
     const float len_sq = dot_yxz(sum, sum);
@@ -1486,7 +1444,6 @@ AWSM_DI bool light_term(const Lit& s, const void* lights_pre, const void* lights
 }
 }  // namespace lean
 #pragma clang fp contract(fast)
-#endif
 
 // Per-wavefront LDS staging of the per-triangle records (level 1 of the chain).  A 16x4 strip holds a handful of distinct triangles, and the
 // 208 bytes that belong to one — setup record 80, three vertex normals 48, three tangents 48, {info word, three TEXCOORD_0} 32 — used to be
@@ -1507,27 +1464,8 @@ AWSM_DI double2 bits_double2(uint4 v) { return make_double2(__hiloint2double((in
 AWSM_DI uint4 as_uint4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
 
 namespace lean {
-// fetch() for a texture whose record sits in scalar registers (the draw is wave-uniform inside the draw loop): base address in an SGPR pair,
-// 32-bit byte offsets per lane -> global_load ... v_off, s[base]: no 64-bit address arithmetic at all.
-struct TexS { const void* base; uint32_t lw, lh; };
-AWSM_DI TexS decode_s(uint32_t lo, uint32_t hi) { return {reinterpret_cast<const void*>(((unsigned long long)(hi & 0xFFFFu) << 32) | lo), (hi >> 16) & 15u, (hi >> 20) & 15u}; }
-AWSM_DI void fetch_s(const TexS& x, float u, float v, Tap& t) {
-    const float xf = __builtin_amdgcn_ldexpf(u, (int)x.lw) - 0.5f, yf = __builtin_amdgcn_ldexpf(v, (int)x.lh) - 0.5f;     // u * W - 0.5 (W a power of two: exact product)
-    const float flx = floorf(xf), fly = floorf(yf);
-    t.fx = xf - flx; t.fy = yf - fly;
-    const uint32_t xi = (uint32_t)(int)flx, yi = (uint32_t)(int)fly;
-    const uint32_t i0 = __builtin_amdgcn_ubfe(xi, 0u, x.lw), j0 = __builtin_amdgcn_ubfe(yi, 0u, x.lh), j1 = __builtin_amdgcn_ubfe(yi + 1u, 0u, x.lh);
-    const uint32_t sh = x.lw + 2u, i0b = i0 << 2;
-    const u32x2a4 p0 = gload<u32x2a4>(x.base, (j0 << sh) | i0b), p1 = gload<u32x2a4>(x.base, (j1 << sh) | i0b);
-    t.t00 = p0.x; t.t10 = p0.y; t.t01 = p1.x; t.t11 = p1.y;
-    if (__builtin_amdgcn_ubfe(xi + 1u, 0u, x.lw) == 0u) {      // i1 wrapped to column 0
-        t.t10 = gload<uint32_t>(x.base, j0 << sh); t.t11 = gload<uint32_t>(x.base, j1 << sh);
-    }
-}
 // MipmapMode::Gradient: textureSampleGrad by the contract of sample_slot<true> (isotropic LOD from the larger of the two gradient lengths, min / mipmap
-// filters linear, repeat addressing), on a square power-of-two pool array whose record sits in scalar registers (LeanDrawDev.gtex).
-// BASE: const void* — the record sits in scalar registers (a strip inside one draw: loads are 32-bit offsets from an SGPR pair); unsigned long long — per
-// lane (a strip over several draws)
+// filters linear, repeat addressing), on a square power-of-two pool array (LeanDrawDev.gtex).  BASE: as TexT's.
 template <typename BASE> struct TexGT { BASE base; uint32_t lw, levels, layer, layers; };
 typedef TexGT<const void*> TexG;
 typedef TexGT<unsigned long long> TexGL;
@@ -1537,8 +1475,6 @@ AWSM_DI TexG decode_g(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
 AWSM_DI TexGL decode_gl(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
     return {((unsigned long long)(w1 & 0xFFFFu) << 32) | w0, w1 >> 24, (w1 >> 16) & 15u, w2, w3};
 }
-template <typename T> AWSM_DI T gload_any(const void* base, uint32_t off) { return gload<T>(base, off); }
-template <typename T> AWSM_DI T gload_any(unsigned long long base, uint32_t off) { return gload64<T>(base, off); }
 struct Lod { uint32_t lo, hi; float f; };
 // m2 = max(|d uv / dx|^2, |d uv / dy|^2) in uv units; scaling by the extent is exact (a power of two), so rho2 has sample_slot<true>'s bits
 template <typename BASE> AWSM_DI Lod select_lod(const TexGT<BASE>& x, float m2) {
@@ -1663,8 +1599,8 @@ template <typename BASE> AWSM_DI void fetch_q(const TexGT<BASE>& x, const Foot& 
     q.t00 = p0.x; q.t10 = p0.y; q.t01 = p1.x; q.t11 = p1.y;
     if (ft.wrap) { q.t10 = gload_any<uint32_t>(x.base, r0); q.t11 = gload_any<uint32_t>(x.base, r1); }
 }
-AWSM_DI TexG decode_any(const void*, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) { return decode_g(w0, w1, w2, w3); }
-AWSM_DI TexGL decode_any(unsigned long long, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) { return decode_gl(w0, w1, w2, w3); }
+AWSM_DI TexG decode_any(std::true_type, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) { return decode_g(w0, w1, w2, w3); }
+AWSM_DI TexGL decode_any(std::false_type, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) { return decode_gl(w0, w1, w2, w3); }
 struct W8 { float l00, l10, l01, l11, h00, h10, h01, h11; };
 template <int BYTE> AWSM_DI float channel8(const Quad& lo, const Quad& hi, const W8& w) {      // (c_lo (1 - f) + c_hi f with the level weights folded into the eight)
     return ((ub<BYTE>(lo.t00) * w.l00 + ub<BYTE>(lo.t10) * w.l10) + (ub<BYTE>(lo.t01) * w.l01 + ub<BYTE>(lo.t11) * w.l11)) +
@@ -1781,6 +1717,11 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     const uint32_t draw = ts0.x & 0x00FFFFFFu;
     const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)draw, (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(hit)));
     const bool one_draw = __builtin_amdgcn_ballot_w64(hit && draw != d0) == 0ull;
+    // a value at byte `off` of the strip's LeanDrawDev by a scalar load (one: std::true_type, a strip inside one draw) or of the lane's (std::false_type)
+    auto ld = [&](auto one, auto type, uint32_t off) {
+        if constexpr (decltype(one)::value) return cload<decltype(type)>(f.draw_lean, d0 * (uint32_t)sizeof(LeanDrawDev) + off);
+        else return gload<decltype(type)>(f.draw_lean, draw * (uint32_t)sizeof(LeanDrawDev) + off);
+    };
     f2 ddx = {0.0f, 0.0f}, ddy = {0.0f, 0.0f};
     float m2 = 0.0f;      // MipmapMode::Gradient: max(|d uv / dx|^2, |d uv / dy|^2), get_uv_derivatives (helpers/mipmap.wgsl:113-205) as attr_uv<true> forms it
     float r2min = 0.0f; f2 major = {0.0f, 0.0f};      // GRAD == 2 (AWSM_CFG_ANISOTROPIC): the smaller of the two and the longer derivative (grad_footprint)
@@ -1866,11 +1807,11 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
                 if (ex & 8u) lean::fetch_trilinear(lean::decode_g(G3.x, G3.y, G3.z, G3.w), m2e, uu, vv, tg3);
                 if (ex & 16u) lean::fetch_trilinear(lean::decode_g(G4.x, G4.y, G4.z, G4.w), m2e, uu, vv, tg4);
             } else {
-                if (ex & 1u) lean::fetch_s(lean::decode_s(L3.x, L3.y), uu, vv, tp0);
-                if (ex & 2u) lean::fetch_s(lean::decode_s(L3.z, L3.w), uu, vv, tp1);
-                if (ex & 4u) lean::fetch_s(lean::decode_s(L4.x, L4.y), uu, vv, tp2);
-                if (ex & 8u) lean::fetch_s(lean::decode_s(L4.z, L4.w), uu, vv, tp3);
-                if (ex & 16u) lean::fetch_s(lean::decode_s(L5.x, L5.y), uu, vv, tp4);
+                if (ex & 1u) lean::fetch(lean::decode_s(L3.x, L3.y), uu, vv, tp0);
+                if (ex & 2u) lean::fetch(lean::decode_s(L3.z, L3.w), uu, vv, tp1);
+                if (ex & 4u) lean::fetch(lean::decode_s(L4.x, L4.y), uu, vv, tp2);
+                if (ex & 8u) lean::fetch(lean::decode_s(L4.z, L4.w), uu, vv, tp3);
+                if (ex & 16u) lean::fetch(lean::decode_s(L5.x, L5.y), uu, vv, tp4);
             }
             exists = exs;
             if (factors) {
@@ -1920,7 +1861,7 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     };
     float nf = 1.0f;                                                       // grad_footprint's N; the level is chosen for rho_max / N
     if (GRAD == 2) {
-        const uint32_t A = one_draw ? cload<uint32_t>(f.draw_lean, d0 * (uint32_t)sizeof(LeanDrawDev) + 92u) : gload<uint32_t>(f.draw_lean, draw * (uint32_t)sizeof(LeanDrawDev) + 92u);
+        const uint32_t A = one_draw ? ld(std::true_type{}, uint32_t{}, 92u) : ld(std::false_type{}, uint32_t{}, 92u);      // LeanDrawDev.max_anisotropy
         if (A > 1u && m2 > 0.0f) {
             const float Af = (float)min(A, 16u);
             nf = r2min * (Af * Af) <= m2 ? Af : __builtin_sqrtf(m2 / r2min);
@@ -1971,22 +1912,14 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     // record by scalar loads for a strip inside one draw, per lane for a strip over several draws and for the resolve kernel's items. ----
     bool shared_fp = false;
     float Lm = 0.0f;
-    auto lean_word = [&](auto one, uint32_t off) {      // one word of the lane's (or the strip's) LeanDrawDev
-        if constexpr (decltype(one)::value) return cload<uint32_t>(f.draw_lean, d0 * (uint32_t)sizeof(LeanDrawDev) + off);
-        else return gload<uint32_t>(f.draw_lean, draw * (uint32_t)sizeof(LeanDrawDev) + off);
-    };
-    auto lean_quad = [&](auto one, uint32_t off) {
-        if constexpr (decltype(one)::value) return cload<u32x4>(f.draw_lean, d0 * (uint32_t)sizeof(LeanDrawDev) + off);
-        else return gload<u32x4>(f.draw_lean, draw * (uint32_t)sizeof(LeanDrawDev) + off);
-    };
     auto decide = [&](auto one) {
-        const uint32_t fl = lean_word(one, 0u);
+        const uint32_t fl = ld(one, uint32_t{}, 0u);
         const uint32_t exs = (fl & kNeed) == kNeed ? (fl >> 8) & 31u : 0u;
         // bounds over the draw's textures: every lod_t = L + lw_t in (0, levels_t - 1)  <=>  -min lw_t < L < min (levels_t - 1 - lw_t)
         int lw_min = 15, top_min = 15;
 #pragma unroll
         for (uint32_t k = 0; k < (uint32_t)kCoreTextures; k++) {
-            const uint32_t w1 = lean_word(one, 96u + 16u * k + 4u);
+            const uint32_t w1 = ld(one, uint32_t{}, 96u + 16u * k + 4u);
             const int lw = (int)(w1 >> 24), lv = (int)((w1 >> 16) & 15u);
             if (exs & (1u << k)) { lw_min = min(lw_min, lw); top_min = min(top_min, lv - 1 - lw); }
         }
@@ -1999,9 +1932,9 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
         if constexpr (decltype(one)::value) asm volatile("; MARK fetch1"); else asm volatile("; MARK fetch1v");
         lean::W8 w8;
         lean::Quad ql0, qh0, ql1, qh1, ql2, qh2, ql3, qh3, ql4, qh4;
-        const u32x4 L0 = lean_quad(one, 0u), L1 = lean_quad(one, 16u), L2 = lean_quad(one, 32u);
-        const uint32_t L5s = lean_word(one, 88u);
-        const u32x4 G0 = lean_quad(one, 96u), G1 = lean_quad(one, 112u), G2 = lean_quad(one, 128u), G3 = lean_quad(one, 144u), G4 = lean_quad(one, 160u);
+        const u32x4 L0 = ld(one, u32x4{}, 0u), L1 = ld(one, u32x4{}, 16u), L2 = ld(one, u32x4{}, 32u);
+        const uint32_t L5s = ld(one, uint32_t{}, 88u);
+        const u32x4 G0 = ld(one, u32x4{}, 96u), G1 = ld(one, u32x4{}, 112u), G2 = ld(one, u32x4{}, 128u), G3 = ld(one, u32x4{}, 144u), G4 = ld(one, u32x4{}, 160u);
         exists = hit ? (L0.x >> 8) & 31u : 0u;
         const float flL = floorf(Lm), ff = Lm - flL;
         const uint32_t cl = hit ? (uint32_t)(-(int)flL) : 1u;                // log2 of the lower level's extent, >= 1 (L < 0 here)
@@ -2009,13 +1942,11 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
         float fxl, fyl, fxh, fyh;
         lean::footprint(cl, u, v, f_lo, fxl, fyl);
         lean::footprint(cl - 1u, u, v, f_hi, fxh, fyh);
-        typedef decltype(lean::decode_any(std::conditional_t<decltype(one)::value, const void*, unsigned long long>{}, 0u, 0u, 0u, 0u)) TexT;
-        const std::conditional_t<decltype(one)::value, const void*, unsigned long long> tag{};
-        if (exists & 1u) { const TexT x = lean::decode_any(tag, G0.x, G0.y, G0.z, G0.w); lean::fetch_q(x, f_lo, ql0); lean::fetch_q(x, f_hi, qh0); }
-        if (exists & 2u) { const TexT x = lean::decode_any(tag, G1.x, G1.y, G1.z, G1.w); lean::fetch_q(x, f_lo, ql1); lean::fetch_q(x, f_hi, qh1); }
-        if (exists & 4u) { const TexT x = lean::decode_any(tag, G2.x, G2.y, G2.z, G2.w); lean::fetch_q(x, f_lo, ql2); lean::fetch_q(x, f_hi, qh2); }
-        if (exists & 8u) { const TexT x = lean::decode_any(tag, G3.x, G3.y, G3.z, G3.w); lean::fetch_q(x, f_lo, ql3); lean::fetch_q(x, f_hi, qh3); }
-        if (exists & 16u) { const TexT x = lean::decode_any(tag, G4.x, G4.y, G4.z, G4.w); lean::fetch_q(x, f_lo, ql4); lean::fetch_q(x, f_hi, qh4); }
+        if (exists & 1u) { const auto x = lean::decode_any(one, G0.x, G0.y, G0.z, G0.w); lean::fetch_q(x, f_lo, ql0); lean::fetch_q(x, f_hi, qh0); }
+        if (exists & 2u) { const auto x = lean::decode_any(one, G1.x, G1.y, G1.z, G1.w); lean::fetch_q(x, f_lo, ql1); lean::fetch_q(x, f_hi, qh1); }
+        if (exists & 4u) { const auto x = lean::decode_any(one, G2.x, G2.y, G2.z, G2.w); lean::fetch_q(x, f_lo, ql2); lean::fetch_q(x, f_hi, qh2); }
+        if (exists & 8u) { const auto x = lean::decode_any(one, G3.x, G3.y, G3.z, G3.w); lean::fetch_q(x, f_lo, ql3); lean::fetch_q(x, f_hi, qh3); }
+        if (exists & 16u) { const auto x = lean::decode_any(one, G4.x, G4.y, G4.z, G4.w); lean::fetch_q(x, f_lo, ql4); lean::fetch_q(x, f_hi, qh4); }
         metallic_in = __uint_as_float(L0.y); roughness_in = __uint_as_float(L0.z); normal_scale = __uint_as_float(L0.w);
         base = {__uint_as_float(L1.x), __uint_as_float(L1.y), __uint_as_float(L1.z)}; occlusion_strength = __uint_as_float(L1.w);
         emissive = {__uint_as_float(L2.x), __uint_as_float(L2.y), __uint_as_float(L2.z)}; normal_bias = __uint_as_float(L2.w); occlusion_bias = __uint_as_float(L5s);
@@ -2098,17 +2029,12 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
             auto acc3 = [&](const lean::TapG& t, float wj) { const lean::Weights wl = lean::weights(t.lo), wh = lean::weights(t.hi); AWSM_LEAN_ACC(8, 0); };
             auto acc4 = [&](const lean::TapG& t, float wj) { const lean::Weights wl = lean::weights(t.lo), wh = lean::weights(t.hi); AWSM_LEAN_ACC(9, 0); AWSM_LEAN_ACC(10, 1); AWSM_LEAN_ACC(11, 2); };
 #undef AWSM_LEAN_ACC
-            if (one_draw) {
-                const uint32_t lo = d0 * (uint32_t)sizeof(LeanDrawDev);
-#define AWSM_LEAN_PROBE_TEX(K, ACC) { const u32x4 G = cload<u32x4>(f.draw_lean, lo + 96u + 16u * K); probes(lean::decode_g(G.x, G.y, G.z, G.w), (exists & (1u << K)) != 0u, ACC); }
-                AWSM_LEAN_PROBE_TEX(0, acc0) AWSM_LEAN_PROBE_TEX(1, acc1) AWSM_LEAN_PROBE_TEX(2, acc2) AWSM_LEAN_PROBE_TEX(3, acc3) AWSM_LEAN_PROBE_TEX(4, acc4)
+            // (expanded in place, not a lambda over `one`: the extra inlining level renames registers in the GRAD 2 kernels — HISTORY.md)
+#define AWSM_LEAN_PROBE_TEX(K, ACC) { const u32x4 G = ld(one, u32x4{}, 96u + 16u * K); probes(lean::decode_any(one, G.x, G.y, G.z, G.w), (exists & (1u << K)) != 0u, ACC); }
+#define AWSM_LEAN_PROBE_ALL { AWSM_LEAN_PROBE_TEX(0, acc0) AWSM_LEAN_PROBE_TEX(1, acc1) AWSM_LEAN_PROBE_TEX(2, acc2) AWSM_LEAN_PROBE_TEX(3, acc3) AWSM_LEAN_PROBE_TEX(4, acc4) }
+            if (one_draw) { const std::true_type one{}; AWSM_LEAN_PROBE_ALL } else { const std::false_type one{}; AWSM_LEAN_PROBE_ALL }
+#undef AWSM_LEAN_PROBE_ALL
 #undef AWSM_LEAN_PROBE_TEX
-            } else {
-                const uint32_t lo = draw * (uint32_t)sizeof(LeanDrawDev);
-#define AWSM_LEAN_PROBE_TEX(K, ACC) { const u32x4 G = gload<u32x4>(f.draw_lean, lo + 96u + 16u * K); probes(lean::decode_gl(G.x, G.y, G.z, G.w), (exists & (1u << K)) != 0u, ACC); }
-                AWSM_LEAN_PROBE_TEX(0, acc0) AWSM_LEAN_PROBE_TEX(1, acc1) AWSM_LEAN_PROBE_TEX(2, acc2) AWSM_LEAN_PROBE_TEX(3, acc3) AWSM_LEAN_PROBE_TEX(4, acc4)
-#undef AWSM_LEAN_PROBE_TEX
-            }
             const float iw = fm::rcp(wsum);
 #pragma unroll
             for (int i = 0; i < 12; i++) ch[i] *= iw;
@@ -2156,37 +2082,27 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
     sf.metallic = clampf(metallic_in, 0.0f, 1.0f);
     sf.roughness = fmaxf(clampf(roughness_in, 0.0f, 1.0f), 0.04f);
     sf.alpha = sf.roughness * sf.roughness;
-#if AWSM_LEAN_LUT_LATE
     const float ndv = lean::dot_nv(sf.n, sf.v);
-#else
-    const float ndv = fm::fdot(sf.n, sf.v);
-#endif
     sf.n_dot_v_ibl = saturate(ndv);
-#if AWSM_LEAN_LUT_LATE
     lean::LutTap lut_tap;      // the table's four texels are on their way from here; their first use sits behind the deferred lights
     lean::brdf_lut_issue(sc->lut_rg16f, sc->lut_w, sc->lut_h, sf.n_dot_v_ibl, sf.roughness, lut_tap);
-#endif
     sf.n_dot_v_dir = fmaxf(ndv, 1e-4f);
     const float f0b = ior_to_f0(1.5f);
     sf.F0 = mix3(splat3(fminf(f0b, 1.0f)), base, sf.metallic);
     sf.f90 = mixf(1.0f, 1.0f, sf.metallic);
-    sf.sheen_scaling_dir = 1.0f;
     sf.g1_v = geometry_schlick_ggx(saturate(ndv), sf.alpha);
-    sf.cc_n = sf.n;
     sf.df90 = splat3(sf.f90) - sf.F0;
     sf.base_diffuse = base * ((1.0f - sf.metallic) * (1.0f / kPi));
     const float ac = fmaxf(sf.alpha, 0.001f);
     sf.a2 = ac * ac; sf.a2m1 = sf.a2 - 1.0f;
     sf.gk = ((ac + 1.0f) * (ac + 1.0f)) * 0.125f; sf.one_m_gk = 1.0f - sf.gk;
-    sf.has_sheen = false; sf.has_clearcoat = false;
     lean::Lit lit;
     lit.n = sf.n; lit.v = sf.v; lit.F0 = sf.F0; lit.df90 = sf.df90; lit.bd = sf.base_diffuse;
-    lit.ndv_raw = ndv; lit.F0max = fmaxf(fmaxf(sf.F0.x, sf.F0.y), sf.F0.z); lit.df90max = sf.f90 - lit.F0max;
+    lit.F0max = fmaxf(fmaxf(sf.F0.x, sf.F0.y), sf.F0.z); lit.df90max = sf.f90 - lit.F0max;
     lit.ndv_dir = sf.n_dot_v_dir; lit.ndv4 = 4.0f * sf.n_dot_v_dir; lit.a2m1 = sf.a2m1; lit.a2_g1v = sf.a2 * sf.g1_v; lit.gk = sf.gk; lit.one_m_gk = sf.one_m_gk;
     lit.occlusion = occlusion;
     f3 color;
     asm volatile("; MARK ibl");
-#if AWSM_LEAN_LUT_LATE
     // brdf_ibl up to the table; then the first kLeanDeferredLights lights, evaluated while the table's texels are in flight (a term reads neither the
     // table nor `color`: a hundred or two instructions to issue instead of a wait).  The window is unrolled, so the terms sit in registers (static
     // indices, scalar branches on i < n_lights), `live` (scalar) remembers which lights the wavefront did not skip, and the colour is then formed in
@@ -2217,54 +2133,6 @@ AWSM_DI bool lean_core(const DevScene* __restrict__ sc, const FrameDev& f, const
         lean::LightTerm t;
         if (lean::light_term(lit, f.lights_pre, lights, world_position, i, t)) lean::add_term(color, t);
     }
-#else
-    {   // brdf_ibl (brdf.wgsl:517-576): the uniform cubes of the builder default, or texel cubes (brdf.wgsl:268-290: irradiance at level 0 along N,
-        // prefiltered at roughness * (mips - 1) along R) through the shared seam-aware sampler
-        const f3 prefiltered = lean::prefiltered(sc, reflect3(-sf.v, sf.n), sf.roughness);
-        const f3 irradiance = lean::irradiance(sc, sf.n);
-        const float n_dot_v = sf.n_dot_v_ibl;
-        const f3 F_view = fresnel_schlick_f90(n_dot_v, sf.F0, sf.f90);
-        const float F_view_max = fmaxf(fmaxf(F_view.x, F_view.y), F_view.z);
-        const f3 base_layer = (base * (1.0f / kPi)) * irradiance;
-        const float k_d = (1.0f - F_view_max) * (1.0f - sf.metallic);
-        const f3 base_contribution = (base_layer * k_d) * occlusion;
-        const f2 lut = lean::brdf_lut(sc->lut_rg16f, sc->lut_w, sc->lut_h, n_dot_v, sf.roughness);
-        const f3 spec_term = sf.F0 * lut.x + splat3(sf.f90 * lut.y);
-        const f3 specular = (prefiltered * spec_term) * mixf(1.0f, occlusion, 0.5f);
-        color = (base_contribution + specular) + emissive;
-    }
-    asm volatile("; MARK lights");
-    const uint32_t n_lights = min(cload<uint32_t>(sc->buf[AWSM_BUF_LIGHTS_INFO], 0u), f.lights_cap);
-    const void* lights = sc->buf[AWSM_BUF_LIGHTS];
-    for (uint32_t i = 0; i < n_lights; i++) {
-        const f32x4 pre0 = cload<f32x4>(f.lights_pre, i * 32u), pre1 = cload<f32x4>(f.lights_pre, i * 32u + 16u);
-        const uint32_t kind = (uint32_t)pre0.w;
-        f3 light_dir = {pre0.x, pre0.y, pre0.z}, radiance = {pre1.x, pre1.y, pre1.z};
-        if (kind == 2u || kind == 3u) {
-            const f32x4 pos_range = cload<f32x4>(lights, i * 64u);
-            const f3 stl = mk3(pos_range.x, pos_range.y, pos_range.z) - world_position;
-            const float d2 = fm::fdot(stl, stl);
-            const float inv_d = d2 > 0.0f ? fm::rsq(d2) : 0.0f;
-            const float dist = d2 * inv_d;
-            float att;   // math.wgsl:12-19 inverse_square
-            if (pos_range.w == 0.0f) att = fm::rcp(fmaxf(dist * dist, 0.01f));
-            else { const float fo = 1.0f - fm::fdiv(dist * dist, pos_range.w * pos_range.w); att = fm::fdiv(saturate(fo * fo), dist * dist + 1.0f); }
-            const f3 to_light = stl * inv_d;
-            if (kind == 3u) {
-                const f32x4 dir_inner = cload<f32x4>(lights, i * 64u + 16u), kind_outer = cload<f32x4>(lights, i * 64u + 48u);
-                const float cos_l = fm::fdot(to_light, -light_dir);
-                const float sm = saturate(fm::fdiv(cos_l - kind_outer.y, dir_inner.w - kind_outer.y));
-                att = att * (sm * sm);
-            }
-            light_dir = to_light;
-            radiance = radiance * att;
-#ifndef AWSM_NO_LIGHT_SKIP
-            if (__builtin_amdgcn_ballot_w64(!(att == 0.0f)) == 0ull) continue;      // out of the light's range (or cone) for the whole wavefront: the term is exactly zero
-#endif
-        } else if (kind != 1u) { light_dir = {0.0f, 0.0f, 0.0f}; radiance = {0.0f, 0.0f, 0.0f}; }
-        lean::direct(lit, light_dir, radiance, color);
-    }
-#endif
     asm volatile("; MARK store");
     if (ITEMS) { item->color = color; return true; }
     store_pixel(f, p, {color.x, color.y, color.z, 1.0f});
